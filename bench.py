@@ -37,6 +37,7 @@ MEASURED_READ_GBS = 6400.0  # what a plain 16 B/lane read kernel reaches on this
 # timed region, more than the 256 MiB Infinity Cache can hold, so the read stream comes from HBM
 LARGE_SCANS = 9
 STREAM_BYTES = 300 * 1024 * 1024  # input the small-scan workloads' timed region cycles through (> the 256 MiB Infinity Cache)
+DUMP_BYTES = 64 * 1024 * 1024  # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -50,7 +51,8 @@ def parse():
     ap.add_argument("--devices", default="",
                     help="comma-separated device of every local rank (default: local rank r -> device r); '0,0' = two ranks on device 0")
     ap.add_argument("--steps", type=int, default=None,
-                    help="timed steps (default: 625 steps of 16 scans for the small-scan workloads, 10000 scans otherwise)")
+                    help="timed steps (default: 625 steps of 16 scans for the small-scan workloads, 200 routed steps for c5, "
+                         "10000 scans otherwise)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--scans-per-step", type=int, default=0,
                     help="scans one step hands to the hot path: 0 = 16 for the workloads the batch pipeline takes (c2, c3: a "
@@ -88,16 +90,21 @@ def parse():
     ap.add_argument("--collective-timeout", type=int, default=120,
                     help="seconds a collective may take before RCCL aborts it (a rank that failed leaves with a non-zero "
                          "exit code at once; its peers follow when this expires)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (rank 0's map: every layer with its non-finite "
+                         "cells coded beside it, its geometry, the last scan's statistics) as DIR/<name>.npy, so that two "
+                         "builds can be compared output for output")
     a = ap.parse_args()
     if a.gpus is None:
         a.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
     small = a.workload in ("c2", "c3") and (a.scans_per_step or 16) > 1
+    routed = a.workload == "c5" and (a.gpus > 1 or a.routed)
     if a.steps is None:
-        a.steps = 625 if small else 10000
+        a.steps = 625 if small else 200 if routed else 10000
     if a.warmup is None:
-        a.warmup = 64 if small else 1000
+        a.warmup = 64 if small else 400 if routed else 1000
     return a
 
 
@@ -105,6 +112,40 @@ def colmajor16(T):
     import numpy as np
     a = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4).T).reshape(16)
     return (C.c_double * 16)(*a.tolist())
+
+
+def dump_outputs(eng, out_dir, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: what a caller of the timed path receives from the engine, as out_dir/<name>.npy, every value
+    finite — each layer as float32, rows x cols in the map's storage order (`color` as its packed bit patterns), with its
+    non-finite cells (unobserved: NaN) written as 0 and `_nonfinite_<layer>` beside it (float32, same shape: 0 finite,
+    1 NaN, 2 +inf, 3 -inf); `_geometry` (float64: the FdmGeometry fields in order) and `_scan_stats` (float64: the last
+    scan's FdmScanStats fields in order).  Layers larger than `budget` in all are written as the same seeded sample of
+    cells for each, `_sample_cells` holding their flat column-major indices (float64).  ('_' never starts the name of a
+    layer a caller sees: tiling.visible_layers.)"""
+    import numpy as np
+    from fastdem_amd import capi, tiling
+    os.makedirs(out_dir, exist_ok=True)
+    eng.sync()
+    names = tiling.visible_layers(eng.layers())
+    g = eng.geometry()
+    np.save(os.path.join(out_dir, "_geometry.npy"),
+            np.array([getattr(g, f) for f, _ in capi.FdmGeometry._fields_], dtype=np.float64))
+    _, st = eng.last_stats()
+    np.save(os.path.join(out_dir, "_scan_stats.npy"), np.array([st[f] for f, _ in capi.FdmScanStats._fields_], dtype=np.float64))
+    n_cells = eng.s_rows * eng.s_cols
+    idx = None
+    if 8 * n_cells * len(names) > budget - (1 << 20):
+        per_cell = 8 * len(names) + 8  # (values + non-finite codes of every layer, and the index)
+        idx = np.unique(np.random.default_rng(seed).integers(0, n_cells, (budget - (1 << 20)) // per_cell))
+        np.save(os.path.join(out_dir, "_sample_cells.npy"), idx.astype(np.float64))
+    for name in names:
+        a = eng.layer(name)
+        if idx is not None:
+            a = a.ravel(order="F")[idx]
+        code = (np.isnan(a) + 2 * np.isposinf(a) + 3 * np.isneginf(a)).astype(np.float32)
+        base = name.replace(os.sep, "_")
+        np.save(os.path.join(out_dir, base + ".npy"), np.where(code == 0, a, np.float32(0)))
+        np.save(os.path.join(out_dir, "_nonfinite_" + base + ".npy"), code)
 
 
 class Resident:
@@ -560,6 +601,8 @@ def main():
     if routed:
         from fastdem_amd import tiling
         args.stall_timeout = args.collective_timeout + 60
+        if args.dump_outputs and rank == 0:
+            args.dump_engine = lambda eng: dump_outputs(eng, args.dump_outputs)
         result = tiling.bench_global(args, rank, local_rank, world)
     else:
         kw = {"order": args.order} if args.workload in ("c2", "c4") else {}
@@ -593,13 +636,15 @@ def main():
         sps = args.scans_per_step or (16 if args.workload in ("c2", "c3") else 1)
         n_timed, n_warm = args.steps * sps, args.warmup * sps
 
-        def timed_region(r, k0):
+        def timed_region(r, k0, dump_dir=None):
             """warm-up, then the K timed steps as ONE call across the language boundary (fdm_engine_integrate_device_batch:
             K x fdm_engine_integrate_device in C++; with a Python / ctypes call per 6 us scan the region would measure the
             interpreter), K scans + the last scan's held-back update between two HIP events on the engine's stream.
             A region shorter than 5 ms (the driver's `--steps 20 --warmup 5` is 0.4 ms at configs[1]) is one launch latency
             and one sync away from noise: the IDENTICAL K-step region — barrier + synchronize on both sides each time —
             is then repeated `args.repeats` times on fresh scans and the MEDIAN is reported, with min / max beside it.
+            `dump_dir`: the engine's outputs after the warm-up and the first K timed steps go there (--dump-outputs), so
+            that they do not depend on whether the region was short enough to be repeated.
             Returns (wall seconds incl. the final sync [median], points, HIP-event us per scan, scans per launch, next k,
             the list of wall seconds of every repeat)."""
             reps_max = max(1, args.repeats)
@@ -629,6 +674,8 @@ def main():
 
             dt_, pts_, us_, bs_ = one(k)
             k += n_timed
+            if dump_dir:
+                dump_outputs(r.eng, dump_dir)
             wall, dev = [dt_], [us_]
             again = 1 if (dt_ < 5e-3 and reps_max > 1) else 0
             if world > 1:  # every rank repeats or none does
@@ -645,7 +692,7 @@ def main():
 
         for kk in range(args.profile_steps + 8):
             res.pose(n_warm + n_timed + kk)
-        dt, pts, timed_launch_us, batch_scans, k, wall_reps = timed_region(res, 0)
+        dt, pts, timed_launch_us, batch_scans, k, wall_reps = timed_region(res, 0, args.dump_outputs if rank == 0 else None)
         if world > 1:  # the MAX over ranks of every repeat, then the median
             dist.barrier()
             t = torch.tensor(wall_reps, dtype=torch.float64, device=f"cuda:{local_rank}" if args.backend == "nccl" else "cpu")
@@ -843,11 +890,13 @@ def main():
         # node share ONE map is BASELINE configs[4]; its line for the same N rides along, so that a 1 / 2 / 4 / 8 sweep
         # of the default command has rows for both.
         from fastdem_amd import tiling
-        args.stall_timeout = args.collective_timeout + 60
+        gargs = argparse.Namespace(**vars(args))
+        gargs.steps, gargs.warmup = min(args.steps, 200), min(args.warmup, 400)  # (a leg beside `value`: kept short)
+        gargs.stall_timeout = args.collective_timeout + 60
         # (this leg has never run on two devices: whatever happens in it, the replicas' line above is printed)
-        args.global_map_fatal = False
-        args.partial_result = result if rank == 0 else None
-        g = tiling.bench_global(args, rank, local_rank, world)
+        gargs.global_map_fatal = False
+        gargs.partial_result = result if rank == 0 else None
+        g = tiling.bench_global(gargs, rank, local_rank, world)
         if rank == 0:
             result["global_map"] = g
             result["global_map_ok"] = bool(g) and "error" not in g

@@ -59,6 +59,16 @@ def device_us_per_scan(gpu, wl, warm, timed, raycast=0, reps=5, **options):
     return best
 
 
+@pytest.fixture
+def own_choice(gpu):
+    """The guards time the engine's OWN pipeline choice, the one profiles/r06/perf_guard.json measured: whichever
+    fixture variant runs them, the engines they build take no forced options."""
+    saved = gpu.Engine.default_options
+    gpu.Engine.default_options = {}
+    yield gpu
+    gpu.Engine.default_options = saved
+
+
 CASES = [("c2", dict(n_scans=16), 160), ("c3", dict(n_scans=8), 96), ("c4", dict(n_scans=4), 40), ("c5", dict(n_scans=4), 40)]
 RAY_CASES = [("c2", dict(n_scans=16), 96), ("c3", dict(n_scans=4), 16), ("c4", dict(n_scans=3), 8)]
 
@@ -72,16 +82,14 @@ def check(name, us, key):
 
 
 @pytest.mark.parametrize("name,kw,timed", CASES, ids=[c[0] for c in CASES])
+@pytest.mark.usefixtures("own_choice")
 def test_integrate_stays_within_reach_of_the_measured_time(gpu, name, kw, timed):
-    if gpu.Engine.default_options:
-        pytest.skip("the engine's own pipeline choice only (the other fixture variant forces slower paths on purpose)")
     check(name, device_us_per_scan(gpu, gpu.synth.make(name, **kw), 32, timed), "integrate_us")
 
 
 @pytest.mark.parametrize("name,kw,timed", RAY_CASES, ids=[c[0] for c in RAY_CASES])
+@pytest.mark.usefixtures("own_choice")
 def test_raycasting_stays_within_reach_of_the_measured_time(gpu, name, kw, timed):
-    if gpu.Engine.default_options:
-        pytest.skip("the engine's own pipeline choice only")
     check(name, device_us_per_scan(gpu, gpu.synth.make(name, **kw), 8, timed, raycast=1), "raycast_us")
 
 
@@ -112,11 +120,10 @@ def stage_ms(gpu, reps=5, iters=20):
     return out
 
 
+@pytest.mark.usefixtures("own_choice")
 def test_stencil_stages_stay_within_reach_of_the_measured_time(gpu):
     """Uncertainty fusion and feature extraction at their default radii (round 6: 0.219 -> 0.090 ms and 0.254 -> 0.121 ms
     on the 1200 x 1200 map; the kernels are bound by instruction issue, so a slip is a compiler or a code change)."""
-    if gpu.Engine.default_options:
-        pytest.skip("the engine's own pipeline choice only")
     if "stage_ms" not in MEASURED:
         pytest.skip("profiles/r06/perf_guard.json holds no stage times")
     got = stage_ms(gpu)
@@ -127,13 +134,12 @@ def test_stencil_stages_stay_within_reach_of_the_measured_time(gpu):
                               f"ceiling {ceiling:.4f} (x {MARGIN} x box scale {scale:.2f}: 256 MiB copy {copy_ms:.3f} ms here)")
 
 
+@pytest.mark.usefixtures("own_choice")
 def test_an_enqueue_only_stream_gets_its_batch_launches_back_behind_a_host_write(gpu):
     """A host write of the obstacle layer (or a pipeline switch) leaves a whole-layer clear owed; until a scan that observed
     a cell has paid it every scan is "not plain": no fused launch, no batch launch, two extra launches per scan.  The
     host learns that the debt is paid from pinned memory, WITHOUT a sync — an enqueue-only caller must be
     back in batch launches a few scans later, and at the usual time per scan."""
-    if gpu.Engine.default_options:
-        pytest.skip("the engine's own pipeline choice only")
     import bench
     wl = gpu.synth.make("c2", n_scans=16)
     res = bench.Resident(wl, 0)
