@@ -542,8 +542,10 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   }
   HIPCK(hipGetLastError());
   if (e->profile) HIPCK(hipEventRecord(e->ev[1], e->stream));
-  // (option "ray_overlap": this scan's stage may start as soon as its bin half has run — marked HERE, ahead of the wait for
-  //  the previous scan's stage that run_held_ray_stage is about to put on this stream)
+  // (option "ray_overlap": this scan's early stage waits for its bin half — marked HERE, ahead of the previous scan's stage
+  //  that run_held_ray_stage is about to put on this stream.  So this mark orders the early stage against the bin only;
+  //  against that previous stage, which uses the buffers of its bank, it is ordered by ev_ray_res[bank], which
+  //  run_held_ray_stage records behind it on either path and start_ray_stage_early waits for as well)
   e->ray_bin_marked = false;
   if (ray_held && e->ray_overlap && e->ray_stream[0]) {
     HIPCK(hipEventRecord(e->ev_ray_bin, e->stream));

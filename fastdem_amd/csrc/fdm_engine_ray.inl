@@ -497,6 +497,12 @@ int run_held_ray_stage(fdm_engine* e, fdm_engine::PendingUpdate& u) {
                                u.ray_box, &key_mode)))
     return rc;
   if ((rc = enqueue_ray_stage(e, u.RQ, true, u.ray_x, u.ray_y, u.ray_z, key_mode))) return rc;
+  // (option "ray_overlap": this stage ran on the main stream in bank 0.  The next early stage of context 0 may already be
+  //  waiting only for a bin half enqueued AHEAD of this stage (enqueue_scan's ev_ray_bin): it waits for this mark too)
+  if (e->ray_stream[0]) {
+    HIPCK(hipEventRecord(e->ev_ray_res[0], e->stream));
+    e->ray_res_pending[0] = true;
+  }
   if (e->profile) {
     HIPCK(hipEventRecord(e->ev_ray[1], e->stream));
     e->ray_timed = true;

@@ -12,7 +12,8 @@ against the oracle: a seeded generator of >= 3 000 scans on a small LOCAL map mi
   * poses that shift the rolling window by fractions of a cell, by many cells and by more than the map;
   * host writes between the calls: `set_layer` of the obstacle / elevation layer, `clear(layer)`, `clearAll`, a user layer;
   * estimator switches at run time (fastdem.cpp:34-38), raycasting on and off (fastdem.cpp:152-159);
-  * every entry point: batch call, enqueue-only scan by scan, the synchronous host call, the pageable host batch.
+  * every entry point: batch call, enqueue-only scan by scan, the synchronous host call, the pageable host batch;
+  * two seeds with option `ray_overlap` (1 and -1): early raycasting stages beside normal-path ones in every order.
 
 Behind every call: the obstacle and elevation layers bit for bit; every 50 scans and at the end: layer names, every layer
 bit for bit (NaN pattern, signs of zeros), geometry, the last scan's statistics.  Through the C ABI.  `scripts/long_horizon_prefix.py` runs this file against a build of the tree before
@@ -150,7 +151,10 @@ def compare(eng, ref, what, names=None):
     assert same_geometry(eng.geometry(), ref.geometry()), what
 
 
-N_SCANS = {2026: 12000, 7: 6000, 31: 6000}
+N_SCANS = {2026: 12000, 7: 6000, 31: 6000, 4099: 12000, 4111: 12000}
+# seeds run with option ray_overlap (two raycasting stages in flight; voxel_small left on): the sizes straddle
+# `voxel_small_max` and `ray_large_min` and the entry points mix, so stages of either path meet in every order
+RAY_OVERLAP = {4099: 1, 4111: -1}
 TRACE = None   # scripts/soak_oracle_repro.py: a list that takes one record per call (what the call looked like)
 HOOK = None    # ... and a callable(call number, eng, ref, scans, poses, Tbs) -> True if it integrated the call's scans itself
 
@@ -167,6 +171,8 @@ def test_thousands_of_scans_against_the_oracle(gpu, R, seed):
     eng.set_option("voxel_small_max", VOXEL_SMALL_MAX)
     if seed == 31:
         eng.set_option("batch_max", 32)   # (Kalman takes 16 scans per launch by default: the 32-scan layout of the update half here too)
+    if seed in RAY_OVERLAP:
+        eng.set_option("ray_overlap", RAY_OVERLAP[seed])
     g = Gen(seed)
     rng = g.rng
     Tbs = T(0.0, 0.0, 1.2)
