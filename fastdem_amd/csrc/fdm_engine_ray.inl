@@ -110,7 +110,10 @@ void launch_voxel_keys(fdm_engine* e, unsigned n, float inv, int flag_slot, cons
 VoxelCompact voxel_compact_of(float voxel_size, const double* box) {
   const float inv = 1.0f / voxel_size;  // voxel_grid_impl.hpp:46
   VoxelCompact C{0, 0, 0, 0, 0};
-  if (box && std::isfinite(box[3]) && box[3] > 0.0 && box[3] * double(inv) < 4.0e6) {
+  // (a centre beyond 1e9 voxels would overflow the int corner below: every index of it clamps anyway, full key)
+  const auto near = [&](double v) { return std::fabs(v) * double(inv) < 1.0e9; };
+  if (box && std::isfinite(box[3]) && box[3] > 0.0 && box[3] * double(inv) < 4.0e6 && near(box[0]) && near(box[1]) &&
+      near(box[2])) {
     const double half = box[3] + 2.0 * double(voxel_size);  // 2-cell margin for the float transforms
     const int span = int(std::ceil(2.0 * half * double(inv))) + 4;
     int bits = 1;
@@ -132,6 +135,12 @@ VoxelCompact voxel_compact_of(float voxel_size, const double* box) {
           C.z0 = int(std::floor(zlo * double(inv))) - 1;
         }
       }
+      // The reference key clamps every voxel index to [-2^20, 2^20 - 1] (voxel.hpp:28-43): far from the origin (UTM
+      // northings: 5.3e6 m / 0.2 m = 2.7e7) all points of a scan collapse onto a few clamped voxels.  The rebased key
+      // does not clamp, so it is only the same key when no index of the box reaches the clamp; otherwise the full key.
+      constexpr long long kMin = -(1ll << 20), kMax = (1ll << 20) - 1;
+      const auto inside = [&](int lo, int b) { return lo >= kMin && (long long)lo + (1ll << b) - 1 <= kMax; };
+      if (!inside(C.x0, C.bits) || !inside(C.y0, C.bits) || !inside(C.z0, C.zbits)) C = VoxelCompact{0, 0, 0, 0, 0};
     }
   }
   return C;
