@@ -339,7 +339,12 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   K.has_var = hv ? 1 : 0;
   K.bin_table = e->bin_table;
   K.dbg = e->dbg_batch;
-  K.walk = e->batch_walk < 0 ? (e->cfg.estimation_type == 1 ? 1 : 0) : e->batch_walk;
+  // the chain of moves walked one launch ahead (mwalk_body): automatic = every scan of a quantile-estimator batch; for
+  // Kalman without the ray stage only the scans from kKalmanWalkFrom on (the longest chains) — the earlier rows walk their
+  // own, which staggers their flushes behind the update half (profiles/r07: all rows at once, 17.6 us per launch against
+  // 15.6; rows 12-15 only, 24.2 -> 25.2 G pts/s); 1 = every scan of every batch
+  K.walk = e->batch_walk < 0 ? ((e->cfg.estimation_type == 1 || !ray) ? 1 : 0) : e->batch_walk;
+  K.walk_from = (e->batch_walk < 0 && e->cfg.estimation_type != 1) ? kKalmanWalkFrom : 0;
 
   const unsigned seq = e->mseq++;
   const int slot = int(seq % unsigned(kMStates)), par = int(seq & 1u);

@@ -29,9 +29,10 @@
 //                entries are compacted and flushed with memory-side atomics on the block's unique cells.
 //                No second look at the scan: the thread that merges a block-local minimum into the scratch also
 //                evaluates that point's sigma_z^2 (the block keeps its points' sensor-frame coordinates in LDS) and
-//                stores {map-frame z, sigma_z^2} at the POINT's index in an observation array; likewise the colour
-//                of a block-local last point.  The update finds the winner's entry through the index in the
-//                reduced key, and the caller's arrays are dead as soon as the launch has run.
+//                stores {map-frame z, sigma_z^2} in an observation array at the block's SLOT for the cell (lb * kMBlock
+//                + the cell's rank in the block's compacted list: a block's winners are one contiguous run); likewise
+//                the colour of a block-local last point.  The update finds the winner's entry through the slot in the
+//                reduced key (aux.w for the colour), and the caller's arrays are dead as soon as the launch has run.
 //   update half  64 cells per block (memory order), four threads per cell.  Round trip 1: the cell's keys of
 //                all scans (four scans per thread), its estimator record, the per-scan geometry.  The block's
 //                (cell, scan) events are then compacted into an LDS list (kEvCap entries) and spread evenly over
@@ -63,6 +64,7 @@ constexpr int kLineWords = 32;           // a 128-byte line of 32-bit words
 #ifndef FDM_MB_WAVES
 #define FDM_MB_WAVES 6  // waves per SIMD k_mbatch is compiled for (<= 80 VGPRs; the LDS allows 6 blocks per CU): every block of a 16-scan VLP-16 batch resident at once
 #endif
+constexpr int kKalmanWalkFrom = 12;     // Kalman batches: the first scan whose bin blocks take the walker's chain (fdm_engine_multi.inl)
 constexpr int kMStates = 4;              // ring of batch states: update b-1 | bin b | crop b+1 | being re-armed
 
 // Device-resident bookkeeping of one batch.  Every word other blocks poll or add to sits on its own 128-byte
@@ -83,6 +85,7 @@ struct MCommon {  // what all scans of a batch share
   float Tbs[16];  // T_base_sensor (one sensor per batch: a scan with another extrinsic closes the batch)
   int sensor_type, integrate_mode, do_move, gate_on_filter, has_var, bin_table;
   int dbg, walk;                 // walk: 1 = the chain of moves is walked one launch ahead (mwalk_body).  dbg, measurement only: 1 = no scratch atomics, 2 = no chain walk (both: wrong results); 3 = every move by the reference's divide; 4 = a chain wait reports MState::err as if it had run out of polls (tests)
+  int walk_from, pad;            // with walk: scans k >= walk_from take the pre-walked chain, the bin blocks of earlier scans walk their own
   unsigned long long* timeline;  // measurement only (nullable): {start, end} of every block in 100 MHz ticks
 };
 struct MScanT {   // per scan: T_world_base without its constant last row (0 0 0 1), column-major 3 x 4 | rotation of the product
@@ -102,8 +105,8 @@ struct MBin {     // bin half: batch b
   unsigned long long* key;
   uint4* aux;
   uint2* zs;
-  float2* obs;                           // [count][obs_stride] {map-frame z, sigma_z^2} of block-local minima, by point index
-  uint32_t* cobs;                        // [count][obs_stride] colour of block-local last points, by point index
+  float2* obs;                           // [count][obs_stride] {map-frame z, sigma_z^2} of block-local minima, by slot (mbin_body's merge)
+  uint32_t* cobs;                        // [count][obs_stride] colour of block-local last points, by slot
   unsigned long long* bin_part;          // [bin blocks]
   float* cap;                            // raycasting: [3][count][obs_stride] map-frame x (NaN: dropped by the crops), y, z by point index (else null)
   double robot_x[kMaxBatch], robot_y[kMaxBatch];  // T_world_base translation of every scan (the chain of moves)
@@ -223,7 +226,7 @@ struct MBinLds {
   DevCand s_cand;
   unsigned s_pass[4], s_in[4], s_occ[4 * kMPts];
 };
-struct MEvent { uint32_t idx; uint16_t cell, k; };  // winner's point index | cell in tile | scan
+struct MEvent { uint32_t idx; uint16_t cell, k; };  // winner's slot in obs | cell in tile | scan
 struct MObs { float min_z, var, max_z, iobs; };
 constexpr unsigned kUpdCells = 64u;   // cells per update block at most (MUpd::tpc == 4; 32 with eight threads per cell)
 __host__ __device__ constexpr unsigned upd_threads_per_cell(unsigned count) { return count > 16u ? 8u : 4u; }
@@ -288,8 +291,12 @@ __device__ __forceinline__ void mcrop_body(const MCrop& Cn, const MCommon& K, co
 // per scan; configs[1] (Kalman; 16 us launches) unchanged on streamed inputs and SLOWER on cache-resident ones (1.02 ->
 // 1.30 us per scan): that launch is bound by its memory-side atomics, the chains staggered the sixteen rows of bin blocks
 // by 0.3 us each and left the update half the first microseconds — all rows at once make the update half the last to
-// finish (phase stamps: 13.6 -> 17.1 us).  So the walker is ON for the quantile estimator and OFF for Kalman by default
-// (option "batch_walk": -1 automatic, 0 off, 1 on).  The walk itself is the reference's sequence, scan by scan: geometry before scan
+// finish (phase stamps: 13.6 -> 17.1 us; measured again with the compact winner slots of mbin_body's merge: rocprof
+// 15.6 -> 17.6 us per launch, profiles/r07).  Taking the walker's chain only in the rows of the longest chains keeps the
+// stagger of the early rows and takes the tail off the late ones: scans >= 12 of a 16-scan Kalman batch
+// (MCommon::walk_from, kKalmanWalkFrom; profiles/r07: 24.2 -> 25.2 G pts/s against 10, 13 or 14 within 0.4 %).  So by
+// default the walker serves every scan with the quantile estimator, scans 12+ with Kalman without the ray stage, none
+// with Kalman and raycasting (option "batch_walk": -1 automatic, 0 off, 1 on for every scan).  The walk itself is the reference's sequence, scan by scan: geometry before scan
 // k + 1 = scan k's candidate if scan k moved the map, else unchanged — the same numbers the per-block walk produces
 // (it defers the index wrap of short moves, which yields the candidate's wrapped index).
 //
@@ -483,7 +490,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     return __hiloint2double(hi, lo);
   };
   auto chain = [&](unsigned passmask) {  // (every lane of the first wavefront, uniformly)
-    if (K.do_move && K.walk && K.dbg != 2 && K.dbg != 3 && uni(w_valid) != 0u &&
+    if (K.do_move && K.walk && K.dbg != 2 && K.dbg != 3 && k >= unsigned(K.walk_from) && uni(w_valid) != 0u &&
         ((uni(w_pre) ^ passmask) & lowbits(k)) == 0u) {  // pre-walked (mwalk_body): nothing to walk
       if (threadIdx.x == 0) {
         S.s_cand = c_pre;
@@ -622,9 +629,18 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   uint32_t* const S_cobs = B.cobs + size_t(k) * B.obs_stride;
 
   // one cell's reduction goes to the scan's scratch; the merging thread also leaves what the update needs of the
-  // block-local winner / last point at the POINT's index
-  auto merge = [&](uint32_t c, unsigned long long key, uint32_t zmx, uint32_t imx, uint32_t fst, uint32_t lst) {
+  // block-local winner / last point in the block's SLOT for the cell: slot = lb * kMBlock + j, j = the cell's rank in
+  // the block's compacted list.  The slot replaces the point index in the low word of the key and in aux.w, so that
+  // a block's observations form one contiguous run (a few lines) instead of one isolated store per cell, and the
+  // update's gather of neighbouring cells shares lines.  Order is kept: block lb owns points [lb kMBlock, lb kMBlock
+  // + kMBlock) and holds one entry per cell, so a lower slot on equal ord(z) is still the earlier point (strict "<",
+  // elevation_mapping.cpp:41-92), and a higher slot is still the later last point.  j < the block's inside points, so
+  // slot < n: inside the scan's slot of obs / cobs and never kNoIdx.  fst and zs stay point indices (never gathered).
+  auto merge = [&](uint32_t c, unsigned long long key, uint32_t zmx, uint32_t imx, uint32_t fst, uint32_t lst,
+                   uint32_t slot) {
     if (K.dbg == 1) return;
+    const uint32_t idx = uint32_t(key);  // the block-local winner's point index (kNoIdx: no finite z below FLT_MAX)
+    if (idx != kNoIdx) key = (key & 0xFFFFFFFF00000000ull) | slot;
     atomicMin(&S_key[c], key);
     uint32_t* a = S_aux + size_t(c) * 4;
     if (zmx) atomicMax(a + 0, zmx);
@@ -633,16 +649,15 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
       atomicMin(a + 2, fst);
     }
     if (has_col) {
-      atomicMax(a + 3, lst);
-      S_cobs[lst] = B.prgb[k][lst];
+      atomicMax(a + 3, slot);
+      S_cobs[slot] = B.prgb[k][lst];
     }
-    const uint32_t idx = uint32_t(key);
     if (idx != kNoIdx) {
       const float4 p = S.s_pt[idx - lb * kMBlock];
       float var = 0.0f;  // CellObservation default (elevation_mapping.hpp:26-34)
       if (K.has_var) var = B.pvar[k][idx];
       else if (K.integrate_mode) var = sigma_z2(V, p.x, p.y, p.z);
-      S_obs[idx] = make_float2(p.w, var);
+      S_obs[slot] = make_float2(p.w, var);
     }
   };
 
@@ -780,7 +795,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   __syncthreads();
   for (unsigned j = threadIdx.x; j < n_occ; j += 256u) {
     const unsigned t = S.s_list[j];
-    merge(S.t_cell[t], S.t_key[t], S.t_zmx[t], S.t_imx[t], S.t_fst[t], S.t_lst[t]);
+    merge(S.t_cell[t], S.t_key[t], S.t_zmx[t], S.t_imx[t], S.t_fst[t], S.t_lst[t], lb * kMBlock + j);
   }
   if (threadIdx.x == 0) {
     const unsigned ni = S.s_in[0] + S.s_in[1] + S.s_in[2] + S.s_in[3];
