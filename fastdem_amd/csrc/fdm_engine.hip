@@ -1366,6 +1366,10 @@ static int route_scan_impl(fdm_engine* e, const fdm_route_plan* plan, uint64_t n
   if (n && (!dx || !dy || !dz || !d_send)) return fail(FDM_ERR_INVALID, "null xyz / send buffer");
   if (n >= 0x7FFFFFFFull) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
   if (e->cfg.mode != 1) return fail(FDM_ERR_INVALID, "scan routing is defined for GLOBAL maps");
+  // an owner's ray stage would see only the points of its share, but rays from the rest of the scan cross its cells:
+  // its ghost removal would differ from the single map's
+  if (e->cfg.raycast_enabled)
+    return fail(FDM_ERR_INVALID, "scan routing cannot reproduce raycasting: disable raycast_enabled on routed engines");
   HIPCK(hipSetDevice(e->device));
   RoutePlan R{};
   R.world = plan->world; R.pr = plan->grid_rows; R.pc = plan->grid_cols;

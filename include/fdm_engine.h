@@ -286,7 +286,9 @@ int fdm_engine_regions_unpack(fdm_engine* e, int32_t n_rects, const fdm_region* 
  * d_counts (device, world + 2 words) receives the points per owner, then the slice's n_after_filter and n_in_map.
  * Enqueue-only on the engine's stream; the host reads d_counts to size the exchange (fdm_halo_route_exchange).
  * The plan: owned rect of rank i * grid_cols + j = rows [row_edge[i], row_edge[i+1]) x cols [col_edge[j], col_edge[j+1])
- * (fdm_tile_plan_route).  GLOBAL mode only.
+ * (fdm_tile_plan_route).  GLOBAL mode only, and raycasting off: an owner's ray stage would see only its own share, while
+ * rays from every other point of the scan cross its cells, so the call fails with FDM_ERR_INVALID when the engine's
+ * config has raycast_enabled set.
  *
  * fdm_engine_integrate_points4_device: FastDEM::integrate of the points an owner received ({x, y, z, intensity}
  * records in HBM, rank order = scan order).  any_in_map: some point of the LOGICAL scan landed in the map (the OR over
