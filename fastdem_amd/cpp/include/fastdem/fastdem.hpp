@@ -32,6 +32,7 @@ class FastDEM {
   FastDEM(ElevationMap& map, const Config& cfg) : map_(map), cfg_(cfg) {
     sensor_model_ = createSensorModel(cfg_.sensor_model);
     mapping_ = std::make_unique<ElevationMapping>(map_, cfg_);
+    bound_ = map_.engineSerial();
   }
   ~FastDEM() {
     try { drain(); } catch (...) {}  // (queued clouds are borrowed: the GPU must be done with them)
@@ -202,6 +203,7 @@ class FastDEM {
       return last;
     }
     drain();
+    rebind();
     map_.flushToDevice();
     const fdm_config f = detail::toEngineConfig(effectiveConfig());
     detail::ck(fdm_engine_set_config(map_.engine(), &f), "fdm_engine_set_config");
@@ -279,6 +281,7 @@ class FastDEM {
       else if (name == "rgb" || name == "rgba") lay.off_rgb = int32_t(f.offset);
     }
     const uint64_t n = uint64_t(msg.width) * uint64_t(msg.height);
+    rebind();
     map_.flushToDevice();
     const fdm_config f = detail::toEngineConfig(effectiveConfig());
     detail::ck(fdm_engine_set_config(map_.engine(), &f), "fdm_engine_set_config");
@@ -352,6 +355,7 @@ class FastDEM {
   bool integrateQueued(const PointCloud& cloud, const Eigen::Isometry3d& T_base_sensor,
                        const Eigen::Isometry3d& T_world_base) {
     {
+      rebind();
       map_.flushToDevice();  // (host writes to the map since the last call; nothing to do when there were none)
       if (cfg_dirty_) {      // (the engine takes its parameters when a scan is ENQUEUED: scans already queued keep theirs)
         const fdm_config fq = detail::toEngineConfig(effectiveConfig());
@@ -371,6 +375,7 @@ class FastDEM {
   bool integrateSync(const CLOUD& cloud, const Eigen::Isometry3d& T_base_sensor,
                      const Eigen::Isometry3d& T_world_base) {
     drain();
+    rebind();
     map_.flushToDevice();
     Config eff = effectiveConfig();
     const float* sigma = nullptr;
@@ -402,6 +407,14 @@ class FastDEM {
     }
     if (on_rasterized_ && last_.n_cells_touched > 0) on_rasterized_(fetch(false, last_.n_cells_touched));  // :148-150
     return true;
+  }
+  // the map has another engine since this mapper last configured one (copy / move assignment, setGeometry): it has
+  // the engine's default parameters and captures no scan — configure it before the next scan
+  void rebind() {
+    if (map_.engineSerial() == bound_) return;
+    bound_ = map_.engineSerial();
+    cfg_dirty_ = true;
+    if (on_preprocessed_ || on_rasterized_) syncCapture();
   }
   void syncCapture() {
     detail::ck(fdm_engine_capture(map_.engine(), on_preprocessed_ ? 2 : 0, on_rasterized_ ? 1 : 0),
@@ -461,6 +474,7 @@ class FastDEM {
   fdm_scan_stats last_{};
   std::vector<fdm_device_scan> batch_;
   bool queued_ = false, pending_ = false, cfg_dirty_ = true;
+  uint64_t bound_ = 0;  // GridMap::engineSerial() of the engine configured last
 };
 
 }  // namespace fastdem

@@ -78,6 +78,7 @@ class ElevationMapping {
   /// ElevationMapping::update(cloud, robot_position) on a cloud already in the map frame
   /// (elevation_mapping.cpp:110-125); clouds carry no covariance channel here, so pt_z_var = 0.
   CellObservations update(const PointCloud& cloud, const Eigen::Vector2d& robot_position) {
+    if (map_.engineSerial() != bound_) apply();  // (the map has another engine since: copy / move assignment)
     map_.flushToDevice();
     fdm_scan_stats st{};
     detail::ck(fdm_engine_update(map_.engine(), cloud.size(), cloud.xData(), cloud.yData(), cloud.zData(),
@@ -96,9 +97,11 @@ class ElevationMapping {
     if (!map_.hasEngine()) throw nanogrid::EngineError("ElevationMapping: the map has no geometry yet");
     const fdm_config f = detail::toEngineConfig(cfg_);
     detail::ck(fdm_engine_set_config(map_.engine(), &f), "fdm_engine_set_config");
+    bound_ = map_.engineSerial();
   }
   ElevationMap& map_;
   Config cfg_;
+  uint64_t bound_ = 0;
 };
 
 inline std::unique_ptr<ElevationMapping> createElevationMapping(ElevationMap& map, const config::Mapping& cfg) {

@@ -2,8 +2,11 @@
 // backed by the DEVICE-RESIDENT map of libfdm_engine.so.  Layers live in HBM; the host keeps a
 // lazily synchronised mirror so `get(layer)` can still hand out a mutable matrix:
 //   device -> host : on the first get()/at() after a device-side change (one download per layer)
-//   host -> device : non-const access marks the layer host-dirty; FastDEM::integrate() /
-//                    ElevationMapping::update() upload dirty layers before launching kernels.
+//   host -> device : non-const access marks the layer host-dirty — get(), and every non-const access through a
+//                    Matrix& (operator(), data(), setConstant, assignment), a reference held across integrate()
+//                    included; every device operation (integrate, update, move, the stencils, a copy) uploads
+//                    the dirty layers first.  Cost: one layer upload per device operation for each layer written
+//                    (or merely accessed through a non-const reference) since the previous one.
 // A `Matrix&` keeps its ADDRESS for the life of the map (the reference hands out references that stay live across
 // integrate(): estimators bind raw pointers, kalman_estimation.hpp:85-95, callers hold references): the host copy of a
 // layer is refreshed IN PLACE at the first host access — get() / at() of ANY layer, by anyone — after the device
@@ -14,6 +17,7 @@
 // (elevation_map.hpp:95-99, ros1/src/fastdem_ros_node.cpp:192-199).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -49,27 +53,29 @@ class Matrix {
   Matrix(const Matrix& o) : r_(o.r_), c_(o.c_), d_((o.guard(), o.d_)) {}
   Matrix(Matrix&& o) noexcept : r_(o.r_), c_(o.c_), d_(std::move(o.d_)) { o.r_ = o.c_ = 0; }
   Matrix& operator=(const Matrix& o) {
-    if (this != &o) { o.guard(); guard(); r_ = o.r_; c_ = o.c_; d_ = o.d_; }
+    if (this != &o) { o.guard(); guard(); touch(); r_ = o.r_; c_ = o.c_; d_ = o.d_; }
     return *this;
   }
   Matrix& operator=(Matrix&& o) noexcept {
-    if (this != &o) { r_ = o.r_; c_ = o.c_; d_ = std::move(o.d_); o.r_ = o.c_ = 0; }
+    if (this != &o) { touch(); r_ = o.r_; c_ = o.c_; d_ = std::move(o.d_); o.r_ = o.c_ = 0; }
     return *this;
   }
   int rows() const { return r_; }
   int cols() const { return c_; }
   size_t size() const { return d_.size(); }
-  float* data() { guard(); return d_.data(); }
+  float* data() { guard(); touch(); return d_.data(); }
   const float* data() const { guard(); return d_.data(); }
-  float& operator()(int i, int j) { guard(); return d_[size_t(j) * r_ + i]; }
+  float& operator()(int i, int j) { guard(); touch(); return d_[size_t(j) * r_ + i]; }
   float operator()(int i, int j) const { guard(); return d_[size_t(j) * r_ + i]; }
   float& operator()(const Index& i) { return (*this)(i(0), i(1)); }
   float operator()(const Index& i) const { return (*this)(i(0), i(1)); }
-  void setConstant(float v) { guard(); std::fill(d_.begin(), d_.end(), v); }
-  // (a layer's host copy: GridMap sets the flag when the device changes the map and clears it when it has refreshed the
-  // copy in place; an access in between reads stale data — debug builds refuse)
-  void watch(const bool* stale) { stale_ = stale; }
-  float* raw() { return d_.data(); }
+  void setConstant(float v) { guard(); touch(); std::fill(d_.begin(), d_.end(), v); }
+  // (a layer's host copy: GridMap sets `stale` when the device changes the map and clears it when it has refreshed the
+  // copy in place; an access in between reads stale data — debug builds refuse.  Every non-const access sets `dirty`,
+  // which GridMap clears when it has uploaded the copy: a write through a reference obtained long before reaches the
+  // device at the next device operation.)
+  void watch(const bool* stale, bool* dirty) { stale_ = stale; dirty_ = dirty; }
+  float* raw() { return d_.data(); }  // (GridMap's own downloads and uploads: marks nothing)
   bool allNaN() const { guard(); for (float v : d_) if (!std::isnan(v)) return false; return true; }
   size_t countFinite() const { guard(); size_t n = 0; for (float v : d_) n += std::isfinite(v) ? 1 : 0; return n; }
 
@@ -81,9 +87,13 @@ class Matrix {
                              "next GridMap::get() / at(): it would read the map as it was (call get() again)");
 #endif
   }
+  void touch() {
+    if (dirty_) *dirty_ = true;
+  }
   int r_ = 0, c_ = 0;
   std::vector<float> d_;
   const bool* stale_ = nullptr;
+  bool* dirty_ = nullptr;
 };
 
 // nanogrid::colorVectorToValue: 0x00RRGGBB bit-cast to float (bridge/ros/impl.hpp:20-21)
@@ -114,9 +124,12 @@ class GridMap {
     if (this != &o) {
       release();
       eng_ = o.eng_; o.eng_ = nullptr;
+      serial_ = o.serial_; o.serial_ = 0;
       rows_ = o.rows_; cols_ = o.cols_; res_ = o.res_; length_ = o.length_;
       frame_id_ = std::move(o.frame_id_); timestamp_ = o.timestamp_;
       mirror_ = std::move(o.mirror_); initial_layers_ = std::move(o.initial_layers_);
+      any_stale_ = o.any_stale_; o.any_stale_ = false;  // (the stale host copies moved with mirror_)
+      o.mirror_.clear();
       pending_pos_ = o.pending_pos_; move_clear_basic_ = o.move_clear_basic_; device_ = o.device_;
     }
     return *this;
@@ -130,6 +143,7 @@ class GridMap {
     g.length_x = length(0); g.length_y = length(1); g.resolution = resolution;
     g.position_x = position(0); g.position_y = position(1);
     ck(fdm_engine_create_map(&g, nullptr, device_, &eng_), "fdm_engine_create_map");
+    serial_ = nextSerial();
     fdm_geometry out{};
     ck(fdm_engine_get_geometry(eng_, &out), "get_geometry");
     rows_ = out.rows; cols_ = out.cols; res_ = out.resolution;
@@ -148,6 +162,9 @@ class GridMap {
   }
   bool hasEngine() const { return eng_ != nullptr; }
   fdm_engine* engine() const { return eng_; }
+  // changes whenever the map gets another engine (setGeometry, copy or move assignment): mappers bound to the map
+  // configure the new one before their next scan — it starts with the engine's default parameters
+  uint64_t engineSerial() const { return serial_; }
   void setDevice(int d) { device_ = d; }
 
   Size getSize() const { return Size(rows_, cols_); }
@@ -301,7 +318,7 @@ class GridMap {
     std::unique_ptr<Mirror> m(new Mirror);
     m->host = Matrix(rows_, cols_);
     ck(fdm_engine_layer_download(eng_, n.c_str(), m->host.raw(), rows_, cols_), "layer_download");
-    m->host.watch(&m->stale);
+    m->host.watch(&m->stale, &m->dirty);
     return *mirror_.emplace(n, std::move(m)).first->second;
   }
   void copyFrom(const GridMap& o) {
@@ -316,6 +333,7 @@ class GridMap {
     mine.length_x = g.length_x; mine.length_y = g.length_y; mine.resolution = g.resolution;
     mine.position_x = g.position_x; mine.position_y = g.position_y;
     ck(fdm_engine_create_map(&mine, nullptr, device_, &eng_), "fdm_engine_create_map");
+    serial_ = nextSerial();
     rows_ = o.rows_; cols_ = o.cols_; res_ = o.res_; length_ = o.length_;
     ck(fdm_engine_set_start_index(eng_, g.start_row, g.start_col), "set_start_index");
     if (move_clear_basic_) ck(fdm_engine_set_option(eng_, "move_clear_basic", 1), "set_option(move_clear_basic)");
@@ -333,13 +351,20 @@ class GridMap {
   static void ck(int rc, const char* what) {
     if (rc < 0) throw EngineError(std::string(what) + ": " + fdm_last_error());
   }
+  static uint64_t nextSerial() {
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+  }
   void release() {
     if (eng_) fdm_engine_destroy(eng_);
     eng_ = nullptr;
+    serial_ = 0;
     mirror_.clear();
+    any_stale_ = false;
   }
 
   fdm_engine* eng_ = nullptr;
+  uint64_t serial_ = 0;
   int device_ = 0;
   int rows_ = 0, cols_ = 0;
   double res_ = 0.0;

@@ -1313,6 +1313,12 @@ TEST(MirrorSemantics, AHeldReferenceKeepsItsAddressAndIsRefreshedInPlace) {
   nanogrid::Matrix value = f.map.get(layer::elevation);
   ASSERT_TRUE(mapper.integrate(makeGroundCloud(1.2f), f.T_base_sensor, f.T_world_base));
   EXPECT_NO_THROW((void)value.countFinite());
+  // a write through the reference HELD since before the first scan (refreshed in place by a host access of another
+  // layer) reaches the device before the next scan, as a write through a reference is the map in the reference
+  (void)f.map.get(layer::variance);
+  elev(c) = 9.0f;
+  ASSERT_TRUE(mapper.integrate(makeGroundCloud(1.2f), f.T_base_sensor, f.T_world_base));
+  EXPECT_GT(f.map.at(layer::elevation, c), 1.25f);     // (the estimator started from 9, not from ~1.2)
 }
 
 TEST(MirrorSemantics, TheMapIsCopyableADeepCopy) {
