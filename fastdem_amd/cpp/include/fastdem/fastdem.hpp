@@ -24,6 +24,9 @@
 
 namespace fastdem {
 
+/// Which point represents a voxel in VoxelMode::ANY (FastDEM::setVoxelAnyOrder).
+enum class VoxelAnyOrder { Stable, StdSort };
+
 class FastDEM {
  public:
   using CloudCallback = std::function<void(const PointCloud&)>;
@@ -246,6 +249,15 @@ class FastDEM {
     return *this;
   }
   bool queued() const noexcept { return queued_; }
+  /// Which point represents a voxel in the raycasting stage's voxel filter (VoxelMode::ANY): StdSort picks what a g++
+  /// build of the reference picks (the order libstdc++'s std::sort leaves inside a voxel), Stable (default) the first
+  /// in point order of the same pick position.  Engine option "voxel_any_order".
+  FastDEM& setVoxelAnyOrder(VoxelAnyOrder order) {
+    voxel_any_order_ = order;
+    syncVoxelAnyOrder();
+    return *this;
+  }
+  VoxelAnyOrder voxelAnyOrder() const noexcept { return voxel_any_order_; }
   /// Wait for every queued scan; the status the last one would have returned (true when nothing was queued).
   bool drain() {
     if (!pending_) return true;
@@ -415,6 +427,11 @@ class FastDEM {
     bound_ = map_.engineSerial();
     cfg_dirty_ = true;
     if (on_preprocessed_ || on_rasterized_) syncCapture();
+    if (voxel_any_order_ != VoxelAnyOrder::Stable) syncVoxelAnyOrder();
+  }
+  void syncVoxelAnyOrder() {
+    detail::ck(fdm_engine_set_option(map_.engine(), "voxel_any_order", voxel_any_order_ == VoxelAnyOrder::StdSort),
+               "fdm_engine_set_option(voxel_any_order)");
   }
   void syncCapture() {
     detail::ck(fdm_engine_capture(map_.engine(), on_preprocessed_ ? 2 : 0, on_rasterized_ ? 1 : 0),
@@ -474,6 +491,7 @@ class FastDEM {
   fdm_scan_stats last_{};
   std::vector<fdm_device_scan> batch_;
   bool queued_ = false, pending_ = false, cfg_dirty_ = true;
+  VoxelAnyOrder voxel_any_order_ = VoxelAnyOrder::Stable;
   uint64_t bound_ = 0;  // GridMap::engineSerial() of the engine configured last
 };
 

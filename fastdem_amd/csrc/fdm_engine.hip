@@ -1092,11 +1092,13 @@ void fdm_engine_destroy(fdm_engine* e) {
   if (e->sort_tmp) (void)hipFree(e->sort_tmp);
   if (e->vs_cnt) (void)hipFree(e->vs_cnt);
   if (e->vs_rec) (void)hipFree(e->vs_rec);
+  if (e->is_buf) (void)hipFree(e->is_buf);
   {  // the second set of the raycasting stage's buffers, its streams and events (option "ray_overlap")
     fdm_engine::RayBank& b = e->ray_bank1;
     for (void* p : {static_cast<void*>(b.rc_cnt), static_cast<void*>(b.rc_min), static_cast<void*>(b.ray_bins),
                     static_cast<void*>(b.vkeys[0]), static_cast<void*>(b.vkeys[1]), static_cast<void*>(b.vidx[0]),
-                    static_cast<void*>(b.vidx[1]), static_cast<void*>(b.vsel), static_cast<void*>(b.ray_blk), b.sort_tmp})
+                    static_cast<void*>(b.vidx[1]), static_cast<void*>(b.vsel), static_cast<void*>(b.ray_blk), b.sort_tmp,
+                    b.is_buf})
       if (p) (void)hipFree(p);
     for (hipStream_t rs : e->ray_stream) if (rs) (void)hipStreamDestroy(rs);
     for (hipEvent_t ev : {e->ev_ray_pre[0], e->ev_ray_pre[1], e->ev_ray_res[0], e->ev_ray_res[1], e->ev_ray_bin})

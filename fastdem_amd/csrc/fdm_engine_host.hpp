@@ -30,6 +30,7 @@
 #include "fdm_multi.hpp"
 #include "fdm_route.hpp"
 #include "fdm_raycast.hpp"
+#include "fdm_introsort.hpp"
 #include "fdm_raywedge.hpp"
 #include "fdm_rbatch.hpp"
 #include "fdm_rsort.hpp"
@@ -165,6 +166,12 @@ struct fdm_engine {
   size_t vs_rec_cap = 0;
   int voxel_small_max = 1 << 16;     // option "voxel_small_max": largest scan that takes it
   VoxelSmall vs{};                   // the last small-scan filter's parameters (k_vs_mark runs from enqueue_ray_stage)
+  // option "voxel_any_order": 0 = ties inside a voxel in point order (stable sort, default); 1 = the order libstdc++'s
+  // std::sort leaves (fdm_introsort.hpp), so VoxelMode::ANY picks what a g++ build of the reference picks.  While it is
+  // on, the sort-free small-scan filter is not used and batch calls with raycasting go scan by scan (multi_run)
+  int voxel_any_order = 0;
+  void* is_buf = nullptr;            // fdm_introsort.hpp's level buffers, rank tables, segment lists (is_layout)
+  size_t is_cap = 0;                 // pairs is_buf is laid out for
   hipEvent_t ev_ray[2] = {nullptr, nullptr};
   hipEvent_t ev_timer[2] = {nullptr, nullptr};  // fdm_engine_timer_start / _stop
   bool ray_timed = false;
@@ -195,6 +202,8 @@ struct fdm_engine {
     uint32_t *vsel = nullptr, *ray_blk = nullptr;
     void* sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0, vcap = 0;
+    void* is_buf = nullptr;
+    size_t is_cap = 0;
   } ray_bank1;
   hipStream_t ray_stream[2] = {nullptr, nullptr};
   hipEvent_t ev_ray_pre[2] = {nullptr, nullptr}, ev_ray_res[2] = {nullptr, nullptr}, ev_ray_bin = nullptr;

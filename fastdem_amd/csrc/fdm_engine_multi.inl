@@ -21,6 +21,7 @@ uint32_t multi_run(fdm_engine* e, uint32_t count, const fdm_device_scan* scans) 
   const bool ray = e->cfg.raycast_enabled != 0;
   if (ray) {
     if (!e->batch_ray || !e->voxel_small || !voxel_size_ok(static_cast<float>(e->G.res))) return 0u;
+    if (e->voxel_any_order) return 0u;  // (the batch's filter is the sort-free one: ties in point order)
     if (e->G.o_rows != e->G.rows || e->G.o_cols != e->G.cols || e->G.s_rows != e->G.rows || e->G.s_cols != e->G.cols) return 0u;
   }
   poll_dense_paid(e);

@@ -100,6 +100,82 @@ void launch_voxel_keys(fdm_engine* e, unsigned n, float inv, int flag_slot, cons
                        e->d_state, dx, dy, dz, keys, e->vsel, tiles, hist);
 }
 
+// ---- option "voxel_any_order" = 1: the order libstdc++'s std::sort leaves (fdm_introsort.hpp) ----
+// Global level passes for n pairs: until no segment is larger than kIsLds, with room for an unbalanced tree (a median of
+// three keeps random, sorted and tie-heavy scans within log2(n / kIsLds) + 2); what is still larger after them takes
+// k_is_rest.  The launch count depends on n only: no host round trip.
+int is_levels(size_t n) {
+  if (n <= kIsLds) return 0;
+  int lg = 0;
+  while ((size_t(kIsLds) << lg) < n) ++lg;
+  return std::min(is_depth_limit(unsigned(n)), 2 * lg + 4);
+}
+size_t is_cap_big(size_t cap) { return cap / (kIsLds + 1u) + 2u; }
+size_t is_cap_fin(size_t cap) { return std::min(cap / 2u + 2u, 2u * size_t(is_levels(cap)) * is_cap_big(cap) + 2u); }
+size_t is_cap_tiles(size_t cap) { return cap / kIsTile + is_cap_big(cap) + 2u; }
+// carve is_buf (laid out for `cap` pairs) into the kernels' arrays; returns the bytes it takes (base 0: only count)
+template <typename KEY>
+size_t is_layout(uintptr_t base, size_t cap, IsBufs<KEY>* B) {
+  size_t off = 0;
+  auto take = [&](auto*& p, size_t count) {
+    using T = std::remove_reference_t<decltype(*p)>;
+    p = reinterpret_cast<T*>(base + off);
+    off += (count * sizeof(T) + 255u) & ~size_t(255);
+  };
+  const size_t cb = is_cap_big(cap), ct = is_cap_tiles(cap);
+  for (int k = 0; k < 2; ++k) { take(B->key[k], cap); take(B->idx[k], cap); }
+  take(B->posg, cap); take(B->posr, cap);
+  take(B->big[0], cb); take(B->big[1], cb); take(B->rest, cb); take(B->fin, is_cap_fin(cap));
+  take(B->piv, cb); take(B->tile0, cb); take(B->tot, 2u * cb);
+  take(B->tile_seg, ct); take(B->tile_cnt, ct); take(B->tile_ag, ct); take(B->tile_ar, ct); take(B->tile_og, ct);
+  take(B->tile_or, ct);
+  take(B->ctl, 1u);
+  B->cap_big = unsigned(cb);
+  B->cap_fin = unsigned(is_cap_fin(cap));
+  B->cap_tiles = unsigned(ct);
+  return off;
+}
+int ensure_introsort_buffers(fdm_engine* e, size_t n) {
+  if (n <= e->is_cap) return FDM_OK;
+  if (int rc_sync = sync_all(e)) return rc_sync;
+  if (e->is_buf) HIPCK(hipFree(e->is_buf));
+  e->is_buf = nullptr;
+  const size_t cap = n + n / 4u + 1024u;
+  IsBufs<unsigned long long> B{};  // (the 64-bit layout is the larger one)
+  HIPCK(hipMalloc(&e->is_buf, is_layout(uintptr_t(0), cap, &B)));
+  e->is_cap = cap;
+  return FDM_OK;
+}
+// (key, position) of the n pairs in vkeys[0] (k_voxel_keys' output) -> vkeys[1] / vidx[1] in std::sort's order, the
+// dropped points behind the valid ones
+template <typename KEY>
+int enqueue_introsort(fdm_engine* e, unsigned n) {
+  if (int rc = ensure_introsort_buffers(e, n)) return rc;
+  IsBufs<KEY> B{};
+  is_layout(reinterpret_cast<uintptr_t>(e->is_buf), e->is_cap, &B);
+  B.okey = reinterpret_cast<KEY*>(e->vkeys[1]);
+  B.oidx = e->vidx[1];
+  const KEY* keys = reinterpret_cast<const KEY*>(e->vkeys[0]);
+  const unsigned ct = std::max(1u, (n + kIsTile - 1u) / kIsTile);
+  hipLaunchKernelGGL(k_is_ccount<KEY>, dim3(ct), dim3(256), 0, e->stream, n, keys, B);
+  hipLaunchKernelGGL(k_is_cscan<KEY>, dim3(1), dim3(256), 0, e->stream, ct, B);
+  hipLaunchKernelGGL(k_is_cscatter<KEY>, dim3(ct), dim3(256), 0, e->stream, n, keys, B);
+  const int levels = is_levels(n);
+  const unsigned tiles = unsigned(std::min<size_t>(is_cap_tiles(n), B.cap_tiles));  // bound of a level's tiles
+  for (int lv = 0; lv < levels; ++lv) {
+    hipLaunchKernelGGL(k_is_plan<KEY>, dim3(1), dim3(256), 0, e->stream, lv, B);
+    hipLaunchKernelGGL(k_is_count<KEY>, dim3(tiles), dim3(256), 0, e->stream, lv, B);
+    hipLaunchKernelGGL(k_is_scan<KEY>, dim3(1), dim3(256), 0, e->stream, lv, B);
+    hipLaunchKernelGGL(k_is_pos<KEY>, dim3(tiles), dim3(256), 0, e->stream, lv, B);
+    hipLaunchKernelGGL(k_is_scatter<KEY>, dim3(tiles), dim3(256), 0, e->stream, lv, int(lv == levels - 1), B);
+  }
+  const unsigned fin_blocks = std::max(1u, std::min(2048u, n / 64u));
+  hipLaunchKernelGGL(k_is_finish<KEY>, dim3(fin_blocks), dim3(64), 0, e->stream, B);
+  if (levels > 0) hipLaunchKernelGGL(k_is_rest<KEY>, dim3(64), dim3(64), 0, e->stream, B);
+  HIPCK(hipGetLastError());
+  return FDM_OK;
+}
+
 // keys -> stable sort: vkeys[1] / vidx[1] hold the voxel-ordered scan afterwards.
 // `box` (nullable): centre (3) + half extent [m] of a box that holds every finite point of the cloud, then the
 // map-frame z interval [lo, hi] they lie in (NaN, NaN if unknown);
@@ -171,6 +247,14 @@ int enqueue_voxel_sort(fdm_engine* e, unsigned n, float voxel_size, int flag_slo
   const int key_bits = 2 * C.bits + C.zbits;
   const bool compact = C.bits > 0 && key_bits <= 31;  // true: the sorted buffer holds uint32 keys
   *key_mode = compact ? 1 : 0;
+  if (e->voxel_any_order) {  // the order std::sort leaves (fdm_introsort.hpp)
+    if (compact) {
+      launch_voxel_keys<uint32_t>(e, n, inv, flag_slot, C, dx, dy, dz, reinterpret_cast<uint32_t*>(e->vkeys[0]));
+      return enqueue_introsort<uint32_t>(e, n);
+    }
+    launch_voxel_keys<unsigned long long>(e, n, inv, flag_slot, C, dx, dy, dz, e->vkeys[0]);
+    return enqueue_introsort<unsigned long long>(e, n);
+  }
   if (compact && e->voxel_small && n <= unsigned(e->voxel_small_max)) {
     // small scans: no sort at all (k_vs_*: fdm_raycast.hpp).  vkeys[0] = keys by point | places by point, vs_rec =
     // {key, point, bucket start, bucket size} by position; k_vs_mark runs from enqueue_ray_stage (key_mode 2)
@@ -268,6 +352,7 @@ void ray_bank_swap(fdm_engine* e) {
   std::swap(e->vsel, b.vsel); std::swap(e->ray_blk, b.ray_blk);
   std::swap(e->sort_tmp, b.sort_tmp); std::swap(e->sort_tmp_bytes, b.sort_tmp_bytes);
   std::swap(e->vcap, b.vcap);
+  std::swap(e->is_buf, b.is_buf); std::swap(e->is_cap, b.is_cap);
 }
 struct RayBankScope {  // bank `ctx` is the live one inside the scope
   fdm_engine* e;
@@ -442,7 +527,8 @@ int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const Sca
   u.ray_pre = 0;
   const bool want = e->ray_overlap > 0 || (e->ray_overlap < 0 && (e->sync_call || u.RQ.n >= 1000000u));
   if (!want || !u.ray || u.RQ.n < unsigned(e->ray_large_min) || e->profile || !e->ray_wedge) return FDM_OK;
-  if (e->voxel_small && u.RQ.n <= unsigned(e->voxel_small_max)) return FDM_OK;  // (the sort-free filter keeps state of its own)
+  if (e->voxel_small && !e->voxel_any_order && u.RQ.n <= unsigned(e->voxel_small_max))
+    return FDM_OK;  // (the sort-free filter keeps state of its own)
   if (!find_layer(e, "elevation")) return FDM_OK;
   int rc;
   if ((rc = ensure_ray_streams(e))) return rc;
@@ -450,8 +536,9 @@ int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const Sca
   bool fresh = false;
   {  // allocations (they may drain the streams and, with them, flush this very scan: then the stage has run) before anything is enqueued
     RayBankScope bank(e, ctx);
-    fresh = e->rc_cnt == nullptr || u.RQ.n > e->vcap;
+    fresh = e->rc_cnt == nullptr || u.RQ.n > e->vcap || (e->voxel_any_order && u.RQ.n > e->is_cap);
     if ((rc = ensure_ray_cells(e)) || (rc = ensure_voxel_buffers(e, u.RQ.n))) return rc;
+    if (e->voxel_any_order && (rc = ensure_introsort_buffers(e, u.RQ.n))) return rc;
   }
   if (!u.ray || !e->chain) return FDM_OK;
   hipStream_t rs = e->ray_stream[ctx];

@@ -356,8 +356,9 @@ int fdm_engine_apply_raycasting_device(fdm_engine* e, uint64_t n, const float* d
                                        const fdm_raycast_config* rc);
 /* nanopcl::filters::voxelGrid(cloud, voxel_size, VoxelMode::ANY) (voxel_grid_impl.hpp:30-60,171-189)
  * on the device: writes the ORIGINAL indices of the kept points, in the filter's output order
- * (ascending voxel key), to out_idx (capacity n) and their count to n_out.  Ties inside a voxel are
- * in original point order (the reference: whatever std::sort leaves — see DESIGN.md).
+ * (ascending voxel key), to out_idx (capacity n) and their count to n_out.  Which point of a voxel
+ * represents it follows the option "voxel_any_order": 0 (default) ties in original point order, 1 the order
+ * libstdc++'s std::sort leaves — what a g++ build of the reference picks.
  * FDM_ERR_INVALID for a voxel_size outside [0.001, 100]. */
 int fdm_engine_voxel_any(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
                          float voxel_size, uint32_t* out_idx, uint64_t* n_out);
@@ -507,6 +508,12 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2);
  *                         own as soon as the scan's bin half has run, its resolve stays behind the scan's update (0, default:
  *                         never; 1 whenever possible; -1 for synchronous calls and scans of >= 1 M points).  Worth 10-14 % in a
  *                         process with few active streams, a loss in one with many
+ *   "voxel_any_order" 0/1: which point represents a voxel in raycasting's voxel filter (VoxelMode::ANY) and in
+ *                         fdm_engine_voxel_any: 0 = ties in point order (stable sort, default), 1 = the order libstdc++'s
+ *                         std::sort leaves, so maps match a g++ build of the reference bit for bit (fdm_introsort.hpp).
+ *                         While it is 1 the sort-free small-scan filter is not used, and batch calls with raycasting on
+ *                         take the scan-by-scan path (batch launches without raycasting are unaffected).  A held-back
+ *                         stage leaves before the value changes
  *   "ray_wedge_parts" n : workgroups per sector of that walk (0 = by the scan's size, the default; 1 .. 16: measurement)
  *   "ray_hold" 0/1      : a scan's raycasting stage is held back together with its map update and runs right behind it —
  *                         in the next scan's launch sequence (the update then shares a launch with that scan's bin half) or
