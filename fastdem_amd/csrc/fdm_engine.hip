@@ -5,7 +5,7 @@
 // k_update on the engine's stream.  No per-point or per-cell work ever runs on the CPU and
 // there is NO CPU fallback: without a HIP device fdm_engine_create fails with
 // FDM_ERR_NO_DEVICE.
-// (One of the library's three translation units: fdm_engine_host.hpp.)
+// (One of the library's five translation units: fdm_engine_host.hpp.)
 #include "fdm_engine_host.hpp"
 
 namespace fdmh {
@@ -22,7 +22,7 @@ namespace fdmh {
 // the next scan of the chain, and before anything that syncs or reallocates.
 // The raycasting stage of the scan whose update was just launched (fdm_engine_ray.inl).
 int join_streams(fdm_engine* e) {
-  if (e->chain) {
+  if (e && e->chain) {
     e->chain = false;
     if (int rc = launch_update_alone(e, e->pend)) return rc;
     if (int rc = run_held_ray_stage(e, e->pend)) return rc;
@@ -272,7 +272,7 @@ int deactivate_records(fdm_engine* e) {
 }
 // Entering it: the estimator's layers (which must all exist) are gathered into the records.
 int activate_records(fdm_engine* e, int kind) {
-  if (!e->use_records) return deactivate_records(e);
+  if (!e->opt.records) return deactivate_records(e);
   if (e->rec_kind == kind) return FDM_OK;
   if (int rc = deactivate_records(e)) return rc;
   const int nf = kind == 1 ? int(PF_COUNT) : int(KF_COUNT);
@@ -339,7 +339,6 @@ int ensure_stage(fdm_engine* e, size_t n);
 int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, const float* dy,
                  const float* dz, const float* dint, const uint32_t* drgb, const float* dvar,
                  const ScanInputs* gather) {
-  if (n >= 0xFFFFFFFEull) return fail(FDM_ERR_INVALID, "point count exceeds 2^32-2");
   if (n >= 0x7FFFFFFFull) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
   int rc;
   poll_dense_paid(e);
@@ -380,7 +379,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
     if (drgb) { e->S.wt_rgb = const_cast<uint32_t*>(gather->rgb); e->S.wt_src_rgb = drgb; }
   }
   // (a scan with raycasting and nothing else optional is held back like a plain one: its stage runs behind its update)
-  const bool ray_held = ray_on && e->ray_hold && e->overlap && e->key2[1] && !e->cap_pre && !e->cap_ras;
+  const bool ray_held = ray_on && e->opt.ray_hold && e->opt.overlap && e->key2[1] && !e->cap_pre && !e->cap_ras;
   if (ray_held && n) {
     if (n > e->rcap_cap) {
       if (int rc_sync = sync_all(e)) return rc_sync;
@@ -426,8 +425,8 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   // 169 tiles 11.8 vs 7.7 / 15.0 vs 19.3, 256 tiles 12.6 vs 15.5 / 15.3 vs 24.4, 625 tiles 13.7 vs 14.4 / 16.6 vs 25.5
   const size_t kt = e->ncell / 1024u;  // (the thresholds below were measured in units of 1 024 cells, round 2)
   const bool enough_tiles = e->tiled_forced || kt >= 240 || (kt >= 160 && n >= 100000);
-  const bool tiled = e->tiled && e->rec_kind >= 0 && n >= e->tiled_min && aligned && n < 0x7FFF0000ull &&
-                     e->bin_variant != 1 && enough_tiles;
+  const bool tiled = e->opt.tiled && e->rec_kind >= 0 && n >= uint64_t(e->opt.tiled_min) && aligned && n < 0x7FFF0000ull &&
+                     e->opt.bin_variant != 1 && enough_tiles;
   if (e->last_kind >= 0 && e->last_kind != int(tiled)) {  // the pipelines keep separate books on which tiles hold
     e->obst_dense_pending = true;                         // obstacle cells
     e->obst_owe_armed = false;
@@ -443,7 +442,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
     e->S.aux = e->aux2[parity];
     e->S.zs = e->zs2[parity];
   }
-  const bool plain = e->overlap && e->key2[1] && (!ray_on || ray_held) && !e->cap_pre &&
+  const bool plain = e->opt.overlap && e->key2[1] && (!ray_on || ray_held) && !e->cap_pre &&
                      !e->cap_ras && !e->obst_dense_pending;
   // A held-back update of the scratch pipeline gathers the winning points AFTER this call has returned and
   // the next scan has been enqueued.  Device arrays handed to the enqueue-only entry points are therefore
@@ -451,7 +450,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   // gathers from that copy: the caller's arrays are free as soon as the bin kernel has run, which is the
   // ordinary stream contract.  (The tiled pipeline never looks at a scan twice.)
   ScanInputs auto_gather{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!tiled && plain && !gather && n && !e->borrow_inputs) {
+  if (!tiled && plain && !gather && n && !e->opt.borrow_inputs) {
     if ((rc = ensure_stage(e, n))) return rc;
     e->stage_rr = (e->stage_rr + 1) % kStageSlots;
     float* base = e->d_stage + size_t(e->stage_rr) * 6 * e->stage_cap;
@@ -469,7 +468,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   // k_bin4 (1024-point blocks, 16 B loads) needs enough blocks to hide a block's latency chain: since k_bin folds
   // its runs through the same per-block LDS table, it wins up to ~400 K points (4 x the blocks; RGB-D 272 K: 13.0
   // vs 15.9 us, 128-beam 262 K: 33.8 vs 39.8; 524 K: 51.1 vs 39.6 the other way)
-  const bool want4 = e->bin_variant == 4 || (e->bin_variant == 0 && n >= 393216);
+  const bool want4 = e->opt.bin_variant == 4 || (e->opt.bin_variant == 0 && n >= 393216);
   const bool use_bin4 = !tiled && want4 && aligned;
   // 4-points-per-thread kernels: 256-thread blocks (1024 points).  (2048-point blocks merged ~20 % more cells on
   // chip when every merged cell still cost memory-side atomics; with the record pools four resident blocks per
@@ -483,16 +482,13 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
     e->bin_part_cap = bin_blocks + bin_blocks / 4 + 64;
     HIPCK(hipMalloc(reinterpret_cast<void**>(&e->S.bin_part), e->bin_part_cap * sizeof(unsigned long long)));
   }
-  if (tiled && (rc = ensure_tile_pool(e, size_t(bin_blocks) * per_block, bin_blocks,
-                                      P.has_intensity != 0,
-                                      P.has_color != 0)))
-    return rc;
+  if (tiled && (rc = ensure_tile_pool(e, size_t(bin_blocks) * per_block, bin_blocks))) return rc;
   e->last_bin_blocks = bin_blocks;
   e->last_bin_part = e->S.bin_part;
-  P.dbg_no_atomics = e->dbg_no_atomics;
-  P.bin_table = e->bin_table;
-  P.dbg_upd = e->dbg_upd;
-  P.move_basic = e->move_clear_basic;
+  P.dbg_no_atomics = e->opt.dbg_no_atomics;
+  P.bin_table = e->opt.bin_table;
+  P.dbg_upd = e->opt.dbg_upd;
+  P.move_basic = e->opt.move_clear_basic;
   P.drop_nonfinite = e->next_drop_nonfinite;
   e->next_drop_nonfinite = 0;
   int32_t* ids = e->want_ids ? e->d_cell_ids : nullptr;
@@ -500,10 +496,10 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   // a scan that asks for nothing optional takes the LEAN bin body (fdm_kernels.hpp)
   // (2: lean, but x / y / z written through for the held-back update's gather)
   const int lean = (ids || e->S.cap_x || P.drop_nonfinite || P.dbg_no_atomics) ? 0 : (e->S.wt_x ? 2 : 1);
-  const fdm_engine::BinVariant bv{use_bin4, P.has_intensity != 0, P.has_color != 0, e->wave_merge, bin_threads, lean};
+  const fdm_engine::BinVariant bv{use_bin4, P.has_intensity != 0, P.has_color != 0, e->opt.wave_merge != 0, bin_threads, lean};
   // a held-back update leaves now: fused with this bin if the two belong to the same pipeline and
   // this scan is a plain one, alone otherwise
-  const bool fusable = tiled || ((!use_bin4 || (e->rec_kind >= 0 && e->S.dense)) && e->wave_merge);
+  const bool fusable = tiled || ((!use_bin4 || (e->rec_kind >= 0 && e->S.dense)) && e->opt.wave_merge);
   // (the fused tiled launch compiles the channels in once, for both halves)
   const bool same_channels = !tiled || (e->pend.P.has_intensity == P.has_intensity && e->pend.P.has_color == P.has_color);
   const bool fuse_now = e->chain && plain && fusable && !e->pend.multi && e->pend.tiled == tiled && same_channels;
@@ -520,25 +516,19 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   } else if (tiled) {
     if ((rc = launch_tbin(e, P, in_b, e->pool[parity], ids, bin_blocks, bv))) return rc;
   } else if (use_bin4) {
-    const bool hi = P.has_intensity != 0, hc = P.has_color != 0;
-    auto launch4 = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(bin_blocks), dim3(bin_threads), 0, e->stream, P, e->G, e->d_state, dx,
-                         dy, dz, dint, e->S, ids);
-    };
-    if (hi && hc) launch4(k_bin4<true, true, 256>);
-    else if (hi) launch4(k_bin4<true, false, 256>);
-    else if (hc) launch4(k_bin4<false, true, 256>);
-    else launch4(k_bin4<false, false, 256>);
+    with_constants([&](auto hi, auto hc) {
+      hipLaunchKernelGGL((k_bin4<hi(), hc(), 256>), dim3(bin_blocks), dim3(bin_threads), 0, e->stream, P, e->G,
+                         e->d_state, dx, dy, dz, dint, e->S, ids);
+    }, bv.has_int, bv.has_col);
   } else {
     auto launch_bin = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(bin_blocks), dim3(256), 0, e->stream, P, e->G, e->d_state, dx, dy,
                          dz, dint, e->S, ids);
     };
-    if (!e->wave_merge) launch_bin(k_bin<false>);
-    else if (P.has_intensity && P.has_color) launch_bin(k_bin<true, 3>);
-    else if (P.has_color) launch_bin(k_bin<true, 2>);
-    else if (P.has_intensity) launch_bin(k_bin<true, 1>);
-    else launch_bin(k_bin<true, 0>);
+    with_constants([&](auto merge, auto ch) {  // ch: intensity | colour << 1, compiled in with the wavefront merge only
+      if constexpr (merge()) launch_bin(k_bin<true, ch()>);
+      else launch_bin(k_bin<false>);
+    }, bv.wave_merge, UpTo<4>{int(bv.has_int) + 2 * int(bv.has_col)});
   }
   HIPCK(hipGetLastError());
   if (e->profile) HIPCK(hipEventRecord(e->ev[1], e->stream));
@@ -547,7 +537,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   //  against that previous stage, which uses the buffers of its bank, it is ordered by ev_ray_res[bank], which
   //  run_held_ray_stage records behind it on either path and start_ray_stage_early waits for as well)
   e->ray_bin_marked = false;
-  if (ray_held && e->ray_overlap && e->ray_stream[0]) {
+  if (ray_held && e->opt.ray_overlap && e->ray_stream[0]) {
     HIPCK(hipEventRecord(e->ev_ray_bin, e->stream));
     e->ray_bin_marked = true;
   }
@@ -699,7 +689,7 @@ int stage_inputs(fdm_engine* e, uint64_t n, const float* x, const float* y, cons
   const size_t cap = e->stage_cap;
   float* base = e->d_stage + size_t(e->stage_rr) * 6 * cap;
   if (gather) *gather = ScanInputs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (gather && e->zero_copy && n <= uint64_t(e->zero_copy)) {
+  if (gather && e->opt.zero_copy && n <= uint64_t(e->opt.zero_copy)) {
     const float* mx = static_cast<const float*>(pinned_alias(x));
     const float* my = mx ? static_cast<const float*>(pinned_alias(y)) : nullptr;
     const float* mz = my ? static_cast<const float*>(pinned_alias(z)) : nullptr;
@@ -761,13 +751,13 @@ int read_stats(fdm_engine* e, fdm_scan_stats* out, int* status) {
     // what a synchronous integrate() of a VLP-16 scan takes end to end).
     bool seen = false;
     // (a scan of more than ~100 K points keeps the device busy for longer than the poll window: sleep at once)
-    if (e->sync_spin_us > 0 && e->last_n <= 131072u && e->last_kind != 1) {
+    if (e->opt.sync_spin_us > 0 && e->last_n <= 131072u && e->last_kind != 1) {
       const auto t0 = std::chrono::steady_clock::now();
       const volatile unsigned long long* const w = &e->h_stats->seq;
       for (;;) {
         if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == e->stats_seq) { seen = true; break; }
         if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >
-            e->sync_spin_us)
+            e->opt.sync_spin_us)
           break;
       }
     }
@@ -1109,7 +1099,7 @@ void fdm_engine_destroy(fdm_engine* e) {
 }
 
 int fdm_engine_set_config(fdm_engine* e, const fdm_config* cfg) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !cfg) return fail(FDM_ERR_INVALID, "null argument");
   if (cfg->mode != 1 && (e->G.s_rows != e->G.rows || e->G.s_cols != e->G.cols))
     return fail(FDM_ERR_INVALID, "tiled engines require GLOBAL mode");
@@ -1119,7 +1109,7 @@ int fdm_engine_set_config(fdm_engine* e, const fdm_config* cfg) {
 }
 
 int fdm_engine_set_stream(fdm_engine* e, void* hip_stream) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (int rc_sync = sync_all(e)) return rc_sync;
   if (hip_stream) {
@@ -1190,7 +1180,7 @@ int fdm_engine_integrate_host_batch(fdm_engine* e, uint32_t count, const fdm_dev
     if (!s.x || !s.y || !s.z) return fail(FDM_ERR_INVALID, "null xyz");
     if (s.n >= 0x7FFFFFFFull) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
     // (option zero_copy is a point-count BOUND, as in stage_inputs: larger clouds are staged also from pinned memory)
-    const float* mx = (e->zero_copy && s.n <= uint64_t(e->zero_copy)) ? static_cast<const float*>(pinned_alias(s.x)) : nullptr;
+    const float* mx = (e->opt.zero_copy && s.n <= uint64_t(e->opt.zero_copy)) ? static_cast<const float*>(pinned_alias(s.x)) : nullptr;
     const float* my = mx ? static_cast<const float*>(pinned_alias(s.y)) : nullptr;
     const float* mz = my ? static_cast<const float*>(pinned_alias(s.z)) : nullptr;
     const float* ma = (mz && s.intensity) ? static_cast<const float*>(pinned_alias(s.intensity)) : nullptr;
@@ -1251,7 +1241,7 @@ int fdm_engine_integrate_device_batch_timed(fdm_engine* e, uint32_t count, const
 int fdm_engine_integrate(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
                          const float* intensity, const uint32_t* rgb, const float* sigma_z2,
                          const double Tbs[16], const double Twb[16], fdm_scan_stats* out) {
-  if (e) { if (int rc_join = join_streams(e)) return rc_join; }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !Tbs || !Twb) return fail(FDM_ERR_INVALID, "null argument");
   if (n == 0) {
     if (out) {
@@ -1284,7 +1274,7 @@ int fdm_engine_integrate(fdm_engine* e, uint64_t n, const float* x, const float*
 int fdm_engine_integrate_points4(fdm_engine* e, uint64_t n, const float* xyz1, const float* intensity,
                                  const uint32_t* rgb, const float* sigma_z2, const double Tbs[16],
                                  const double Twb[16], fdm_scan_stats* out) {
-  if (e) { if (int rc_join = join_streams(e)) return rc_join; }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !Tbs || !Twb) return fail(FDM_ERR_INVALID, "null argument");
   if (n == 0) {
     if (out) std::memset(out, 0, sizeof(*out));
@@ -1329,12 +1319,12 @@ int fdm_engine_integrate_points4(fdm_engine* e, uint64_t n, const float* xyz1, c
   // (the channels already sit in the engine's own staging slot, which stays valid until read_stats below has flushed the
   // held-back update: the update gathers from the slot itself — without this a plain non-tiled scan took a SECOND slot
   // and had the bin kernel write x / y / z through to it, 12 B per point for nothing: ADVICE r05)
-  const bool borrow = e->borrow_inputs;
-  e->borrow_inputs = true;
+  const bool borrow = e->opt.borrow_inputs;
+  e->opt.borrow_inputs = true;
   e->sync_call = true;
   rc = enqueue_scan(e, P, n, base, base + cap, base + cap * 2, da, dc, dv);
   e->sync_call = false;
-  e->borrow_inputs = borrow;
+  e->opt.borrow_inputs = borrow;
   if (rc) return rc;
   int status = FDM_OK;
   if ((rc = read_stats(e, out, &status))) return rc;
@@ -1495,7 +1485,7 @@ int fdm_engine_update_device(fdm_engine* e, uint64_t n, const float* dx, const f
 int fdm_engine_update(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
                       const float* z_var, const float* intensity, const uint32_t* rgb, double rx,
                       double ry, fdm_scan_stats* out) {
-  if (e) { if (int rc_join = join_streams(e)) return rc_join; }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null xyz");
   HIPCK(hipSetDevice(e->device));
@@ -1710,14 +1700,14 @@ int fdm_engine_wait_event(fdm_engine* e, void* hip_event) {
 }
 
 int fdm_engine_sync(fdm_engine* e) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (int rc_sync = sync_all(e)) return rc_sync;
   return report_fault(e);
 }
 
 int fdm_engine_last_stats(fdm_engine* e, fdm_scan_stats* out) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (e->have_scan && e->last_was_integrate && e->last_n == 0) {
     if (int rc_sync = sync_all(e)) return rc_sync;

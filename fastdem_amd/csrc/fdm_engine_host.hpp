@@ -1,9 +1,11 @@
 // fdm_engine_host.hpp — what the translation units of libfdm_engine.so share: the engine object behind the C ABI and the
-// host helpers one unit defines for the others.  The library is THREE objects (round 6; one 2 000-line unit + 8 .inl +
-// 13 kernel headers used to be one hipcc invocation, every A/B a full rebuild): fdm_engine.hip (the scan path: bin /
-// update / batch kernels, layers, options), fdm_engine_ray.hip (the raycasting stage of one scan: voxel filter, radix
-// sort, ray queue, walks, resolve), fdm_engine_post.hip (stencils, egress, ingest).  Non-template kernels in the shared
-// headers are `inline` (weak symbols: one definition per library), a unit emits only the kernels it launches.
+// host helpers one unit defines for the others.  The library is FIVE objects (one 2 000-line unit + 8 .inl + 13 kernel
+// headers used to be one hipcc invocation, every A/B a full rebuild): fdm_engine.hip (the small-scan path: bin / update
+// kernels, layers, options, the C entry points), fdm_engine_tiled.hip (the large-scan pipeline: record pools, k_tbin /
+// k_tupdate), fdm_engine_multi.hip (the batch pipeline: k_mbatch, raycasting inside batches), fdm_engine_ray.hip (the
+// raycasting stage of one scan: voxel filter, sorts, ray queue, walks, resolve), fdm_engine_post.hip (stencils, egress,
+// ingest).  Non-template kernels in the shared headers are `inline` (weak symbols: one definition per library), a unit
+// emits only the kernels it launches.
 #pragma once
 #include "../../include/fdm_engine.h"
 #include "../../include/fdm_engine_debug.h"
@@ -76,106 +78,61 @@ const char* const kP2Q[5] = {"_p2_q0", "_p2_q1", "_p2_q2", "_p2_q3", "_p2_q4"};
 const char* const kP2N[5] = {"_p2_n0", "_p2_n1", "_p2_n2", "_p2_n3", "_p2_n4"};
 }  // namespace
 
-struct fdm_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = true;
-  fdm_config cfg{};
-  GeomConst G{};
-  size_t ncell = 0;
-  std::vector<Layer> layers;
-  float** d_layer_ptrs = nullptr;  // device array of every layer pointer (strip clears)
-  int n_layer_ptrs = 0;
-  bool layer_ptrs_dirty = true;
-  Scratch S{};
-  DevState* d_state = nullptr;
-  DevState* h_state = nullptr;  // pinned mirror for read-backs
-  StatsOut* h_stats = nullptr;  // pinned + device-mapped: k_collect_stats writes here
-  StatsOut* h_stats_dev = nullptr;  // the device's alias of h_stats
-  unsigned long long stats_seq = 0; // sequence number of the last statistics launch (StatsOut::seq)
-  int sync_spin_us = 150;           // read_stats polls the pinned block this long before a stream wait (option)
-  StatsAcc* d_stats_acc = nullptr;
-  uint64_t scan_no = 0;
-  bool have_scan = false;
-  uint32_t last_n = 0;        // points of the last scan as enqueued (array length of the captures / cell ids)
-  uint32_t last_n_input = 0;  // ... as the reference counts them (cloud.size(): finite points of a PointCloud2)
-  int next_drop_nonfinite = 0;  // set by fdm_engine_integrate_cloud2 for the scan it enqueues
-  unsigned ingest_blocks = 0; // > 0: the last scan came through k_ingest_soa; its finite count is still on the device
-  int last_was_integrate = 0;
-  // staging for the host-pointer entry points
-  float* d_stage = nullptr;
-  float4* d_aos = nullptr;  // fdm_engine_integrate_points4 on pageable memory: the cloud's {x, y, z, 1} records
-  size_t aos_cap = 0;
-  size_t stage_cap = 0;  // in points
-  int stage_rr = 0;      // rotating staging block
-  int32_t* d_cell_ids = nullptr;
-  size_t ids_cap = 0;
-  bool want_ids = false;
-  bool profile = false;
-  bool wave_merge = true;
+// The values fdm_engine_set_option writes: one plain int each, one row of kOptions (fdm_engine_opts.inl) each, in the
+// table's order.  The comment on a field is the option's documentation: what it selects and what was measured.  State
+// DERIVED from an option (tiled_forced, Scratch::dense, the timeline buffer ...) stays in fdm_engine.
+struct EngineOptions {
+  // ---- the scan path ----
+  int wave_merge = 1;               // option "wave_merge": k_bin merges same-cell runs inside the wavefront before the atomics
   int bin_table = 1;                 // k_bin: per-block LDS cell table (option "bin_table")
+  int bin_variant = 0;  // 0 = by scan size, 4 = k_bin4 (LDS-staged), 1 = k_bin (one point/thread)
+  int overlap = 1;                  // option "overlap": the update of a plain scan is held back and leaves with the next scan's bin half (enqueue_scan)
+  int borrow_inputs = 0;             // option "borrow_inputs": a held-back update gathers from the CALLER's device arrays
+                                    // (1: device arrays of enqueue-only scans stay untouched by the caller until the NEXT-BUT-ONE
+                                    // scan is enqueued, or a flush: no staging copy)
   // fdm_engine_integrate_async: scans of up to this many points whose arrays are PINNED host memory
   // are read in place by the bin kernel (0 = always stage with copy commands; option "zero_copy")
   int zero_copy = 1 << 30;
-  int dbg_no_atomics = 0;
-  int dbg_upd = 0;
-  int bin_variant = 0;  // 0 = by scan size, 4 = k_bin4 (LDS-staged), 1 = k_bin (one point/thread)
-  size_t bin_part_cap = 0;   // blocks
-  unsigned last_bin_blocks = 0;
-  std::vector<unsigned long long> h_bin_part;
-  unsigned n_tiles = 0;
-  std::vector<uint32_t> h_upd_part;
-  bool obst_dense_pending = false;  // host wrote the obstacle layer / the pipeline changed: the next scan that observes a
-                                    // cell clears it densely — which scan that is only the device knows (DevState::
-                                    // dense_owed / dense_paid); the flag falls at the first sync behind it
-  bool obst_owe_armed = false;      // ... the device has been told about the current debt
-  unsigned obst_owe_seq = 0;
-  bool estimator_ready = false;     // ElevationMapping ctor ran (ensureLayers + obstacle layer)
-  bool use_records = true;          // pack the active estimator's state into cell records
-  float* d_rec = nullptr;           // [ncell][rec_floats]
-  int rec_kind = -1;                // -1 none, 0 Kalman, 1 P2
-  int rec_floats = 0;
-  float* d_tmp = nullptr;           // ncell floats: contiguous staging for strided layer transfers
-  bool cap_pre = false, cap_ras = false;  // scan-callback captures
-  bool cap_cov = false;                   // ... the preprocessed cloud with its 3x3 covariance channel
-  float* d_cap = nullptr;            // 4 channels x cap_cap points
-  size_t cap_cap = 0;
-  // the preprocessed cloud of a scan whose raycasting stage is HELD BACK with its update (option "ray_hold"): by scan
-  // parity — the next scan's bin half writes its own while the stage of this one has not run yet; 3 channels x rcap_cap
-  float* d_rcap[2] = {nullptr, nullptr};
-  size_t rcap_cap = 0;
-  int ray_hold = 1;
-  float* d_ras = nullptr;            // ncell
-  bool saved_want_ids = false;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float last_ms[3] = {0.f, 0.f, 0.f};
-  // raycasting stage (fdm_raycast.hpp)
-  uint32_t* rc_cnt = nullptr;        // [ncell] ray-scan points observed in the cell this frame
-  uint32_t* rc_min = nullptr;        // [ncell] ord(min ray height), kRayEmpty = not traversed
-  uint32_t* ray_bins = nullptr;      // large scans: ray-queue bucket counts | offsets | block sums (fdm_raycast.hpp)
-  unsigned long long* vkeys[2] = {nullptr, nullptr};  // voxel keys: unsorted / sorted
-  uint32_t* vidx[2] = {nullptr, nullptr};             // point indices: unsorted / sorted
-  uint32_t* vsel = nullptr;          // voxel_any output staging
-  uint32_t* ray_blk = nullptr;       // rays queued per block of k_ray_compact (large scans: block-local queue regions)
-  size_t vcap = 0;
-  void* sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
+  int sync_spin_us = 150;           // read_stats polls the pinned block this long before a stream wait (option)
+  int records = 1;                  // option "records": pack the active estimator's state into cell records (1, default) or one array per layer (0)
+  int move_clear_basic = 0;         // option "move_clear_basic": GridMap::move()'s strips clear {elevation, elevation_min, elevation_max} only (the other reading of nanoGrid: DESIGN.md §6); such an engine takes no batch launches
+  // ---- the large-scan (tiled) pipeline ----
+  int tiled = 1;                    // option "tiled": large scans go through per-tile record pools
+  int tiled_min = 2048;             // ... from this many points up (on a map of >= 512 tiles the pipeline wins at every
+                                    // size measured: 2 K points 13.1 vs 14.6 us, 32 K 16.6 vs 20.5, 262 K 18.9 vs 34.3)
+  int upd_blocks = 768;             // option "upd_blocks": update blocks (four tile wavefronts each) of a FUSED launch
+  int upd_blocks_alone = 2048;      // option "upd_blocks_alone": ... of an update launch of its own
+  int upd_prio = 1;                 // option "upd_prio": update wavefronts run at raised issue priority
+  int tiled_lds_pad = -1;           // option "tiled_lds_pad": extra dynamic LDS per block of the large-scan bin / fused launches; -1 = as much as
+                                    // makes it SIX blocks per CU (seven: configs[3] 32.3 -> 31.8 us at six; five — what the fixed 4 KB of round 5
+                                    // came to for a scan with an intensity channel, 29.7 KB per block — 31.4 -> 30.3 us at six, profiles/r06/probe_l.json)
+  int cnt_shift = 5;                // option "cnt_shift": one tile counter per 2^cnt_shift words (TilePool::cnt_shift); takes effect before the pools exist
+  int bin_delay = 0;                // option "bin_delay": see TileWork::delay (measurement: profiles/r06/probe_delay.json)
+  int bin_delay_blocks = 1024;      // option "bin_delay_blocks"
+  int bin_stagger = 0;              // option "bin_stagger": start stagger of the fused launch's first-round bin blocks (TileWork::stagger)
+  // ---- the batch pipeline ----
+  int batch = 1;                     // option "batch": fdm_engine_integrate_device_batch groups eligible scans
+  int batch_max = 0;                 // option "batch_max": scans per launch (2 .. kMaxBatch = 32); 0 = automatic: 32 with the quantile
+                                     // estimator or with raycasting on (configs[1] with it: 9.25 -> 7.78 us per scan), 16 with Kalman
+                                     // alone — measured (profiles/r06/batch_max.txt): configs[2] (P2, 272 K-point
+                                     // scans) 52.8 -> 56.9 G pts/s at 32, configs[1] (Kalman, 28.8 K-point scans) 27.0 -> 26.2: that
+                                     // launch is within ~2 x of its instruction-issue floor, a second round of blocks only adds its time
+  int batch_fuse = 1;                // option "batch_fuse": hold a batch's update back for the next batch's bin launch
+  int batch_crop = 1;                // option "batch_crop": evaluate the next batch's crops one launch ahead
+  int batch_walk = -1;               // option "batch_walk": the chain of moves walked one launch ahead (fdm_multi.hpp mwalk_body): -1 = for the quantile estimator only, 0 off, 1 on
+  int batch_ray = 1;                 // option "batch_ray": 0 = an engine with raycasting on takes the single-scan path
+  int batch_ray_seg = 4;             // option "batch_ray_seg": lanes per ray of k_rb_ray (1, 4, 8, 16)
+  int batch_ray_lds = 1;             // option "batch_ray_lds": 0 = always the global-atomic walk (k_rb_ray)
+  int batch_ray_parts = 0;           // option "batch_ray_parts": workgroups per quadrant and scan of k_rb_ray_lds (0 = fill the chip)
+  int batch_ray_words = 0;           // option "batch_ray_words": LDS image words of k_rb_ray_lds (0 = twice a centred sensor's quadrant)
+  // ---- the raycasting stage ----
   int voxel_small = 1;               // option "voxel_small": scans of <= 64 K points take the sort-free voxel filter
-  uint32_t* vs_cnt = nullptr;        // fine | coarse bucket counters | valid points of k_vs_*
-  uint4* vs_rec = nullptr;           // {key, point, bucket start, bucket size} by position
-  size_t vs_rec_cap = 0;
   int voxel_small_max = 1 << 16;     // option "voxel_small_max": largest scan that takes it
-  VoxelSmall vs{};                   // the last small-scan filter's parameters (k_vs_mark runs from enqueue_ray_stage)
   // option "voxel_any_order": 0 = ties inside a voxel in point order (stable sort, default); 1 = the order libstdc++'s
   // std::sort leaves (fdm_introsort.hpp), so VoxelMode::ANY picks what a g++ build of the reference picks.  While it is
   // on, the sort-free small-scan filter is not used and batch calls with raycasting go scan by scan (multi_run)
   int voxel_any_order = 0;
-  void* is_buf = nullptr;            // fdm_introsort.hpp's level buffers, rank tables, segment lists (is_layout)
-  size_t is_cap = 0;                 // pairs is_buf is laid out for
-  hipEvent_t ev_ray[2] = {nullptr, nullptr};
-  hipEvent_t ev_timer[2] = {nullptr, nullptr};  // fdm_engine_timer_start / _stop
-  bool ray_timed = false;
-  int dbg_ray = 0;
+  int ray_hold = 1;                  // option "ray_hold": the stage of a plain scan is held back with the scan's update and runs right behind it
   // scans from this many points up: bucketed ray queue, one lane per ray (option "ray_large_min").  Stage time, shared-
   // ray segments vs this path: 131 K points 0.48 vs 0.52 ms, 262 K 0.78 vs 0.57, 524 K 1.17 vs 0.67, RGB-D 272 K 0.23 vs 0.19
   int ray_large_min = 196608;
@@ -194,6 +151,97 @@ struct fdm_engine {
                                      // depends on the process: HIP maps streams onto four hardware queues, and in a process that has used
                                      // more than that (bench.py by the time of its large raycasting leg) the three streams of a stage
                                      // share queues and the events serialise them: 339 -> 365 us (profiles/r06/ray_overlap_ab.txt)
+  // ---- measurement only ----
+  int dbg_no_atomics = 0;            // option "dbg_no_atomics": results are wrong when set
+  int dbg_upd = 0;                   // option "dbg_upd" (ScanParams::dbg_upd)
+  int dbg_batch = 0;                 // measurement only (option "dbg_batch")
+  int dbg_ray = 0;                   // option "dbg_ray": bit switches of the raycasting stage (RayParams::dbg)
+  int dbg_post = 0;                  // measurement only: 1 = untiled feature kernel, 32 = fusion with integer samples, 64 = features with min / max chains
+};
+
+struct fdm_engine {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = true;
+  fdm_config cfg{};
+  EngineOptions opt;               // what fdm_engine_set_option sets (above)
+  GeomConst G{};
+  size_t ncell = 0;
+  std::vector<Layer> layers;
+  float** d_layer_ptrs = nullptr;  // device array of every layer pointer (strip clears)
+  int n_layer_ptrs = 0;
+  bool layer_ptrs_dirty = true;
+  Scratch S{};
+  DevState* d_state = nullptr;
+  DevState* h_state = nullptr;  // pinned mirror for read-backs
+  StatsOut* h_stats = nullptr;  // pinned + device-mapped: k_collect_stats writes here
+  StatsOut* h_stats_dev = nullptr;  // the device's alias of h_stats
+  unsigned long long stats_seq = 0; // sequence number of the last statistics launch (StatsOut::seq)
+  StatsAcc* d_stats_acc = nullptr;
+  uint64_t scan_no = 0;
+  bool have_scan = false;
+  uint32_t last_n = 0;        // points of the last scan as enqueued (array length of the captures / cell ids)
+  uint32_t last_n_input = 0;  // ... as the reference counts them (cloud.size(): finite points of a PointCloud2)
+  int next_drop_nonfinite = 0;  // set by fdm_engine_integrate_cloud2 for the scan it enqueues
+  unsigned ingest_blocks = 0; // > 0: the last scan came through k_ingest_soa; its finite count is still on the device
+  int last_was_integrate = 0;
+  // staging for the host-pointer entry points
+  float* d_stage = nullptr;
+  float4* d_aos = nullptr;  // fdm_engine_integrate_points4 on pageable memory: the cloud's {x, y, z, 1} records
+  size_t aos_cap = 0;
+  size_t stage_cap = 0;  // in points
+  int stage_rr = 0;      // rotating staging block
+  int32_t* d_cell_ids = nullptr;
+  size_t ids_cap = 0;
+  bool want_ids = false;
+  bool profile = false;
+  size_t bin_part_cap = 0;   // blocks
+  unsigned last_bin_blocks = 0;
+  std::vector<unsigned long long> h_bin_part;
+  unsigned n_tiles = 0;
+  std::vector<uint32_t> h_upd_part;
+  bool obst_dense_pending = false;  // host wrote the obstacle layer / the pipeline changed: the next scan that observes a
+                                    // cell clears it densely — which scan that is only the device knows (DevState::
+                                    // dense_owed / dense_paid); the flag falls at the first sync behind it
+  bool obst_owe_armed = false;      // ... the device has been told about the current debt
+  unsigned obst_owe_seq = 0;
+  bool estimator_ready = false;     // ElevationMapping ctor ran (ensureLayers + obstacle layer)
+  float* d_rec = nullptr;           // [ncell][rec_floats]
+  int rec_kind = -1;                // -1 none, 0 Kalman, 1 P2
+  int rec_floats = 0;
+  float* d_tmp = nullptr;           // ncell floats: contiguous staging for strided layer transfers
+  bool cap_pre = false, cap_ras = false;  // scan-callback captures
+  bool cap_cov = false;                   // ... the preprocessed cloud with its 3x3 covariance channel
+  float* d_cap = nullptr;            // 4 channels x cap_cap points
+  size_t cap_cap = 0;
+  // the preprocessed cloud of a scan whose raycasting stage is HELD BACK with its update (option "ray_hold"): by scan
+  // parity — the next scan's bin half writes its own while the stage of this one has not run yet; 3 channels x rcap_cap
+  float* d_rcap[2] = {nullptr, nullptr};
+  size_t rcap_cap = 0;
+  float* d_ras = nullptr;            // ncell
+  bool saved_want_ids = false;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float last_ms[3] = {0.f, 0.f, 0.f};
+  // raycasting stage (fdm_raycast.hpp)
+  uint32_t* rc_cnt = nullptr;        // [ncell] ray-scan points observed in the cell this frame
+  uint32_t* rc_min = nullptr;        // [ncell] ord(min ray height), kRayEmpty = not traversed
+  uint32_t* ray_bins = nullptr;      // large scans: ray-queue bucket counts | offsets | block sums (fdm_raycast.hpp)
+  unsigned long long* vkeys[2] = {nullptr, nullptr};  // voxel keys: unsorted / sorted
+  uint32_t* vidx[2] = {nullptr, nullptr};             // point indices: unsorted / sorted
+  uint32_t* vsel = nullptr;          // voxel_any output staging
+  uint32_t* ray_blk = nullptr;       // rays queued per block of k_ray_compact (large scans: block-local queue regions)
+  size_t vcap = 0;
+  void* sort_tmp = nullptr;
+  size_t sort_tmp_bytes = 0;
+  uint32_t* vs_cnt = nullptr;        // fine | coarse bucket counters | valid points of k_vs_*
+  uint4* vs_rec = nullptr;           // {key, point, bucket start, bucket size} by position
+  size_t vs_rec_cap = 0;
+  VoxelSmall vs{};                   // the last small-scan filter's parameters (k_vs_mark runs from enqueue_ray_stage)
+  void* is_buf = nullptr;            // fdm_introsort.hpp's level buffers, rank tables, segment lists (is_layout)
+  size_t is_cap = 0;                 // pairs is_buf is laid out for
+  hipEvent_t ev_ray[2] = {nullptr, nullptr};
+  hipEvent_t ev_timer[2] = {nullptr, nullptr};  // fdm_engine_timer_start / _stop
+  bool ray_timed = false;
   bool sync_call = false;            // a synchronous entry point is running (its flush follows the enqueue at once)
   struct RayBank {                   // the second set of the stage's buffers (ray_bank_swap)
     uint32_t *rc_cnt = nullptr, *rc_min = nullptr, *ray_bins = nullptr;
@@ -215,7 +263,6 @@ struct fdm_engine {
   unsigned long long* key2[2] = {nullptr, nullptr};  // scratch of even / odd scans ([0] == the original allocation)
   uint4* aux2[2] = {nullptr, nullptr};
   uint2* zs2[2] = {nullptr, nullptr};
-  bool overlap = true;          // option "overlap"
   bool chain = false;           // an update is held back: the next bin derives its geometry from the previous slot
   struct BinVariant { bool bin4, has_int, has_col, wave_merge; unsigned threads; int lean; };  // lean: see bin4_body
   // the held-back update (plain data: the layer set cannot change while it is pending, every entry
@@ -240,22 +287,7 @@ struct fdm_engine {
     double ray_box[6] = {0, 0, 0, 0, 0, 0};
   } pend;
   // ---- tiled pipeline state (allocated when the first large scan arrives) ----
-  bool borrow_inputs = false;       // option "borrow_inputs": a held-back update gathers from the CALLER's device arrays
-  int tiled = 1;                    // option "tiled": large scans go through per-tile record pools
-  unsigned tiled_min = 2048;        // ... from this many points up (on a map of >= 512 tiles the pipeline wins at every
-                                    // size measured: 2 K points 13.1 vs 14.6 us, 32 K 16.6 vs 20.5, 262 K 18.9 vs 34.3)
   bool tiled_forced = false;        // tiled_min was set by hand (option "tiled_min"): no map-size condition
-  int upd_blocks = 768;             // option "upd_blocks": update blocks (four tile wavefronts each) of a FUSED launch
-  int upd_blocks_alone = 2048;      // option "upd_blocks_alone": ... of an update launch of its own
-  int move_clear_basic = 0;         // option "move_clear_basic": GridMap::move()'s strips clear {elevation, elevation_min, elevation_max} only (the other reading of nanoGrid: DESIGN.md §6); such an engine takes no batch launches
-  int upd_prio = 1;                 // option "upd_prio": update wavefronts run at raised issue priority
-  int tiled_lds_pad = -1;           // option "tiled_lds_pad": extra dynamic LDS per block of the large-scan bin / fused launches; -1 = as much as
-                                    // makes it SIX blocks per CU (seven: configs[3] 32.3 -> 31.8 us at six; five — what the fixed 4 KB of round 5
-                                    // came to for a scan with an intensity channel, 29.7 KB per block — 31.4 -> 30.3 us at six, profiles/r06/probe_l.json)
-  int cnt_shift = 5;                // option "cnt_shift": one tile counter per 2^cnt_shift words (TilePool::cnt_shift); takes effect before the pools exist
-  int bin_delay = 0;                // option "bin_delay": see TileWork::delay (measurement: profiles/r06/probe_delay.json)
-  int bin_delay_blocks = 1024;      // option "bin_delay_blocks"
-  int bin_stagger = 0;              // option "bin_stagger": start stagger of the fused launch's first-round bin blocks (TileWork::stagger)
   size_t tile_rare_waves = 0;       // update wavefronts the rare-path scratch is sized for
   TileGrid TG{};
   TilePool pool[2] = {};            // by scan parity
@@ -269,13 +301,6 @@ struct fdm_engine {
   int last_kind = -1;               // pipeline of the last scan (0 scratch, 1 tiled)
   int last_do_move = 0, last_gate = 0;
   // ---- batch pipeline (fdm_multi.hpp): up to kMaxBatch small scans per launch, allocated by the first batch ----
-  int batch = 1;                     // option "batch": fdm_engine_integrate_device_batch groups eligible scans
-  int batch_max = 0;                 // option "batch_max": scans per launch (2 .. kMaxBatch = 32); 0 = automatic: 32 with the quantile
-                                     // estimator or with raycasting on (configs[1] with it: 9.25 -> 7.78 us per scan), 16 with Kalman
-                                     // alone — measured (profiles/r06/batch_max.txt): configs[2] (P2, 272 K-point
-                                     // scans) 52.8 -> 56.9 G pts/s at 32, configs[1] (Kalman, 28.8 K-point scans) 27.0 -> 26.2: that
-                                     // launch is within ~2 x of its instruction-issue floor, a second round of blocks only adds its time
-  int batch_fuse = 1;                // option "batch_fuse": hold a batch's update back for the next batch's bin launch
   unsigned long long* mkey[2] = {nullptr, nullptr};  // [kMaxBatch][ncell] per batch parity
   uint4* maux[2] = {nullptr, nullptr};
   uint2* mzs[2] = {nullptr, nullptr};
@@ -290,9 +315,6 @@ struct fdm_engine {
   int last_batch_n = 0;              // scans of the batch launch the last scan left in (0: it took the single-scan path)
   uint64_t n_mbatch = 0;             // batch launches since creation (fdm_engine_debug_batch_launches)
   bool fault_watch = false;          // a launch that can raise DevState::fault was enqueued since it was last read (none can since round 4)
-  int dbg_batch = 0;                 // measurement only (option "dbg_batch")
-  int batch_crop = 1;                // option "batch_crop": evaluate the next batch's crops one launch ahead
-  int batch_walk = -1;               // option "batch_walk": the chain of moves walked one launch ahead (fdm_multi.hpp mwalk_body): -1 = for the quantile estimator only, 0 off, 1 on
   unsigned long long batch_call = 0; // calls of fdm_engine_integrate_device_batch so far: a look-ahead is only ever honoured inside the call that made it
   unsigned long long pre_call = 0;
   bool pre_valid = false;            // the last launch carried the crop pass of the batch (pre_scans, pre_count) = number pre_seq
@@ -301,11 +323,6 @@ struct fdm_engine {
   unsigned pre_seq = 0;
   const unsigned long long* last_bin_part = nullptr;  // per-block statistics of the last scan (either pipeline)
   // ---- raycasting inside the small-scan batches (fdm_rbatch.hpp) ----
-  int batch_ray = 1;                 // option "batch_ray": 0 = an engine with raycasting on takes the single-scan path
-  int batch_ray_seg = 4;             // option "batch_ray_seg": lanes per ray of k_rb_ray (1, 4, 8, 16)
-  int batch_ray_lds = 1;             // option "batch_ray_lds": 0 = always the global-atomic walk (k_rb_ray)
-  int batch_ray_parts = 0;           // option "batch_ray_parts": workgroups per quadrant and scan of k_rb_ray_lds (0 = fill the chip)
-  int batch_ray_words = 0;           // option "batch_ray_words": LDS image words of k_rb_ray_lds (0 = twice a centred sensor's quadrant)
   unsigned rb_lds_words = 0;         // dynamic LDS k_rb_ray_lds may use, in 32-bit words (0: not asked yet)
   RState* rb_state = nullptr;
   float* rb_cap = nullptr;           // [3][kMaxBatch][rb_stride] preprocessed clouds of the batch being binned
@@ -330,7 +347,6 @@ struct fdm_engine {
   FeatEntry* d_feat_tab = nullptr;   // kMaxRegion entries: the region as k_features_tiled reads it
   std::vector<RegionEntry> h_region; // what d_region holds (upload_region skips an identical table)
   std::vector<FeatEntry> h_feat_tab; // what d_feat_tab holds
-  int dbg_post = 0;                  // measurement only: 1 = untiled feature kernel, 32 = fusion with integer samples, 64 = features with min / max chains
   unsigned long long* d_timeline = nullptr;  // measurement only: {start, end} ticks per block of the last fused launch
   unsigned timeline_cap = 0;         // blocks the buffer holds
   unsigned timeline_blocks = 0, timeline_upd = 0;  // grid of the last fused launch, its update blocks
@@ -350,9 +366,9 @@ struct fdm_engine {
   size_t pack_cap = 0;               // in floats
 };
 
-// ---- helpers shared by the library's translation units (fdm_engine.hip | fdm_engine_ray.hip | fdm_engine_post.hip) ----
+// ---- helpers shared by the library's translation units ----
 namespace fdmh {
-int join_streams(fdm_engine* e);
+int join_streams(fdm_engine* e);  // (a null engine: FDM_OK — every C entry point starts with it, ahead of its null checks)
 void poll_dense_paid(fdm_engine* e);
 int sync_all(fdm_engine* e);
 Layer* find_layer(fdm_engine* e, const char* name);
@@ -394,7 +410,7 @@ int run_held_ray_stage(fdm_engine* e, fdm_engine::PendingUpdate& u);
 int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const ScanParams& P);
 // the large-scan pipeline (fdm_engine_tiled.hip)
 int ensure_tile_aux(fdm_engine* e);
-int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks, bool has_int, bool has_col);
+int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks);
 unsigned update_blocks(const fdm_engine* e, bool fused);
 int launch_tbin(fdm_engine* e, const ScanParams& P, const ScanInputs& in, const TilePool& Q, int32_t* ids,
                 unsigned bin_blocks, fdm_engine::BinVariant bv);
@@ -473,6 +489,28 @@ int with_policy(fdm_engine* e, F&& f) {
 template <typename POLICY>
 constexpr bool is_rec_policy = std::is_same<POLICY, KalmanRecPolicy>::value || std::is_same<POLICY, P2RecPolicy>::value;
 
+// Runtime flags -> template arguments: with_constants(f, a, b, ...) calls f(A{}, B{}, ...), one std::integral_constant per
+// argument — a bool as it is, UpTo<N>{v} as an int in 0 .. N - 1 (clamped).  Every launch site that picks a kernel variant
+// by (has_int, has_col[, lean]) goes through it; f instantiates the whole product of its arguments, so a site whose
+// kernels cover only part of it says so with `if constexpr`.
+template <int N>
+struct UpTo { int v; };
+template <typename F>
+auto with_constants(F&& f) { return f(); }
+template <typename F, int N, typename... Rest>
+auto with_constants(F&& f, UpTo<N> k, Rest... rest);
+template <typename F, typename... Rest>
+auto with_constants(F&& f, bool b, Rest... rest) {
+  return b ? with_constants([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+           : with_constants([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+template <typename F, int N, typename... Rest>
+auto with_constants(F&& f, UpTo<N> k, Rest... rest) {
+  if constexpr (N > 1) {
+    if (k.v < N - 1) return with_constants(f, UpTo<N - 1>{k.v}, rest...);
+  }
+  return with_constants([&](auto... c) { return f(std::integral_constant<int, N - 1>{}, c...); }, rest...);
+}
 
 // kernels with more than 64 KB of dynamic LDS need the attribute once
 template <typename K>

@@ -1,5 +1,5 @@
 // fdm_engine_io.inl — host side of PointCloud2 ingest (fdm_ingest.hpp) and map egress (fdm_egress.hpp).
-// Part of fdm_engine_post.hip (one of the library's three translation units, fdm_engine_host.hpp).
+// Part of fdm_engine_post.hip (one of the library's five translation units, fdm_engine_host.hpp).
 
 namespace {
 // fdm_cloud2_layout -> IngestLayout; L.aligned covers the record layout only (the caller adds the blob's address)
@@ -26,7 +26,7 @@ extern "C" {
 // ---- ingest ----
 int fdm_engine_ingest_cloud2(fdm_engine* e, const void* data, int on_device, uint64_t n_points,
                              const fdm_cloud2_layout* lay, uint64_t* n_valid) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !lay) return fail(FDM_ERR_INVALID, "null argument");
   if (n_valid) *n_valid = 0;
   e->in_n = 0;
@@ -102,7 +102,7 @@ int fdm_engine_ingested(fdm_engine* e, const float** dx, const float** dy, const
 int fdm_engine_integrate_cloud2(fdm_engine* e, const void* data, int on_device, uint64_t n_points,
                                 const fdm_cloud2_layout* lay, const double Tbs[16], const double Twb[16],
                                 fdm_scan_stats* out) {
-  if (e) { if (int rc_join = join_streams(e)) return rc_join; }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !lay || !Tbs || !Twb) return fail(FDM_ERR_INVALID, "null argument");
   auto empty = [&]() {  // fastdem.cpp:125-128
     if (out) std::memset(out, 0, sizeof(*out));
@@ -119,7 +119,7 @@ int fdm_engine_integrate_cloud2(fdm_engine* e, const void* data, int on_device, 
   const size_t bytes = size_t(n_points) * L.point_step;
   const uint8_t* blob = static_cast<const uint8_t*>(data);
   if (!on_device) {
-    const void* alias = e->zero_copy ? pinned_alias(data) : nullptr;
+    const void* alias = e->opt.zero_copy ? pinned_alias(data) : nullptr;
     if (alias) {
       blob = static_cast<const uint8_t*>(alias);
     } else {
@@ -257,7 +257,7 @@ void write_fields(const PackPlan& pl, char* buf, uint64_t cap) {
 int fdm_engine_pack_cloud_device(fdm_engine* e, const char* elevation_layer, int32_t r0, int32_t c0,
                                  int32_t nr, int32_t nc, void** d_out, uint64_t* n_points,
                                  uint32_t* point_step) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !elevation_layer || !n_points) return fail(FDM_ERR_INVALID, "null argument");
   HIPCK(hipSetDevice(e->device));
   PackPlan pl;
@@ -273,7 +273,7 @@ int fdm_engine_pack_cloud_device(fdm_engine* e, const char* elevation_layer, int
 int fdm_engine_pack_cloud(fdm_engine* e, const char* elevation_layer, int32_t r0, int32_t c0, int32_t nr,
                           int32_t nc, void* host_out, uint64_t cap_bytes, uint64_t* n_points,
                           uint32_t* point_step, char* fields_buf, uint64_t fields_cap) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !elevation_layer || !n_points) return fail(FDM_ERR_INVALID, "null argument");
   HIPCK(hipSetDevice(e->device));
   PackPlan pl;

@@ -39,34 +39,19 @@ int launch_update_fused(fdm_engine* e, const fdm_engine::PendingUpdate& u, const
                          e->d_layer_ptrs, e->n_layer_ptrs, u.S, u.in, unsigned(e->ncell), ub, Pb, Sb, Ib, ids_b);
     };
     if (!bv.bin4) {
-      if (!u.S.dense) {  // stamp-gated maps: one generic variant
-        go(k_update_bin<POLICY, true, true>, 256u);
-      } else if (kRec && bv.lean == 1) {  // channel tests folded at compile time, optional work compiled out
-        if constexpr (kRec) {
-          if (bv.has_int && bv.has_col) go(k_update_bin<POLICY, true, false, 3, 1>, 256u);
-          else if (bv.has_col) go(k_update_bin<POLICY, true, false, 2, 1>, 256u);
-          else if (bv.has_int) go(k_update_bin<POLICY, true, false, 1, 1>, 256u);
-          else go(k_update_bin<POLICY, true, false, 0, 1>, 256u);
-        }
-      } else if (kRec && bv.lean == 2) {  // ... but x / y / z written through to the engine's staging block
-        if constexpr (kRec) {
-          if (bv.has_int && bv.has_col) go(k_update_bin<POLICY, true, false, 3, 2>, 256u);
-          else if (bv.has_col) go(k_update_bin<POLICY, true, false, 2, 2>, 256u);
-          else if (bv.has_int) go(k_update_bin<POLICY, true, false, 1, 2>, 256u);
-          else go(k_update_bin<POLICY, true, false, 0, 2>, 256u);
-        }
-      } else {  // everything else (captures, cell ids, per-layer layout ...): channels read from ScanParams
-        go(k_update_bin<POLICY, true, false>, 256u);
-      }
+      with_constants([&](auto dense, auto lean, auto ch) {  // ch: intensity | colour << 1
+        if constexpr (!dense())  // stamp-gated maps: one generic variant
+          go(k_update_bin<POLICY, true, true>, 256u);
+        else if constexpr (kRec && lean() != 0)  // channel tests folded at compile time, optional work compiled out
+          go(k_update_bin<POLICY, true, false, ch(), lean()>, 256u);  // (lean 2: x / y / z written through to the staging block)
+        else  // everything else (captures, cell ids, per-layer layout ...): channels read from ScanParams
+          go(k_update_bin<POLICY, true, false>, 256u);
+      }, u.S.dense != 0, UpTo<3>{bv.lean}, UpTo<4>{int(bv.has_int) + 2 * int(bv.has_col)});
     } else if constexpr (kRec) {
       if (!u.S.dense) return fail(FDM_ERR_INVALID, "internal: k_bin4 fused with a stamp-gated update");
-#define FDM_FUSED4(LN)                                                                       \
-      if (bv.has_int && bv.has_col) go(k_update_bin4<POLICY, true, true, 256, false, LN>, 256u);   \
-      else if (bv.has_int) go(k_update_bin4<POLICY, true, false, 256, false, LN>, 256u);           \
-      else if (bv.has_col) go(k_update_bin4<POLICY, false, true, 256, false, LN>, 256u);           \
-      else go(k_update_bin4<POLICY, false, false, 256, false, LN>, 256u);
-      if (bv.lean == 1) { FDM_FUSED4(1) } else if (bv.lean == 2) { FDM_FUSED4(2) } else { FDM_FUSED4(0) }
-#undef FDM_FUSED4
+      with_constants([&](auto hi, auto hc, auto lean) {
+        go(k_update_bin4<POLICY, hi(), hc(), 256, false, lean()>, 256u);
+      }, bv.has_int, bv.has_col, UpTo<3>{bv.lean});
     } else {
       return fail(FDM_ERR_INVALID, "internal: k_bin4 fused with a per-layer policy");
     }

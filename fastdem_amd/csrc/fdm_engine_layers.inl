@@ -3,7 +3,7 @@
 // Part of fdm_engine.hip's translation unit (inside its extern "C" block): do not compile on its own.
 
 int fdm_engine_move(fdm_engine* e, double x, double y) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (e->G.s_rows != e->G.rows || e->G.s_cols != e->G.cols)
     return fail(FDM_ERR_INVALID, "move() is not defined for tiled engines");
@@ -14,7 +14,7 @@ int fdm_engine_move(fdm_engine* e, double x, double y) {
 }
 
 int fdm_engine_get_geometry(fdm_engine* e, fdm_geometry* out) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !out) return fail(FDM_ERR_INVALID, "null argument");
   if (int rc_sync = sync_all(e)) return rc_sync;
   DevGeom g;
@@ -32,7 +32,7 @@ int fdm_engine_get_geometry(fdm_engine* e, fdm_geometry* out) {
 }
 
 int fdm_engine_set_position(fdm_engine* e, double x, double y) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (int rc_sync = sync_all(e)) return rc_sync;
   const double p[2] = {x, y};
@@ -41,7 +41,7 @@ int fdm_engine_set_position(fdm_engine* e, double x, double y) {
 }
 
 int fdm_engine_set_start_index(fdm_engine* e, int32_t row, int32_t col) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (row < 0 || col < 0 || row >= e->G.rows || col >= e->G.cols)
     return fail(FDM_ERR_INVALID, "start index out of range");
@@ -54,7 +54,7 @@ int fdm_engine_set_start_index(fdm_engine* e, int32_t row, int32_t col) {
 }
 
 int fdm_engine_num_layers(fdm_engine* e) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (int rc = resolve_pending(e)) return rc;
   int n = 0;
@@ -63,7 +63,7 @@ int fdm_engine_num_layers(fdm_engine* e) {
 }
 
 const char* fdm_engine_layer_name(fdm_engine* e, int i) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return nullptr; } }
+  if (join_streams(e)) return nullptr;
   if (!e) return nullptr;
   if (resolve_pending(e)) return nullptr;
   int k = 0;
@@ -75,7 +75,7 @@ const char* fdm_engine_layer_name(fdm_engine* e, int i) {
 }
 
 int fdm_engine_layer_exists(fdm_engine* e, const char* name) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !name) return fail(FDM_ERR_INVALID, "null argument");
   if (int rc = resolve_pending(e)) return rc;
   Layer* l = find_layer(e, name);
@@ -83,7 +83,7 @@ int fdm_engine_layer_exists(fdm_engine* e, const char* name) {
 }
 
 int fdm_engine_layer_add(fdm_engine* e, const char* name, float value) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !name) return fail(FDM_ERR_INVALID, "null argument");
   HIPCK(hipSetDevice(e->device));
   if (std::strcmp(name, "obstacle") == 0) { e->obst_dense_pending = true; e->obst_owe_armed = false; }
@@ -92,7 +92,7 @@ int fdm_engine_layer_add(fdm_engine* e, const char* name, float value) {
 }
 
 int fdm_engine_layer_download(fdm_engine* e, const char* name, float* host, int32_t rows, int32_t cols) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !name || !host) return fail(FDM_ERR_INVALID, "null argument");
   if (rows != e->G.s_rows || cols != e->G.s_cols) return fail(FDM_ERR_INVALID, "shape mismatch");
   if (int rc = resolve_pending(e)) return rc;
@@ -110,7 +110,7 @@ int fdm_engine_layer_download(fdm_engine* e, const char* name, float* host, int3
 }
 
 int fdm_engine_layer_upload(fdm_engine* e, const char* name, const float* host, int32_t rows, int32_t cols) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !name || !host) return fail(FDM_ERR_INVALID, "null argument");
   if (rows != e->G.s_rows || cols != e->G.s_cols) return fail(FDM_ERR_INVALID, "shape mismatch");
   HIPCK(hipSetDevice(e->device));
@@ -160,14 +160,14 @@ int fdm_engine_layer_copy(fdm_engine* dst, fdm_engine* src, const char* name) {
 }
 
 float* fdm_engine_layer_device_ptr(fdm_engine* e, const char* name) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return nullptr; } }
+  if (join_streams(e)) return nullptr;
   if (!e || !name) return nullptr;
   Layer* l = find_layer(e, name);
   return (l && l->field < 0) ? l->d : nullptr;  // record fields have no contiguous array
 }
 
 int fdm_engine_clear(fdm_engine* e, const char* name) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   HIPCK(hipSetDevice(e->device));
   if (name) {
@@ -222,12 +222,12 @@ static int regions_copy(fdm_engine* e, int n_rects, const fdm_region* rects, con
 
 int fdm_engine_regions_pack(fdm_engine* e, int32_t n_rects, const fdm_region* rects, const char* const* names,
                             int n_layers, float* d_buf) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   return regions_copy(e, n_rects, rects, names, n_layers, d_buf, 1);
 }
 int fdm_engine_regions_unpack(fdm_engine* e, int32_t n_rects, const fdm_region* rects, const char* const* names,
                               int n_layers, const float* d_buf) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   return regions_copy(e, n_rects, rects, names, n_layers, const_cast<float*>(d_buf), 0);
 }
 int fdm_engine_region_pack(fdm_engine* e, int32_t r0, int32_t c0, int32_t nr, int32_t nc,

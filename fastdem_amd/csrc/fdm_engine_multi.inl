@@ -13,26 +13,26 @@ bool affine_last_row(const double* T) { return T[3] == 0.0 && T[7] == 0.0 && T[1
 // (enqueue_scan's `plain`), on the per-cell scratch pipeline with the one-point-per-thread bin kernel, from ONE
 // sensor (same T_base_sensor) and with the same optional channels.
 uint32_t multi_run(fdm_engine* e, uint32_t count, const fdm_device_scan* scans) {
-  if (!e->batch || count < 2u || !e->overlap || !e->wave_merge || e->bin_variant == 4) return 0u;
+  if (!e->opt.batch || count < 2u || !e->opt.overlap || !e->opt.wave_merge || e->opt.bin_variant == 4) return 0u;
   if (!e->estimator_ready || e->rec_kind < 0 || !e->S.dense || e->ncell > kBatchMaxCells) return 0u;
   if (e->cap_pre || e->cap_ras || e->want_ids || e->profile) return 0u;
   // raycasting on (fastdem.cpp:152-159): the stage rides in the batch (fdm_rbatch.hpp) if every scan can take the
   // sort-free voxel filter on compact keys and the engine holds the whole map
   const bool ray = e->cfg.raycast_enabled != 0;
   if (ray) {
-    if (!e->batch_ray || !e->voxel_small || !voxel_size_ok(static_cast<float>(e->G.res))) return 0u;
-    if (e->voxel_any_order) return 0u;  // (the batch's filter is the sort-free one: ties in point order)
+    if (!e->opt.batch_ray || !e->opt.voxel_small || !voxel_size_ok(static_cast<float>(e->G.res))) return 0u;
+    if (e->opt.voxel_any_order) return 0u;  // (the batch's filter is the sort-free one: ties in point order)
     if (e->G.o_rows != e->G.rows || e->G.o_cols != e->G.cols || e->G.s_rows != e->G.rows || e->G.s_cols != e->G.cols) return 0u;
   }
   poll_dense_paid(e);
   if (e->obst_dense_pending || e->last_kind == 1 || e->next_drop_nonfinite) return 0u;
-  if (e->dbg_no_atomics || e->dbg_upd || e->move_clear_basic) return 0u;
+  if (e->opt.dbg_no_atomics || e->opt.dbg_upd || e->opt.move_clear_basic) return 0u;
   const fdm_device_scan& f = scans[0];
   const size_t kt = e->ncell / 1024u;  // (the thresholds below were measured in units of 1 024 cells, round 2)
   uint32_t run = 0;
   // (automatic: 32 with the quantile estimator, and with raycasting on — a batch is then seven launches, five of them the
   //  ray stage's, whose fixed costs halve per scan: configs[1] 9.25 -> 7.78 us per scan, 24 per launch 8.3; 16 for Kalman alone)
-  const uint32_t batch_max = e->batch_max > 0 ? uint32_t(e->batch_max)
+  const uint32_t batch_max = e->opt.batch_max > 0 ? uint32_t(e->opt.batch_max)
                                               : ((e->cfg.estimation_type == 1 || ray) ? uint32_t(kMaxBatch) : 16u);
   const uint32_t cap = std::min<uint32_t>(count, batch_max);
   for (; run < cap; ++run) {
@@ -41,14 +41,14 @@ uint32_t multi_run(fdm_engine* e, uint32_t count, const fdm_device_scan* scans) 
     if (s.n >= 393216u) break;  // the 4-points-per-thread kernels take over there (enqueue_scan)
     // ... and the record-pool pipeline on maps with enough tiles
     const bool enough_tiles = e->tiled_forced || kt >= 240 || (kt >= 160 && s.n >= 100000);
-    if (e->tiled && s.n >= e->tiled_min && enough_tiles) break;
+    if (e->opt.tiled && s.n >= uint64_t(e->opt.tiled_min) && enough_tiles) break;
     if ((s.intensity != nullptr) != (f.intensity != nullptr) || (s.rgb != nullptr) != (f.rgb != nullptr) ||
         (s.sigma_z2 != nullptr) != (f.sigma_z2 != nullptr))
       break;
     if (!affine_last_row(s.T_base_sensor) || !affine_last_row(s.T_world_base)) break;
     if (std::memcmp(s.T_base_sensor, f.T_base_sensor, 16 * sizeof(double)) != 0) break;
     if (ray) {
-      if (s.n > uint64_t(e->voxel_small_max)) break;
+      if (s.n > uint64_t(e->opt.voxel_small_max)) break;
       ScanParams P;
       double box[6];
       fill_integrate_params(e, P, s.T_base_sensor, s.T_world_base);
@@ -185,14 +185,14 @@ int launch_rbatch(fdm_engine* e, const RBatch& R) {
       (void)hipGetLastError();
   }
   const size_t quadrant = (size_t(e->G.rows) / 2 + 2) * (size_t(e->G.cols) / 2 + 2);
-  if (e->batch_ray_lds && quadrant * 2 <= e->rb_lds_words) {
-    unsigned parts = e->batch_ray_parts > 0 ? unsigned(e->batch_ray_parts) : std::max(1u, 256u / (4u * R.count));
+  if (e->opt.batch_ray_lds && quadrant * 2 <= e->rb_lds_words) {
+    unsigned parts = e->opt.batch_ray_parts > 0 ? unsigned(e->opt.batch_ray_parts) : std::max(1u, 256u / (4u * R.count));
     parts = std::min(parts, std::max(1u, (max_n + kRbRayThreads - 1u) / kRbRayThreads));
     // (LDS for twice a centred sensor's quadrant — a LOCAL map follows the robot, a GLOBAL map's sensor may wander: a
     // larger quadrant takes the kernel's global-atomic loop — or for the whole map when that is less)
     const unsigned words = unsigned(std::min<size_t>({size_t(e->rb_lds_words), size_t(e->G.rows) * size_t(e->G.cols),
-                                                      e->batch_ray_words > 0 ? size_t(e->batch_ray_words) : quadrant * 2}));
-    if (e->dbg_ray & (1 << 20))  // (dbg_ray 1048576, measurement only: the integer image of round 4)
+                                                      e->opt.batch_ray_words > 0 ? size_t(e->opt.batch_ray_words) : quadrant * 2}));
+    if (e->opt.dbg_ray & (1 << 20))  // (dbg_ray 1048576, measurement only: the integer image of round 4)
       hipLaunchKernelGGL(k_rb_ray_lds<false>, dim3(4u * parts, R.count), dim3(kRbRayThreads), words * sizeof(uint32_t),
                          e->stream, R, e->G, parts, words);
     else
@@ -205,7 +205,7 @@ int launch_rbatch(fdm_engine* e, const RBatch& R) {
       const unsigned threads = ((max_n + 63u) & ~63u) * unsigned(SEG);
       hipLaunchKernelGGL((k_rb_ray<SEG>), dim3((threads + 255u) / 256u, R.count, 4), dim3(256), 0, e->stream, R, e->G);
     };
-    switch (e->batch_ray_seg) {
+    switch (e->opt.batch_ray_seg) {
       case 1: rays(std::integral_constant<int, 1>{}); break;
       case 8: rays(std::integral_constant<int, 8>{}); break;
       case 16: rays(std::integral_constant<int, 16>{}); break;
@@ -214,16 +214,6 @@ int launch_rbatch(fdm_engine* e, const RBatch& R) {
   }
   HIPCK(hipGetLastError());
   return FDM_OK;
-}
-
-template <typename F>
-int with_channels(int ch, F&& f) {
-  switch (ch & 3) {
-    case 0: return f(std::integral_constant<int, 0>{});
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    default: return f(std::integral_constant<int, 3>{});
-  }
 }
 
 // One k_mbatch launch: [ update U | bin B | crop Cn ], any of which may be empty (count == 0).
@@ -246,17 +236,12 @@ int launch_mbatch(fdm_engine* e, int ch, const MUpd& U, const MBin& B, const MCr
   return with_policy(e, [&](auto tag, const auto& layers) -> int {
     using POLICY = decltype(tag);
     if constexpr (is_rec_policy<POLICY>) {
-      return with_channels(ch, [&](auto chc) -> int {
-        constexpr int CH = decltype(chc)::value;
-        if (U.ray.stamp != 0u || B.cap != nullptr)  // (a half with raycasting: the variant whose update resolves ray events)
-          hipLaunchKernelGGL((k_mbatch<POLICY, CH, true>), dim3(gx, rows), dim3(256), 0, e->stream, U, B, Cn, Kt, e->G,
-                             e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs, unsigned(e->ncell), ub, urows);
-        else
-          hipLaunchKernelGGL((k_mbatch<POLICY, CH, false>), dim3(gx, rows), dim3(256), 0, e->stream, U, B, Cn, Kt, e->G,
-                             e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs, unsigned(e->ncell), ub, urows);
+      return with_constants([&](auto chc, auto ray) -> int {  // (ray: the variant whose update resolves ray events)
+        hipLaunchKernelGGL((k_mbatch<POLICY, chc(), ray()>), dim3(gx, rows), dim3(256), 0, e->stream, U, B, Cn, Kt, e->G,
+                           e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs, unsigned(e->ncell), ub, urows);
         HIPCK(hipGetLastError());
         return FDM_OK;
-      });
+      }, UpTo<4>{ch & 3}, U.ray.stamp != 0u || B.cap != nullptr);  // (a half with raycasting)
     } else {
       return fail(FDM_ERR_INVALID, "internal: batch launch with a per-layer policy");
     }
@@ -338,14 +323,14 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   K.do_move = P.do_move;
   K.gate_on_filter = P.gate_on_filter;
   K.has_var = hv ? 1 : 0;
-  K.bin_table = e->bin_table;
-  K.dbg = e->dbg_batch;
+  K.bin_table = e->opt.bin_table;
+  K.dbg = e->opt.dbg_batch;
   // the chain of moves walked one launch ahead (mwalk_body): automatic = every scan of a quantile-estimator batch; for
   // Kalman without the ray stage only the scans from kKalmanWalkFrom on (the longest chains) — the earlier rows walk their
   // own, which staggers their flushes behind the update half (profiles/r07: all rows at once, 17.6 us per launch against
   // 15.6; rows 12-15 only, 24.2 -> 25.2 G pts/s); 1 = every scan of every batch
-  K.walk = e->batch_walk < 0 ? ((e->cfg.estimation_type == 1 || !ray) ? 1 : 0) : e->batch_walk;
-  K.walk_from = (e->batch_walk < 0 && e->cfg.estimation_type != 1) ? kKalmanWalkFrom : 0;
+  K.walk = e->opt.batch_walk < 0 ? ((e->cfg.estimation_type == 1 || !ray) ? 1 : 0) : e->opt.batch_walk;
+  K.walk_from = (e->opt.batch_walk < 0 && e->cfg.estimation_type != 1) ? kKalmanWalkFrom : 0;
 
   const unsigned seq = e->mseq++;
   const int slot = int(seq % unsigned(kMStates)), par = int(seq & 1u);
@@ -400,7 +385,7 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   }
   B.pre = 1u;
   // ... and the scouts of the batch after this one ride in this launch (option "batch_crop" 0: they never do)
-  if (next_count >= 2u && gated && e->batch_crop &&
+  if (next_count >= 2u && gated && e->opt.batch_crop &&
       std::memcmp(scans[count].T_base_sensor, f.T_base_sensor, 16 * sizeof(double)) == 0) {
     fill_scouts(Cn, next_count, scans + count, e->mstate + int((seq + 1u) % unsigned(kMStates)));
     e->pre_valid = true;
@@ -420,7 +405,7 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
     R.stamp = e->rb_seq;
     R.do_move = K.do_move;
     R.gate_on_filter = K.gate_on_filter;
-    R.dbg = e->dbg_ray;
+    R.dbg = e->opt.dbg_ray;
     R.ms = B.ms;
     R.rs = e->rb_state;
     R.resolution = static_cast<float>(e->G.res);
@@ -466,7 +451,7 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   e->chain = true;
   e->last_do_move = P.do_move;
   e->last_gate = P.gate_on_filter;
-  if (!e->batch_fuse && (rc = join_streams(e))) return rc;
+  if (!e->opt.batch_fuse && (rc = join_streams(e))) return rc;
   // bookkeeping as enqueue_scan leaves it after the batch's last scan
   const fdm_device_scan& l = scans[count - 1u];
   e->last_kind = 0;

@@ -1,8 +1,8 @@
-// fdm_engine_opts.inl — scan-callback captures, per-point cell ids, the per-launch profile and fdm_engine_set_option.
+// fdm_engine_opts.inl — scan-callback captures, per-point cell ids, the per-launch profile and fdm_engine_set_option (the option table).
 // Part of fdm_engine.hip's translation unit (inside its extern "C" block): do not compile on its own.
 
 int fdm_engine_capture(fdm_engine* e, int preprocessed, int rasterized) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   e->cap_pre = preprocessed != 0;
   e->cap_cov = preprocessed == 2;
@@ -13,7 +13,7 @@ int fdm_engine_capture(fdm_engine* e, int preprocessed, int rasterized) {
 
 int fdm_engine_last_preprocessed(fdm_engine* e, uint64_t cap, float* x, float* y, float* z,
                                  float* sigma_z2, uint64_t* n_out) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !n_out) return fail(FDM_ERR_INVALID, "null argument");
   *n_out = 0;
   if (!e->cap_pre) return fail(FDM_ERR_INVALID, "preprocessed-scan capture is off");
@@ -41,7 +41,7 @@ int fdm_engine_last_preprocessed(fdm_engine* e, uint64_t cap, float* x, float* y
 }
 
 int fdm_engine_last_preprocessed_cov(fdm_engine* e, uint64_t cap, float* cov9, uint64_t* n_out) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !n_out || !cov9) return fail(FDM_ERR_INVALID, "null argument");
   *n_out = 0;
   if (!e->cap_pre || !e->cap_cov) return fail(FDM_ERR_INVALID, "covariance capture is off (fdm_engine_capture(e, 2, ..))");
@@ -66,7 +66,7 @@ int fdm_engine_last_preprocessed_cov(fdm_engine* e, uint64_t cap, float* cov9, u
 
 int fdm_engine_last_rasterized(fdm_engine* e, uint64_t cap, float* x, float* y, float* z,
                                uint64_t* n_out) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !n_out) return fail(FDM_ERR_INVALID, "null argument");
   *n_out = 0;
   if (!e->cap_ras) return fail(FDM_ERR_INVALID, "rasterized-scan capture is off");
@@ -98,14 +98,14 @@ int fdm_engine_last_rasterized(fdm_engine* e, uint64_t cap, float* x, float* y, 
 }
 
 int fdm_engine_enable_cell_ids(fdm_engine* e, int on) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   e->want_ids = on != 0;
   return FDM_OK;
 }
 
 int fdm_engine_last_cell_ids(fdm_engine* e, int32_t* host_out, uint64_t n) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !host_out) return fail(FDM_ERR_INVALID, "null argument");
   if (!e->want_ids || !e->d_cell_ids || n != e->last_n)
     return fail(FDM_ERR_INVALID, "cell ids not recorded for the last scan");
@@ -115,7 +115,7 @@ int fdm_engine_last_cell_ids(fdm_engine* e, int32_t* host_out, uint64_t n) {
 }
 
 int fdm_engine_enable_profile(fdm_engine* e, int on) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   e->profile = on != 0;
   return FDM_OK;
@@ -136,217 +136,135 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2) {
   return FDM_OK;
 }
 
-/* tuning knob used by bench.py's A/B runs (not part of the reference surface) */
+// ---- fdm_engine_set_option: one table (kOptions), one lookup-and-apply routine, five hooks ----
+// What a row accepts and how the value is normalised before it is stored.
+struct OptRule {
+  enum Kind { kBool, kRaw, kAtLeast, kRange, kOneOf } kind;
+  long long a, b;       // kAtLeast: clamp from below to a; kRange: a .. b inclusive; kOneOf: a = bit mask of the accepted values
+  const char* accepts;  // the error message after "<name>: "
+};
+constexpr OptRule opt_bool() { return {OptRule::kBool, 0, 1, ""}; }  // stored as value != 0
+constexpr OptRule opt_raw() { return {OptRule::kRaw, 0, 0, ""}; }    // measurement switches: any value
+constexpr OptRule opt_at_least(long long lo) { return {OptRule::kAtLeast, lo, 0, ""}; }
+constexpr OptRule opt_range(long long lo, long long hi, const char* accepts) { return {OptRule::kRange, lo, hi, accepts}; }
+constexpr OptRule opt_one_of(unsigned long long mask, const char* accepts) {
+  return {OptRule::kOneOf, static_cast<long long>(mask), 0, accepts};
+}
+constexpr unsigned long long bits(int lo, int hi) { return ((1ull << (hi + 1)) - 1ull) & ~((1ull << lo) - 1ull); }
+constexpr long long kAnyCount = std::numeric_limits<int>::max();
+
+// The hooks: what is more than a plain store.  A hook runs behind the row's checks and barrier and ahead of the store;
+// an error leaves the field as it was.
+static int opt_records(fdm_engine* e, int v) {  // repack (or unpack) the estimator's layers now
+  e->opt.records = v;
+  return e->estimator_ready ? activate_records(e, e->cfg.estimation_type == 1 ? 1 : 0) : FDM_OK;
+}
+static int opt_dense(fdm_engine* e, int v) {  // force stamp-gated (0) or dense (1) update sweeps
+  e->S.dense = v;
+  e->obst_dense_pending = true;  // stamps were not maintained while dense
+  e->obst_owe_armed = false;
+  return FDM_OK;
+}
+static int opt_dbg_timeline(fdm_engine* e, int v) {  // measurement only: block start / end ticks of the fused tiled launches
+  if (e->d_timeline) { (void)hipFree(e->d_timeline); e->d_timeline = nullptr; }
+  e->timeline_cap = 0;
+  if (v > 0) {
+    e->timeline_cap = 1u << 16;
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_timeline), size_t(e->timeline_cap) * 16));
+    HIPCK(hipMemset(e->d_timeline, 0, size_t(e->timeline_cap) * 16));
+  }
+  return FDM_OK;
+}
+static int opt_tiled_min(fdm_engine* e, int) {  // set by hand: no map-size condition (enqueue_scan)
+  e->tiled_forced = true;
+  return FDM_OK;
+}
+static int opt_cnt_shift(fdm_engine* e, int) {
+  return e->pool[0].cnt ? fail(FDM_ERR_INVALID, "cnt_shift: the record pools exist already") : FDM_OK;
+}
+
+struct OptionRow {
+  const char* name;
+  int EngineOptions::*field;  // null: the hook is all there is to it
+  OptRule rule;
+  bool sync;                  // sync_all ahead of the write (every option joins the streams first)
+  int (*hook)(fdm_engine*, int);
+};
+// In the order of EngineOptions' fields (fdm_engine_host.hpp, where each option is documented) and of the list in
+// include/fdm_engine.h, which tests/test_option_table.py holds against this table.
+static const OptionRow kOptions[] = {
+  // the scan path
+  {"wave_merge", &EngineOptions::wave_merge, opt_bool(), false, nullptr},
+  {"bin_table", &EngineOptions::bin_table, opt_bool(), false, nullptr},
+  {"bin_variant", &EngineOptions::bin_variant, opt_one_of(1 | 2 | 16, "0, 1 or 4"), false, nullptr},
+  {"overlap", &EngineOptions::overlap, opt_bool(), false, nullptr},
+  {"borrow_inputs", &EngineOptions::borrow_inputs, opt_bool(), false, nullptr},
+  {"zero_copy", &EngineOptions::zero_copy, opt_range(0, kAnyCount, "a point count (0 = off)"), false, nullptr},
+  {"sync_spin_us", &EngineOptions::sync_spin_us, opt_at_least(0), false, nullptr},
+  {"records", &EngineOptions::records, opt_bool(), false, opt_records},
+  {"dense", nullptr, opt_bool(), false, opt_dense},
+  {"move_clear_basic", &EngineOptions::move_clear_basic, opt_bool(), true, nullptr},
+  // the large-scan pipeline
+  {"tiled", &EngineOptions::tiled, opt_bool(), false, nullptr},
+  {"tiled_min", &EngineOptions::tiled_min, opt_range(0, kAnyCount, "a point count"), false, opt_tiled_min},
+  {"upd_blocks", &EngineOptions::upd_blocks, opt_range(1, 65535, "1 .. 65535"), true, nullptr},
+  {"upd_blocks_alone", &EngineOptions::upd_blocks_alone, opt_range(1, 65535, "1 .. 65535"), true, nullptr},
+  {"upd_prio", &EngineOptions::upd_prio, opt_bool(), false, nullptr},
+  {"tiled_lds_pad", &EngineOptions::tiled_lds_pad, opt_range(-1, 120 * 1024, "-1 (automatic) or 0 .. 122880 bytes"), false, nullptr},
+  {"cnt_shift", &EngineOptions::cnt_shift, opt_range(0, 5, "0 .. 5"), false, opt_cnt_shift},
+  {"bin_delay", &EngineOptions::bin_delay, opt_range(0, 65535, "0 .. 65535"), false, nullptr},
+  {"bin_delay_blocks", &EngineOptions::bin_delay_blocks, opt_range(0, 65535, "0 .. 65535"), false, nullptr},
+  {"bin_stagger", &EngineOptions::bin_stagger, opt_range(0, 64, "0 .. 64"), false, nullptr},
+  // the batch pipeline
+  {"batch", &EngineOptions::batch, opt_bool(), false, nullptr},
+  {"batch_max", &EngineOptions::batch_max, opt_one_of(1 | bits(2, kMaxBatch), "0 (automatic) or 2 .. 32 scans per launch"), false, nullptr},
+  {"batch_fuse", &EngineOptions::batch_fuse, opt_bool(), false, nullptr},
+  {"batch_crop", &EngineOptions::batch_crop, opt_bool(), false, nullptr},
+  {"batch_walk", &EngineOptions::batch_walk, opt_range(-1, 1, "-1 (automatic), 0, 1"), false, nullptr},
+  {"batch_ray", &EngineOptions::batch_ray, opt_bool(), false, nullptr},
+  {"batch_ray_seg", &EngineOptions::batch_ray_seg, opt_one_of(bits(1, 1) | bits(4, 4) | bits(8, 8) | bits(16, 16), "1, 4, 8 or 16 lanes per ray"), false, nullptr},
+  {"batch_ray_lds", &EngineOptions::batch_ray_lds, opt_bool(), false, nullptr},
+  {"batch_ray_parts", &EngineOptions::batch_ray_parts, opt_range(0, 64, "0 (automatic) .. 64"), false, nullptr},
+  {"batch_ray_words", &EngineOptions::batch_ray_words, opt_range(0, kAnyCount, ">= 0"), false, nullptr},
+  // the raycasting stage.  (Its options are read when a scan's stage is LAUNCHED; under ray_hold the previous scan's stage
+  // may still be pending: the join every option starts with sends it off first, so that a switch never lands in the scan
+  // before it — results are the same either way, A/B timings are attributed to the right scan)
+  {"voxel_small", &EngineOptions::voxel_small, opt_bool(), false, nullptr},
+  {"voxel_small_max", &EngineOptions::voxel_small_max, opt_range(1, 1 << 20, "1 .. 2^20 points"), false, nullptr},
+  {"voxel_any_order", &EngineOptions::voxel_any_order, opt_range(0, 1, "0 (stable), 1 (std::sort)"), true, nullptr},
+  {"ray_hold", &EngineOptions::ray_hold, opt_bool(), false, nullptr},
+  {"ray_large_min", &EngineOptions::ray_large_min, opt_at_least(1), false, nullptr},
+  {"ray_wedge", &EngineOptions::ray_wedge, opt_bool(), false, nullptr},
+  {"ray_wedge_parts", &EngineOptions::ray_wedge_parts, opt_range(0, 16, "0 .. 16"), false, nullptr},
+  {"ray_overlap", &EngineOptions::ray_overlap, opt_range(-1, 1, "-1 (automatic), 0, 1"), true, nullptr},
+  // measurement only
+  {"dbg_no_atomics", &EngineOptions::dbg_no_atomics, opt_raw(), false, nullptr},
+  {"dbg_upd", &EngineOptions::dbg_upd, opt_raw(), false, nullptr},
+  {"dbg_batch", &EngineOptions::dbg_batch, opt_raw(), false, nullptr},
+  {"dbg_ray", &EngineOptions::dbg_ray, opt_raw(), false, nullptr},
+  {"dbg_post", &EngineOptions::dbg_post, opt_raw(), false, nullptr},
+  {"dbg_timeline", nullptr, opt_raw(), true, opt_dbg_timeline},
+};
+
+/* tuning knobs of the A/B measurements (not part of the reference surface): include/fdm_engine.h lists them */
 int fdm_engine_set_option(fdm_engine* e, const char* key, int value) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !key) return fail(FDM_ERR_INVALID, "null argument");
-  if (std::strcmp(key, "wave_merge") == 0) {
-    e->wave_merge = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "bin_table") == 0) {
-    e->bin_table = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "overlap") == 0) {
-    e->overlap = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch") == 0) {  // fdm_engine_integrate_device_batch: group small scans into batch launches
-    e->batch = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "voxel_small") == 0) {  // 0: every scan through the library sort
-    e->voxel_small = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "voxel_small_max") == 0) {
-    if (value < 1 || value > (1 << 20)) return fail(FDM_ERR_INVALID, "voxel_small_max: 1 .. 2^20 points");
-    e->voxel_small_max = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dbg_batch") == 0) {
-    e->dbg_batch = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_walk") == 0) {
-    if (value < -1 || value > 1) return fail(FDM_ERR_INVALID, "batch_walk: -1 (automatic), 0, 1");
-    e->batch_walk = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_crop") == 0) {
-    e->batch_crop = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_ray") == 0) {  // 0: scans of an engine with raycasting on leave one by one
-    e->batch_ray = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_ray_lds") == 0) {
-    e->batch_ray_lds = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_ray_words") == 0) {
-    if (value < 0) return fail(FDM_ERR_INVALID, "batch_ray_words: >= 0");
-    e->batch_ray_words = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_ray_parts") == 0) {
-    if (value < 0 || value > 64) return fail(FDM_ERR_INVALID, "batch_ray_parts: 0 (automatic) .. 64");
-    e->batch_ray_parts = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_ray_seg") == 0) {
-    if (value != 1 && value != 4 && value != 8 && value != 16) return fail(FDM_ERR_INVALID, "batch_ray_seg: 1, 4, 8 or 16 lanes per ray");
-    e->batch_ray_seg = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_fuse") == 0) {
-    e->batch_fuse = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "batch_max") == 0) {
-    if (value != 0 && (value < 2 || value > kMaxBatch)) return fail(FDM_ERR_INVALID, "batch_max: 0 (automatic) or 2 .. 32 scans per launch");
-    e->batch_max = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "bin_delay") == 0 || std::strcmp(key, "bin_delay_blocks") == 0) {
-    if (value < 0 || value > 65535) return fail(FDM_ERR_INVALID, "bin_delay: 0 .. 65535");
-    if (key[9] == '_') e->bin_delay_blocks = value; else e->bin_delay = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "bin_stagger") == 0) {
-    if (value < 0 || value > 64) return fail(FDM_ERR_INVALID, "bin_stagger: 0 .. 64");
-    e->bin_stagger = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "move_clear_basic") == 0) {  // which layers GridMap::move()'s strips clear (see fdm_engine::move_clear_basic)
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    e->move_clear_basic = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "cnt_shift") == 0) {
-    if (value < 0 || value > 5) return fail(FDM_ERR_INVALID, "cnt_shift: 0 .. 5");
-    if (e->pool[0].cnt) return fail(FDM_ERR_INVALID, "cnt_shift: the record pools exist already");
-    e->cnt_shift = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "tiled_lds_pad") == 0) {
-    if (value < -1 || value > 120 * 1024) return fail(FDM_ERR_INVALID, "tiled_lds_pad: -1 (automatic) or 0 .. 122880 bytes");
-    e->tiled_lds_pad = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "upd_prio") == 0) {
-    e->upd_prio = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "upd_blocks") == 0 || std::strcmp(key, "upd_blocks_alone") == 0) {  // update blocks of a large-scan launch
-    if (value < 1 || value > 65535) return fail(FDM_ERR_INVALID, "upd_blocks: 1 .. 65535");
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (key[10] == '_') e->upd_blocks_alone = value; else e->upd_blocks = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "zero_copy") == 0) {
-    if (value < 0) return fail(FDM_ERR_INVALID, "zero_copy: a point count (0 = off)");
-    e->zero_copy = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dbg_timeline") == 0) {  // measurement only: block start / end ticks of the fused tiled launches
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->d_timeline) { (void)hipFree(e->d_timeline); e->d_timeline = nullptr; }
-    e->timeline_cap = 0;
-    if (value > 0) {
-      e->timeline_cap = 1u << 16;
-      HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_timeline), size_t(e->timeline_cap) * 16));
-      HIPCK(hipMemset(e->d_timeline, 0, size_t(e->timeline_cap) * 16));
+  for (const OptionRow& o : kOptions) {
+    if (std::strcmp(key, o.name) != 0) continue;
+    const OptRule& r = o.rule;
+    bool ok = true;
+    switch (r.kind) {
+      case OptRule::kBool: value = value != 0; break;
+      case OptRule::kRaw: break;
+      case OptRule::kAtLeast: value = int(std::max<long long>(value, r.a)); break;
+      case OptRule::kRange: ok = value >= r.a && value <= r.b; break;
+      case OptRule::kOneOf: ok = value >= 0 && value < 64 && ((r.a >> value) & 1); break;
     }
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "sync_spin_us") == 0) {
-    e->sync_spin_us = value < 0 ? 0 : value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dbg_post") == 0) {
-    e->dbg_post = value;
-    return FDM_OK;
-  }
-  // (the ray options are read when a scan's raycasting stage is LAUNCHED; under ray_hold the previous scan's stage may
-  // still be pending: it leaves first, so that a switch never lands in the scan before it — results are the same either
-  // way, A/B timings are attributed to the right scan: ADVICE r05)
-  if (std::strcmp(key, "ray_large_min") == 0) {
-    if (int rc = join_streams(e)) return rc;
-    e->ray_large_min = value < 1 ? 1 : value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "ray_hold") == 0) {
-    if (int rc = join_streams(e)) return rc;
-    e->ray_hold = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "ray_wedge") == 0) {
-    if (int rc = join_streams(e)) return rc;
-    e->ray_wedge = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "voxel_any_order") == 0) {  // which point represents a voxel (fdm_introsort.hpp)
-    if (value < 0 || value > 1) return fail(FDM_ERR_INVALID, "voxel_any_order: 0 (stable), 1 (std::sort)");
-    if (int rc = sync_all(e)) return rc;
-    e->voxel_any_order = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "ray_overlap") == 0) {  // two raycasting stages of large scans in flight (fdm_engine_ray.inl)
-    if (value < -1 || value > 1) return fail(FDM_ERR_INVALID, "ray_overlap: -1 (automatic), 0, 1");
-    if (int rc = sync_all(e)) return rc;
-    e->ray_overlap = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "ray_wedge_parts") == 0) {  // workgroups per sector of k_ray_wedge (0 = by the scan's size)
-    if (value < 0 || value > 16) return fail(FDM_ERR_INVALID, "ray_wedge_parts: 0 .. 16");
-    if (int rc = join_streams(e)) return rc;
-    e->ray_wedge_parts = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dbg_ray") == 0) {
-    if (int rc = join_streams(e)) return rc;
-    e->dbg_ray = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "tiled") == 0) {  // large scans through per-tile record pools (1, default) or the per-cell scratch (0)
-    e->tiled = value != 0;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "borrow_inputs") == 0) {  // 1: device arrays of enqueue-only scans stay untouched by the caller
-    e->borrow_inputs = value != 0;              //    until the NEXT-BUT-ONE scan is enqueued (or a flush): no staging copy
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "tiled_min") == 0) {
-    if (value < 0) return fail(FDM_ERR_INVALID, "tiled_min: a point count");
-    e->tiled_min = unsigned(value);
-    e->tiled_forced = true;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "bin_variant") == 0) {
-    if (value != 0 && value != 1 && value != 4) return fail(FDM_ERR_INVALID, "bin_variant must be 0, 1 or 4");
-    e->bin_variant = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "records") == 0) {  // cell-record layout (1, default) or one array per layer (0)
-    e->use_records = value != 0;
-    if (e->estimator_ready) return activate_records(e, e->cfg.estimation_type == 1 ? 1 : 0);
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dense") == 0) {  // force stamp-gated (0) or dense (1) update sweeps
-    e->S.dense = value != 0;
-    e->obst_dense_pending = true;  // stamps were not maintained while dense
-    e->obst_owe_armed = false;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dbg_upd") == 0) {
-    e->dbg_upd = value;
-    return FDM_OK;
-  }
-  if (std::strcmp(key, "dbg_no_atomics") == 0) {  // measurement only: results are wrong when set
-    e->dbg_no_atomics = value;
+    if (!ok) return fail(FDM_ERR_INVALID, std::string(o.name) + ": " + r.accepts);
+    if (o.sync) if (int rc = sync_all(e)) return rc;
+    if (o.hook) if (int rc = o.hook(e, value)) return rc;
+    if (o.field) e->opt.*o.field = value;
     return FDM_OK;
   }
   return fail(FDM_ERR_INVALID, std::string("unknown option ") + key);

@@ -1,5 +1,5 @@
 // fdm_engine_post.inl — host side of the stencil post-processing stages (kernels: fdm_post.hpp).
-// Part of fdm_engine_post.hip (one of the library's three translation units, fdm_engine_host.hpp).
+// Part of fdm_engine_post.hip (one of the library's five translation units, fdm_engine_host.hpp).
 
 extern "C" {
 
@@ -80,7 +80,7 @@ int ensure_tmp2(fdm_engine* e) {
 }  // namespace
 
 int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid, int inplace) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   HIPCK(hipSetDevice(e->device));
   int rc;
@@ -108,7 +108,7 @@ int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid
   }
   bool in_layer = start_in_layer;
   for (int it = 0; it < iters; ++it) {
-    if (e->dbg_post & 4)
+    if (e->opt.dbg_post & 4)
       hipLaunchKernelGGL(k_inpaint_pass, dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
                          in_layer ? A : B, in_layer ? As : 1, in_layer ? B : A, in_layer ? 1 : As, min_valid,
                          unsigned(e->ncell));
@@ -122,7 +122,7 @@ int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid
 }
 
 int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int kernel_size, int min_valid) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !layer) return fail(FDM_ERR_INVALID, "null argument");
   // (any kernel size the reference accepts: region(Size(k, k)) spans dr, dc in [-k/2, k/2] — for an even k that is the
   // (k + 1)-wide box; a window beyond kMaxRegion cells takes the pooled kernel)
@@ -135,7 +135,7 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
   if (!l || l->pending) return FDM_OK;  // spatial_smoothing.hpp:42
   if ((rc = ensure_tmp(e))) return rc;
   if ((rc = copy_strided(e, e->d_tmp, 1, lptr(e, *l), lstride(e, *l)))) return rc;  // the double buffer
-  if (kernel_size == 3 && !(e->dbg_post & 4))
+  if (kernel_size == 3 && !(e->opt.dbg_post & 4))
     hipLaunchKernelGGL(k_median3_tiled, dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), min_valid);
   else if (kernel_size == 3)
@@ -145,7 +145,7 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
     hipLaunchKernelGGL(k_median, dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), kernel_size, min_valid,
                        unsigned(e->ncell));
-  else if (median_sel_lds_bytes(kernel_size) <= 160u * 1024u && !(e->dbg_post & 8)) {
+  else if (median_sel_lds_bytes(kernel_size) <= 160u * 1024u && !(e->opt.dbg_post & 8)) {
     // selection by bisection on an LDS tile (fdm_post.hpp k_median_sel): every window up to ~175 x 175
     const unsigned lds = median_sel_lds_bytes(kernel_size);
     if ((rc = allow_lds(k_median_sel, lds))) return rc;
@@ -164,7 +164,7 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
 }
 
 int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* cfg) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !cfg) return fail(FDM_ERR_INVALID, "null argument");
   if (!cfg->enabled) return FDM_OK;
   HIPCK(hipSetDevice(e->device));
@@ -201,7 +201,7 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
   int halo = 0;
   for (const RegionEntry& r : reg) halo = std::max(halo, std::max(std::abs(r.dr), std::abs(r.dc)));
   const auto q_ok = [](float q) { return q >= 1e-6f && q <= 1.0f; };  // (k_fusion_f64_tiled's walk: a positive target within the total)
-  if (reg.size() <= 29 && halo <= kFusHaloMax && !(e->dbg_ray & 1024) && !(e->dbg_post & (2 | 32)) && q_ok(F.q_lower) &&
+  if (reg.size() <= 29 && halo <= kFusHaloMax && !(e->opt.dbg_ray & 1024) && !(e->opt.dbg_post & (2 | 32)) && q_ok(F.q_lower) &&
       q_ok(F.q_upper)) {  // (a disc of a radius has 1, 5, 9, 13, 21, 25, 29, 37 .. cells: nothing between 29 and 32)
     // samples as doubles sorted by v_min_f64 / v_max_f64 (the default radius: 29 cells), neighbourhood staged in LDS
     const unsigned tblocks = unsigned((e->G.s_rows + kFusTileR - 1) / kFusTileR) *
@@ -213,7 +213,7 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
     };
     // one instantiation per disc size there is below 30 cells (the sorting network shrinks with it: 171 exchanges for 29
     // samples, 19 for the 9 of the shipped 0.15 m on a 0.1 m map); dbg_post 128: the 29-slot kernel with branches
-    const size_t nreg = (e->dbg_post & 128) ? 0 : reg.size();
+    const size_t nreg = (e->opt.dbg_post & 128) ? 0 : reg.size();
     if (nreg == 29) launch_f64(k_fusion_f64_tiled<29, true>);
     else if (nreg == 25) launch_f64(k_fusion_f64_tiled<25, true>);
     else if (nreg == 21) launch_f64(k_fusion_f64_tiled<21, true>);
@@ -221,18 +221,18 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
     else if (nreg == 9) launch_f64(k_fusion_f64_tiled<9, true>);
     else if (nreg == 5) launch_f64(k_fusion_f64_tiled<5, true>);
     else launch_f64(k_fusion_f64_tiled<29, false>);
-  } else if (reg.size() <= 32 && halo <= kFusHaloMax && !(e->dbg_ray & 1024) && !(e->dbg_post & 2)) {
+  } else if (reg.size() <= 32 && halo <= kFusHaloMax && !(e->opt.dbg_ray & 1024) && !(e->opt.dbg_post & 2)) {
     // samples as 64-bit integers sorted in registers, neighbourhood staged in LDS (round 2; any quantile)
     const unsigned tblocks = unsigned((e->G.s_rows + kFusTileR - 1) / kFusTileR) *
                              unsigned((e->G.s_cols + kFusTileC - 1) / kFusTileC);
     hipLaunchKernelGGL(k_fusion_net32_tiled, dim3(tblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, halo, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo));
-  } else if (reg.size() <= 32 && !(e->dbg_ray & 1024)) {  // the same from L2
+  } else if (reg.size() <= 32 && !(e->opt.dbg_ray & 1024)) {  // the same from L2
     hipLaunchKernelGGL(k_fusion_net32, dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
-  } else if (int(reg.size()) <= kFusionWaveMax && !(e->dbg_post & 16)) {  // one wavefront per cell, the samples sorted in LDS
+  } else if (int(reg.size()) <= kFusionWaveMax && !(e->opt.dbg_post & 16)) {  // one wavefront per cell, the samples sorted in LDS
     unsigned n_pad = 64u;
     while (n_pad < reg.size()) n_pad <<= 1;
     const unsigned lds = fusion_wave_lds_bytes(n_pad);
@@ -269,7 +269,7 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
 }
 
 int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_valid, float lo_pct, float hi_pct) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   HIPCK(hipSetDevice(e->device));
   int rc;
@@ -330,11 +330,11 @@ int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_val
   int elev_s = lstride(e, *elev);
   // (the LDS-tiled kernel stages its tile straight from the records: every cell is fetched ~3.4 times, from the L2, behind
   //  other blocks' arithmetic — the copy was 17 of the call's 127 us at configs[3]; dbg_post 256: copy first, as before)
-  const bool tiled_ok = pct_ok && need_lo <= 16 && need_hi <= 16 && !tab.empty() && !(e->dbg_post & 1);
+  const bool tiled_ok = pct_ok && need_lo <= 16 && need_hi <= 16 && !tab.empty() && !(e->opt.dbg_post & 1);
   // (the tiled kernel reads its own table only: the plain region — which the fusion stage of the same publish cycle keeps
   //  on the device with its weights — is left alone, and neither stage uploads anything from the second cycle on)
   if (!tiled_ok && (rc = upload_region(e, reg))) return rc;
-  if (elev_s != 1 && (!tiled_ok || (e->dbg_post & 256))) {
+  if (elev_s != 1 && (!tiled_ok || (e->opt.dbg_post & 256))) {
     if ((rc = ensure_tmp(e))) return rc;
     if ((rc = copy_strided(e, e->d_tmp, 1, elev_p, elev_s))) return rc;
     elev_p = e->d_tmp;
@@ -352,7 +352,7 @@ int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_val
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(kFeatThreads), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                          e->d_feat_tab, F, halo, elev_p, elev_s, O);
     };
-    if (e->dbg_post & 64) {  // (measurement: the two-instruction insertion chains of round 2)
+    if (e->opt.dbg_post & 64) {  // (measurement: the two-instruction insertion chains of round 2)
       if (need_lo <= 8 && need_hi <= 8) launch_tiled(k_features_tiled<8, 8, false>);
       else launch_tiled(k_features_tiled<16, 16, false>);
     } else if (need_lo <= 2 && need_hi <= 3) launch_tiled(k_features_tiled<2, 3>);  // the defaults on a 29-cell disc (0.3 m on a 0.1 m map)
@@ -362,8 +362,8 @@ int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_val
     else launch_tiled(k_features_tiled<16>);
   } else if (pct_ok && need_lo <= 8 && need_hi <= 8) launch_feat(k_features<8>);
   else if (pct_ok && need_lo <= 16 && need_hi <= 16) launch_feat(k_features<16>);
-  else if (reg.size() <= size_t(kMaxRegion) && (e->dbg_post & 8)) launch_feat(k_features<0>);
-  else if (features_sel_lds_bytes(halo, int(reg.size())) <= 160u * 1024u && !(e->dbg_post & 8)) {
+  else if (reg.size() <= size_t(kMaxRegion) && (e->opt.dbg_post & 8)) launch_feat(k_features<0>);
+  else if (features_sel_lds_bytes(halo, int(reg.size())) <= 160u * 1024u && !(e->opt.dbg_post & 8)) {
     // any disc, any percentile pair: order statistics by bisection on an LDS tile (fdm_post.hpp k_features_sel)
     const unsigned lds = features_sel_lds_bytes(halo, int(reg.size()));
     if ((rc = allow_lds(k_features_sel, lds))) return rc;

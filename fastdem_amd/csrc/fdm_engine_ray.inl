@@ -1,6 +1,6 @@
 // fdm_engine_ray.inl — host side of the raycasting stage (kernels: fdm_raycast.hpp): voxel sort, ray
 // queue, resolve; entry points fdm_engine_apply_raycasting*, fdm_engine_voxel_any, fdm_engine_last_ray_ms.
-// The body of fdm_engine_ray.hip (one of the library's three translation units, fdm_engine_host.hpp).
+// The body of fdm_engine_ray.hip (one of the library's five translation units, fdm_engine_host.hpp).
 
 namespace fdmh {
 
@@ -247,7 +247,7 @@ int enqueue_voxel_sort(fdm_engine* e, unsigned n, float voxel_size, int flag_slo
   const int key_bits = 2 * C.bits + C.zbits;
   const bool compact = C.bits > 0 && key_bits <= 31;  // true: the sorted buffer holds uint32 keys
   *key_mode = compact ? 1 : 0;
-  if (e->voxel_any_order) {  // the order std::sort leaves (fdm_introsort.hpp)
+  if (e->opt.voxel_any_order) {  // the order std::sort leaves (fdm_introsort.hpp)
     if (compact) {
       launch_voxel_keys<uint32_t>(e, n, inv, flag_slot, C, dx, dy, dz, reinterpret_cast<uint32_t*>(e->vkeys[0]));
       return enqueue_introsort<uint32_t>(e, n);
@@ -255,7 +255,7 @@ int enqueue_voxel_sort(fdm_engine* e, unsigned n, float voxel_size, int flag_slo
     launch_voxel_keys<unsigned long long>(e, n, inv, flag_slot, C, dx, dy, dz, e->vkeys[0]);
     return enqueue_introsort<unsigned long long>(e, n);
   }
-  if (compact && e->voxel_small && n <= unsigned(e->voxel_small_max)) {
+  if (compact && e->opt.voxel_small && n <= unsigned(e->opt.voxel_small_max)) {
     // small scans: no sort at all (k_vs_*: fdm_raycast.hpp).  vkeys[0] = keys by point | places by point, vs_rec =
     // {key, point, bucket start, bucket size} by position; k_vs_mark runs from enqueue_ray_stage (key_mode 2)
     if (!e->vs_cnt) {
@@ -281,7 +281,7 @@ int enqueue_voxel_sort(fdm_engine* e, unsigned n, float voxel_size, int flag_slo
     V.rec = e->vs_rec;
     V.cap = unsigned(e->vs_rec_cap);
     V.ibits = 1u;
-    V.dbg = (e->dbg_ray >> 8) & 3;
+    V.dbg = (e->opt.dbg_ray >> 8) & 3;
     while ((1u << V.ibits) < n) ++V.ibits;
     const unsigned blocks = (n + 255u) / 256u;
     hipLaunchKernelGGL(k_vs_count, dim3(blocks), dim3(256), 0, e->stream, n, inv, flag_slot, C, V, e->d_state, dx, dy,
@@ -333,7 +333,7 @@ RayParams make_ray_params(fdm_engine* e, const fdm_raycast_config& c, const floa
   Q.slot = slot;
   Q.flag_slot = flag_slot;
   Q.vis_stamp = 3u * unsigned(e->scan_no) + (flag_slot >= 0 ? 3u : 1u);
-  Q.dbg = e->dbg_ray;
+  Q.dbg = e->opt.dbg_ray;
   Q.by_sector = 0;
   Q.ctx = 0;
   Q.pre_slot = -1;
@@ -416,11 +416,11 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
                          e->vkeys[1], e->vidx[1], e->vsel);
   }
   // large scans: queue bucketed by (wedge, length class) before the walk (see k_ray_compact)
-  const bool large = Q.n >= unsigned(e->ray_large_min);  // one lane per ray, queue bucketed by (wedge, length)
-  const bool sort_queue = large && !(e->dbg_ray & 2048);
+  const bool large = Q.n >= unsigned(e->opt.ray_large_min);  // one lane per ray, queue bucketed by (wedge, length)
+  const bool sort_queue = large && !(e->opt.dbg_ray & 2048);
   // large scans walk with an angular sector's minimum-height image in LDS (fdm_raywedge.hpp): the queue is ordered
   // (sector, length class) for it
-  const bool wedge = sort_queue && e->ray_wedge != 0;
+  const bool wedge = sort_queue && e->opt.ray_wedge != 0;
   if (wedge) Q.by_sector = 1;
   uint32_t* ray_key = sort_queue ? reinterpret_cast<uint32_t*>(e->vkeys[0]) : nullptr;       // vkeys hold 2 x vcap uint32
   uint32_t* ray_rank = sort_queue ? reinterpret_cast<uint32_t*>(e->vkeys[0]) + e->vcap : nullptr;
@@ -486,7 +486,7 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
     const unsigned sectors = kRaySectors;
     // (a camera's 60-degree field of view puts its rays into 43 of the 256 sectors; four workgroups per sector for
     // scans of that size measured 22 us against 18: every one initialises and flushes a window of its own)
-    const unsigned parts = e->ray_wedge_parts > 0 ? unsigned(e->ray_wedge_parts)
+    const unsigned parts = e->opt.ray_wedge_parts > 0 ? unsigned(e->opt.ray_wedge_parts)
                                                   : std::max(1u, std::min(8u, Q.n / (sectors * 8u * kRwThreads)));
     const uint32_t* bin_start = e->ray_bins + kRayBins;
     auto launch_wedge = [&](auto kern) -> int {
@@ -495,7 +495,7 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
                          ray_list, bin_start, e->rc_min, H, parts);
       return FDM_OK;
     };
-    const bool fwin = !(e->dbg_ray & (1 << 20));  // (dbg_ray 1048576, measurement only: the integer window of round 5)
+    const bool fwin = !(e->opt.dbg_ray & (1 << 20));  // (dbg_ray 1048576, measurement only: the integer window of round 5)
     if (tiled) rc = fwin ? launch_wedge(k_ray_wedge<true, true>) : launch_wedge(k_ray_wedge<true, false>);
     else rc = fwin ? launch_wedge(k_ray_wedge<false, true>) : launch_wedge(k_ray_wedge<false, false>);
     if (rc) return rc;
@@ -525,9 +525,9 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
 // update, ahead of the next one, on the main stream, which waits for the early part there.
 int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const ScanParams& P) {
   u.ray_pre = 0;
-  const bool want = e->ray_overlap > 0 || (e->ray_overlap < 0 && (e->sync_call || u.RQ.n >= 1000000u));
-  if (!want || !u.ray || u.RQ.n < unsigned(e->ray_large_min) || e->profile || !e->ray_wedge) return FDM_OK;
-  if (e->voxel_small && !e->voxel_any_order && u.RQ.n <= unsigned(e->voxel_small_max))
+  const bool want = e->opt.ray_overlap > 0 || (e->opt.ray_overlap < 0 && (e->sync_call || u.RQ.n >= 1000000u));
+  if (!want || !u.ray || u.RQ.n < unsigned(e->opt.ray_large_min) || e->profile || !e->opt.ray_wedge) return FDM_OK;
+  if (e->opt.voxel_small && !e->opt.voxel_any_order && u.RQ.n <= unsigned(e->opt.voxel_small_max))
     return FDM_OK;  // (the sort-free filter keeps state of its own)
   if (!find_layer(e, "elevation")) return FDM_OK;
   int rc;
@@ -536,9 +536,9 @@ int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const Sca
   bool fresh = false;
   {  // allocations (they may drain the streams and, with them, flush this very scan: then the stage has run) before anything is enqueued
     RayBankScope bank(e, ctx);
-    fresh = e->rc_cnt == nullptr || u.RQ.n > e->vcap || (e->voxel_any_order && u.RQ.n > e->is_cap);
+    fresh = e->rc_cnt == nullptr || u.RQ.n > e->vcap || (e->opt.voxel_any_order && u.RQ.n > e->is_cap);
     if ((rc = ensure_ray_cells(e)) || (rc = ensure_voxel_buffers(e, u.RQ.n))) return rc;
-    if (e->voxel_any_order && (rc = ensure_introsort_buffers(e, u.RQ.n))) return rc;
+    if (e->opt.voxel_any_order && (rc = ensure_introsort_buffers(e, u.RQ.n))) return rc;
   }
   if (!u.ray || !e->chain) return FDM_OK;
   hipStream_t rs = e->ray_stream[ctx];
@@ -614,7 +614,7 @@ extern "C" {
 int fdm_engine_apply_raycasting_device(fdm_engine* e, uint64_t n, const float* dx, const float* dy,
                                        const float* dz, const float origin[3],
                                        const fdm_raycast_config* rcfg) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !origin) return fail(FDM_ERR_INVALID, "null argument");
   const fdm_raycast_config c = rcfg ? *rcfg : ray_config_of(e->cfg);
   if (!c.enabled || n == 0) return FDM_OK;  // raycasting.cpp:207-209
@@ -631,7 +631,7 @@ int fdm_engine_apply_raycasting_device(fdm_engine* e, uint64_t n, const float* d
 
 int fdm_engine_apply_raycasting(fdm_engine* e, uint64_t n, const float* x, const float* y,
                                 const float* z, const float origin[3], const fdm_raycast_config* rcfg) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !origin) return fail(FDM_ERR_INVALID, "null argument");
   if (!(rcfg ? rcfg->enabled : e->cfg.raycast_enabled) || n == 0) return FDM_OK;
   if (!x || !y || !z) return fail(FDM_ERR_INVALID, "null xyz");
@@ -647,7 +647,7 @@ int fdm_engine_apply_raycasting(fdm_engine* e, uint64_t n, const float* x, const
 
 int fdm_engine_voxel_any(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
                          float voxel_size, uint32_t* out_idx, uint64_t* n_out) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !n_out) return fail(FDM_ERR_INVALID, "null argument");
   *n_out = 0;
   if (!voxel_size_ok(voxel_size)) return fail(FDM_ERR_INVALID, "voxel_size must be in [0.001, 100]");
@@ -675,7 +675,7 @@ int fdm_engine_voxel_any(fdm_engine* e, uint64_t n, const float* x, const float*
 }
 
 int fdm_engine_last_ray_ms(fdm_engine* e, float* ms) {
-  if (e) { if (int rc_join = join_streams(e)) { (void)rc_join; return rc_join; } }
+  if (int rc = join_streams(e)) return rc;
   if (!e || !ms) return fail(FDM_ERR_INVALID, "null argument");
   if (!e->profile) return fail(FDM_ERR_INVALID, "profiling is off");
   *ms = 0.f;

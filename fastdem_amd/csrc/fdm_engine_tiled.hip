@@ -11,17 +11,17 @@ TileWork tile_work(const fdm_engine* e, unsigned blocks) {
   TileWork K{};
   K.W = blocks * 4u;
   K.T = (e->TG.n_tiles + K.W - 1u) / K.W;
-  K.prio = e->upd_prio ? 1u : 0u;
-  K.stagger = unsigned(e->bin_stagger);
-  K.delay = unsigned(e->bin_delay);
-  K.delay_blocks = unsigned(e->bin_delay_blocks);
+  K.prio = e->opt.upd_prio ? 1u : 0u;
+  K.stagger = unsigned(e->opt.bin_stagger);
+  K.delay = unsigned(e->opt.bin_delay);
+  K.delay_blocks = unsigned(e->opt.bin_delay_blocks);
   return K;
 }
 // update blocks of a launch: alone, enough to fill the chip; beside a bin half (fused launch), few — the bin blocks are
 // the arithmetic, the update wavefronts are chains of round trips that run beside them (option "upd_blocks")
 unsigned update_blocks(const fdm_engine* e, bool fused) {
   const unsigned most = (e->TG.n_tiles + 3u) / 4u;  // one tile per wavefront
-  const unsigned want = fused ? unsigned(e->upd_blocks) : unsigned(e->upd_blocks_alone);
+  const unsigned want = fused ? unsigned(e->opt.upd_blocks) : unsigned(e->opt.upd_blocks_alone);
   return std::max(1u, std::min(most, want));
 }
 
@@ -53,10 +53,9 @@ int ensure_tile_aux(fdm_engine* e) {
 }
 
 // The record pools of the tiled pipeline: `records` per pool, `blocks` chunk slots per tile.
-int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks, bool has_int, bool has_col) {
+int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks) {
   if (int rc_aux = ensure_tile_aux(e)) return rc_aux;
   const bool grow_rec = records > e->pool_cap;
-  (void)has_int; (void)has_col;
   const bool grow_desc = blocks > e->desc_stride;
   if (!grow_rec && !grow_desc) return FDM_OK;
   if (int rc_sync = sync_all(e)) return rc_sync;  // (every chunk list is consumed: the tile counters are all zero)
@@ -79,7 +78,7 @@ int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks, bool has_in
     }
     if (grow_desc && (rc = re(q.desc, size_t(e->TG.n_tiles) * e->desc_stride * 8))) return rc;  // (only entries below a tile's counter are ever read)
     if (!q.cnt) {
-      q.cnt_shift = unsigned(e->cnt_shift);
+      q.cnt_shift = unsigned(e->opt.cnt_shift);
       HIPCK(hipMalloc(reinterpret_cast<void**>(&q.cnt), (size_t(e->TG.n_tiles) << q.cnt_shift) * sizeof(unsigned)));
       HIPCK(hipMemsetAsync(q.cnt, 0, (size_t(e->TG.n_tiles) << q.cnt_shift) * sizeof(unsigned), e->stream));
     }
@@ -90,7 +89,7 @@ int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks, bool has_in
 
 // dynamic LDS of a large-scan launch that needs `lds` bytes: padded so that six blocks share a CU's 160 KB, not seven
 unsigned tiled_lds_padded(const fdm_engine* e, unsigned lds) {
-  if (e->tiled_lds_pad >= 0) return lds + unsigned(e->tiled_lds_pad);
+  if (e->opt.tiled_lds_pad >= 0) return lds + unsigned(e->opt.tiled_lds_pad);
   constexpr unsigned kSeven = 163840u / 7u;  // at most this much: seven blocks fit
   return lds <= kSeven ? kSeven + 16u : lds;
 }
@@ -103,13 +102,8 @@ int launch_tbin(fdm_engine* e, const ScanParams& P, const ScanInputs& in, const 
     hipLaunchKernelGGL(kern, dim3(bin_blocks), dim3(bv.threads), lds, e->stream, P, e->G, e->TG, e->d_state, in, e->S,
                        Q, ids);
   };
-#define FDM_TBIN(LN)                                               \
-  if (bv.has_int && bv.has_col) go(k_tbin<true, true, 256, LN>);    \
-  else if (bv.has_int) go(k_tbin<true, false, 256, LN>);            \
-  else if (bv.has_col) go(k_tbin<false, true, 256, LN>);            \
-  else go(k_tbin<false, false, 256, LN>);
-  if (bv.lean == 1) { FDM_TBIN(true) } else { FDM_TBIN(false) }
-#undef FDM_TBIN
+  with_constants([&](auto hi, auto hc, auto lean) { go(k_tbin<hi(), hc(), 256, lean()>); }, bv.has_int, bv.has_col,
+                 bv.lean == 1);
   if (rc) return rc;
   HIPCK(hipGetLastError());
   return FDM_OK;
@@ -129,10 +123,7 @@ int launch_tiled_update_alone(fdm_engine* e, const fdm_engine::PendingUpdate& u)
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, e->stream, u.P, e->G, e->TG, e->d_state, layers,
                            e->d_layer_ptrs, e->n_layer_ptrs, u.Q, u.A, K);
       };
-      if (hi && hc) go(k_tupdate<POLICY, true, true>);
-      else if (hi) go(k_tupdate<POLICY, true, false>);
-      else if (hc) go(k_tupdate<POLICY, false, true>);
-      else go(k_tupdate<POLICY, false, false>);
+      with_constants([&](auto ci, auto cc) { go(k_tupdate<POLICY, ci(), cc()>); }, hi, hc);
     } else {
       return fail(FDM_ERR_INVALID, "internal: tiled update with a per-layer policy");
     }
@@ -165,13 +156,8 @@ int launch_tiled_update_fused(fdm_engine* e, const fdm_engine::PendingUpdate& u,
                              e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs, u.Q, A, K, ub, Pb, Ib, Sb, Qb,
                              ids_b);
         };
-#define FDM_TF(LN)                                                                  \
-        if (bv.has_int && bv.has_col) go(k_tupdate_tbin<POLICY, true, true, 256, LN>);   \
-        else if (bv.has_int) go(k_tupdate_tbin<POLICY, true, false, 256, LN>);           \
-        else if (bv.has_col) go(k_tupdate_tbin<POLICY, false, true, 256, LN>);           \
-        else go(k_tupdate_tbin<POLICY, false, false, 256, LN>);
-        if (bv.lean == 1) { FDM_TF(true) } else { FDM_TF(false) }
-#undef FDM_TF
+        with_constants([&](auto hi, auto hc, auto lean) { go(k_tupdate_tbin<POLICY, hi(), hc(), 256, lean()>); },
+                       bv.has_int, bv.has_col, bv.lean == 1);
         if (rc) return rc;
       } else {
         return fail(FDM_ERR_INVALID, "internal: tiled update with a per-layer policy");
