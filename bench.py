@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""bench.py — M points/s integrated into the ElevationMap on MI355X, with roofline + CPU baseline.
+"""bench.py — M points/s integrated into the ElevationMap on MI355X; with --full also roofline + CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--full]
 
 A "step" is ONE pass of the hot path over one batch of synthetic input whose SoA channels are already
 resident in HBM (through the C ABI; enqueue-only, no host sync inside the timed region).  For the small-scan
@@ -14,12 +14,16 @@ maps do not shard so every rank runs an independent replica (we
 data-path collective); `--workload c5` instead tiles ONE global map across the ranks with an
 RCCL halo exchange per scan (fastdem_amd/tiling.py).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step`) with the configuration it was measured on.  Everything else the benchmark measures or checks
+takes runs of its own and rides behind --full (the --no-* switches choose among these legs).  Extra objects of --full:
   roofline     — dominant kernel: algorithmic bytes per launch / HIP-event duration vs 8 TB/s
   cpu_baseline — the CPU oracle ("port" of the reference path, 1 thread) timed on this host
   kernels      — both kernels' event-timed durations and algorithmic bytes
   large        — the same roofline measurement on configs[3] (2 M-pt scan), where an HBM
                  fraction is physically meaningful (a 30 K-pt scan is launch-latency bound)
+  ... and latency_path, cache_resident, raycasting_on, the PCIe-inclusive host legs and, with N > 1 on a LOCAL-map
+  workload, global_map (BASELINE configs[4] for the same N)
 """
 import argparse
 import ctypes as C
@@ -58,6 +62,11 @@ def parse():
                     help="scans one step hands to the hot path: 0 = 16 for the workloads the batch pipeline takes (c2, c3: a "
                          "step is ONE launch over one batch of 16 scans), 1 for the large-scan workloads (one launch per scan)")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: per-kernel "
+                         "and roofline figures, the cache-resident and raycasting legs, the PCIe-inclusive host entry points, "
+                         "the 2 M-point workload, the CPU baseline with its parity gate, and with N > 1 the global-map leg "
+                         "(--no-host-legs, --no-large, --no-cpu-baseline, --no-global-map leave single legs out)")
     ap.add_argument("--native-routed", type=int, default=1, help="c5 routed: 1 = the step as one C call (libfdm_halo), 2 = that call pipelined over consecutive scans (one rank), 0 = the Python loop")
     ap.add_argument("--order", default="azimuth", choices=["azimuth", "ring"])
     ap.add_argument("--scans", type=int, default=0,
@@ -690,8 +699,9 @@ def main():
                     dev.append(u_)
             return float(np.median(wall)), pts_, float(np.median(dev)), bs_, k, wall
 
-        for kk in range(args.profile_steps + 8):
-            res.pose(n_warm + n_timed + kk)
+        if args.full:
+            for kk in range(args.profile_steps + 8):
+                res.pose(n_warm + n_timed + kk)
         dt, pts, timed_launch_us, batch_scans, k, wall_reps = timed_region(res, 0, args.dump_outputs if rank == 0 else None)
         if world > 1:  # the MAX over ranks of every repeat, then the median
             dist.barrier()
@@ -727,7 +737,7 @@ def main():
                        "step": (f"one launch of the batch pipeline over {sps} scans (fdm_engine_integrate_device_batch)"
                                 if sps > 1 else "one scan")},
         }
-        if rank == 0:
+        if rank == 0 and args.full:
             kern, roof = measure_kernels(res, k, args.profile_steps, args.workload, args.overlap)
             if args.overlap and "k_update_bin" in kern and batch_scans == 1:
                 # the timed region is nothing but back-to-back k_update_bin launches, one per scan:
@@ -885,7 +895,7 @@ def main():
                 del big
             if world == 1 and not args.no_cpu_baseline:
                 result["cpu_baseline"] = cpu_baseline(wl)
-    if world > 1 and not routed and not args.no_global_map:
+    if world > 1 and not routed and args.full and not args.no_global_map:
         # LOCAL maps do not shard: `value` above is N independent replicas.  The configuration in which the GPUs of a
         # node share ONE map is BASELINE configs[4]; its line for the same N rides along, so that a 1 / 2 / 4 / 8 sweep
         # of the default command has rows for both.

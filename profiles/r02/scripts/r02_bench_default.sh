@@ -1,10 +1,10 @@
 #!/bin/bash
-mkdir -p gpurun_out
-timeout 900 python bench.py "$@" > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; echo rc=$?
-tail -c 800 gpurun_out/bench_default.err | grep -v amdgpu.ids
+mkdir -p out
+timeout 900 python bench.py --full "$@" > out/bench_default.json 2> out/bench_default.err; echo rc=$?
+tail -c 800 out/bench_default.err | grep -v amdgpu.ids
 python - <<'PY'
 import json
-d=json.loads(open("gpurun_out/bench_default.json").read().strip().splitlines()[-1])
+d=json.loads(open("out/bench_default.json").read().strip().splitlines()[-1])
 print({k:d.get(k) for k in ("value","device_value","ms_per_step","steps")}, d["roofline"]["avg_kernel_us"], d["roofline"]["frac"])
 print({k:v for k,v in d.items() if k.startswith("host_")})
 if "large" in d:

@@ -9,6 +9,6 @@ tag=$1; shift
 i=0
 for SET in "${SETS[@]}"; do
   i=$((i+1))
-  rocprofv3 --pmc $SET --output-format csv -d $O/pmc_$tag/p$i -o p -- python3 $R/bench.py --workload c4 --no-host-legs --no-large --no-cpu-baseline --steps 60 --warmup 10 --profile-steps 6 "$@" > $O/pmc_$tag.p$i.log 2>&1 || tail -2 $O/pmc_$tag.p$i.log
+  rocprofv3 --pmc $SET --output-format csv -d $O/pmc_$tag/p$i -o p -- python3 $R/bench.py --full --workload c4 --no-host-legs --no-large --no-cpu-baseline --steps 60 --warmup 10 --profile-steps 6 "$@" > $O/pmc_$tag.p$i.log 2>&1 || tail -2 $O/pmc_$tag.p$i.log
 done
 python3 $R/scripts/pmc_traffic.py $tag $O/pmc_$tag $O/pmc_traffic_ab.json

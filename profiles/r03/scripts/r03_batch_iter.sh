@@ -7,8 +7,8 @@ cd $R
 timeout 900 python -m pytest tests/test_batch_gpu.py -m gpu -x -q 2>&1 | tail -15
 python scripts/batch_probe.py "$@" | tee $O/probe.json
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -o c2 -- python3 $R/bench.py --no-host-legs --no-cpu-baseline --no-large --steps 4000 --warmup 400 > $O/bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_nofuse -o c2 -- python3 $R/bench.py --no-host-legs --no-cpu-baseline --no-large --steps 4000 --warmup 400 --set batch_fuse=0 > $O/bench_nofuse.json 2> $O/bench_nofuse.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -o c2 -- python3 $R/bench.py --full --no-host-legs --no-cpu-baseline --no-large --steps 4000 --warmup 400 > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_nofuse -o c2 -- python3 $R/bench.py --full --no-host-legs --no-cpu-baseline --no-large --steps 4000 --warmup 400 --set batch_fuse=0 > $O/bench_nofuse.json 2> $O/bench_nofuse.err
 python3 - $O <<'PY'
 import csv, sys
 for d in ("rocprof", "rocprof_nofuse"):

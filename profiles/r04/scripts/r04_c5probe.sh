@@ -5,7 +5,7 @@ mkdir -p $O
 cd $R
 export FDM_BENCH_TRACE=1
 for i in 1 2 3 4; do
-timeout 300 python3 bench.py --workload c5 --steps 100 --warmup 10 > $O/t_$i.json 2> $O/t_$i.err
+timeout 300 python3 bench.py --full --workload c5 --steps 100 --warmup 10 > $O/t_$i.json 2> $O/t_$i.err
 python3 - $i $O <<'PY'
 import json,sys
 i,O=sys.argv[1],sys.argv[2]

@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r04_final
 mkdir -p $O
 cd $R
-time (python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err)
+time (python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err)
 python3 - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r04_final/bench_steps20.json') if l.startswith('{')][-1])

@@ -5,7 +5,7 @@ mkdir -p $O
 cd $R
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -25 > $O/pytest.txt
 cat $O/pytest.txt
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r04_full/bench_default.json') if l.startswith('{')][-1])

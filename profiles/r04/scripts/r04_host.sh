@@ -4,7 +4,7 @@ O=$R/gpurun_out/r04_host
 mkdir -p $O
 cd $R
 timeout 1200 python -m pytest tests/test_cpp_host_api.py tests/test_batch_gpu.py tests/test_tiling_gpu.py -m gpu -q -x 2>&1 | tail -15
-timeout 900 python bench.py --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
+timeout 900 python bench.py --full --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r04_host/bench_default.json') if l.startswith('{')][-1])

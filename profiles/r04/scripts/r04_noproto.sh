@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_batch_gpu.py tests/test_tbatch_gpu.py -m gpu -q -x 2>&1 | tail -4
 for W in c2 c3; do
-timeout 600 python bench.py --workload $W --no-cpu-baseline --no-host-legs --no-large > $O/bench_$W.json 2>$O/err_$W.txt || tail -3 $O/err_$W.txt
+timeout 600 python bench.py --full --workload $W --no-cpu-baseline --no-host-legs --no-large > $O/bench_$W.json 2>$O/err_$W.txt || tail -3 $O/err_$W.txt
 python - $W <<'PY'
 import json,sys
 w=sys.argv[1]

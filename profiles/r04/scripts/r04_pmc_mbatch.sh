@@ -10,7 +10,7 @@ i=0
 for SET in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_WAIT_INST_LDS SQ_WAVES SQ_BUSY_CYCLES"; do
   for FUSE in 0 1; do
     i=$((i+1))
-    timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --scans 4 --no-host-legs --no-cpu-baseline --no-large --steps 200 --warmup 16 --profile-steps 4 --set batch_fuse=$FUSE > $O/p$i.log 2>&1 || tail -3 $O/p$i.log
+    timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --full --scans 4 --no-host-legs --no-cpu-baseline --no-large --steps 200 --warmup 16 --profile-steps 4 --set batch_fuse=$FUSE > $O/p$i.log 2>&1 || tail -3 $O/p$i.log
   done
 done
 cd $R

@@ -17,9 +17,9 @@ args_of() {
 }
 # (1) kernel-trace stats of the bench commands (no host legs / CPU baseline / large leg: the timed region's kernels only)
 for W in c2 c3 c4 c5; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_$W -o $W -- python3 $R/bench.py --no-host-legs --no-cpu-baseline --no-large $(args_of $W) > $O/rocprof_$W.json 2> $O/rocprof_$W.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_$W -o $W -- python3 $R/bench.py --full --no-host-legs --no-cpu-baseline --no-large $(args_of $W) > $O/rocprof_$W.json 2> $O/rocprof_$W.err
 done
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_c5_routed -o c5r -- python3 $R/bench.py --workload c5 --steps 100 --warmup 10 > $O/rocprof_c5_routed.json 2> $O/rocprof_c5_routed.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_c5_routed -o c5r -- python3 $R/bench.py --full --workload c5 --steps 100 --warmup 10 > $O/rocprof_c5_routed.json 2> $O/rocprof_c5_routed.err
 # (2) traffic counters (request-size counters: exact for every access pattern of this engine, profiles/r02/pmc_calibration.json)
 SETS=("TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "TCC_EA0_ATOMIC_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_REQ_sum")
 for W in c2 c3 c4 c5; do
@@ -28,7 +28,7 @@ for W in c2 c3 c4 c5; do
     i=$((i+1))
     A=$(args_of $W | sed 's/--steps [0-9]* --warmup [0-9]*//')
     ST="--steps 64 --warmup 16 --profile-steps 6"; [ $W = c2 ] && ST="--steps 640 --warmup 64 --profile-steps 6"
-    timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/pmc_$W/p$i -o p -- python3 $R/bench.py --no-host-legs --no-large --no-cpu-baseline $A $ST > $O/pmc_$W.p$i.log 2>&1 || tail -2 $O/pmc_$W.p$i.log
+    timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/pmc_$W/p$i -o p -- python3 $R/bench.py --full --no-host-legs --no-large --no-cpu-baseline $A $ST > $O/pmc_$W.p$i.log 2>&1 || tail -2 $O/pmc_$W.p$i.log
   done
   python3 $R/scripts/pmc_traffic.py $W $O/pmc_$W $O/pmc_traffic.json
 done
@@ -38,8 +38,8 @@ for SET in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_INSTS_FLAT SQ_ACTIVE_INST_LDS" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS_ATOMIC SQ_INSTS_BRANCH SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_WAIT_INST_LDS"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/sq_c2/p$i -o p -- python3 $R/bench.py --no-host-legs --no-cpu-baseline --no-large --steps 640 --warmup 64 --profile-steps 4 > $O/sq_c2.p$i.log 2>&1 || tail -2 $O/sq_c2.p$i.log
-  timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/sq_c4/p$i -o p -- python3 $R/bench.py --workload c4 --no-host-legs --no-cpu-baseline --no-large --steps 64 --warmup 16 --profile-steps 4 > $O/sq_c4.p$i.log 2>&1 || tail -2 $O/sq_c4.p$i.log
+  timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/sq_c2/p$i -o p -- python3 $R/bench.py --full --no-host-legs --no-cpu-baseline --no-large --steps 640 --warmup 64 --profile-steps 4 > $O/sq_c2.p$i.log 2>&1 || tail -2 $O/sq_c2.p$i.log
+  timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/sq_c4/p$i -o p -- python3 $R/bench.py --full --workload c4 --no-host-legs --no-cpu-baseline --no-large --steps 64 --warmup 16 --profile-steps 4 > $O/sq_c4.p$i.log 2>&1 || tail -2 $O/sq_c4.p$i.log
 done
 cd $R
 python3 - $O <<'PY' > $O/pmc_sq.txt
@@ -60,10 +60,10 @@ cat $O/pmc_sq.txt | cut -c1-400
 timeout 200 python3 scripts/timeline_batch.py > $O/timeline_c2_batch.json 2> $O/timeline_c2_batch.err
 timeout 300 python3 scripts/timeline.py c4 > $O/timeline_c4_fused.json 2> $O/timeline_c4_fused.err
 # (5) the default bench line + the other configs' lines, unprofiled
-timeout 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-for W in c3 c4; do timeout 300 python3 bench.py $(args_of $W) --no-large --no-cpu-baseline > $O/bench_$W.json 2> $O/bench_$W.err; done
-timeout 300 python3 bench.py --workload c5 --routed 0 --steps 500 --warmup 50 --no-large --no-cpu-baseline > $O/bench_c5_plain.json 2> $O/bench_c5_plain.err
-timeout 300 python3 bench.py --workload c5 --steps 100 --warmup 10 > $O/bench_c5_routed_1rank.json 2> $O/bench_c5_routed_1rank.err
+timeout 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+for W in c3 c4; do timeout 300 python3 bench.py --full $(args_of $W) --no-large --no-cpu-baseline > $O/bench_$W.json 2> $O/bench_$W.err; done
+timeout 300 python3 bench.py --full --workload c5 --routed 0 --steps 500 --warmup 50 --no-large --no-cpu-baseline > $O/bench_c5_plain.json 2> $O/bench_c5_plain.err
+timeout 300 python3 bench.py --full --workload c5 --steps 100 --warmup 10 > $O/bench_c5_routed_1rank.json 2> $O/bench_c5_routed_1rank.err
 ls $O | head -60
 cat $O/pmc_traffic.json | python3 -c "import json,sys; d=json.load(sys.stdin); print({w: {k: round(v.get('hbm_bytes_per_launch', 0)) for k, v in e.items()} for w, e in d.items()})"
 # (6) raycasting: stage bench per workload (single-scan stage, batch call), kernel stats of the batch call with raycasting

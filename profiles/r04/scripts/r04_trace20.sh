@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r04_trace20
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o t -- python3 $R/bench.py --steps 20 --warmup 5 --no-host-legs --no-large --no-cpu-baseline > $O/run.json 2> $O/run.err
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o t -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-host-legs --no-large --no-cpu-baseline > $O/run.json 2> $O/run.err
 python3 - $O <<'PY'
 import csv,glob,sys,json
 f=glob.glob(sys.argv[1]+'/prof/**/t_kernel_trace.csv', recursive=True)[0]

@@ -9,5 +9,5 @@ timeout 300 scripts/ubench/valu_issue.bin > $O/valu_issue.jsonl 2> $O/valu_issue
 cat $O/valu_issue.jsonl
 timeout 600 python scripts/c4_ab.py "" > $O/c4_ab.json 2> $O/c4_ab.err
 cat $O/c4_ab.json; tail -3 $O/c4_ab.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err
 tail -c 1500 $O/bench_20_5.json

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 while [ $# -ge 2 ]; do
   TAG=$1; ARGS=$2; shift 2
   O=$R/gpurun_out/kt_$TAG; mkdir -p $O
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- python3 $R/bench.py --no-large --no-cpu-baseline --no-host-legs --steps 100 --warmup 10 --profile-steps 5 --workload c4 $ARGS > $O/log.txt 2>&1 || tail -3 $O/log.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- python3 $R/bench.py --full --no-large --no-cpu-baseline --no-host-legs --steps 100 --warmup 10 --profile-steps 5 --workload c4 $ARGS > $O/log.txt 2>&1 || tail -3 $O/log.txt
   python3 - $O $TAG <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):

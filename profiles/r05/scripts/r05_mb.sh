@@ -9,7 +9,7 @@ for N in "$@"; do
 import json, subprocess, sys, os
 from fastdem_amd import capi
 PY
-  timeout 600 python scripts/lib_bench.py $L --no-large --no-cpu-baseline --no-host-legs 2>/dev/null | python3 -c "
+  timeout 600 python scripts/lib_bench.py $L --full --no-large --no-cpu-baseline --no-host-legs 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print({k: d[k] for k in ('value','ms_per_step','repeats')}, d['roofline']['frac'], d['roofline']['avg_kernel_us'])"

@@ -10,7 +10,7 @@ while [ $# -ge 2 ]; do
   for SET in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" \
              "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_BUSY_CYCLES SQ_INSTS_VALU_FMA_F64"; do
     i=$((i+1))
-    rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --overlap 0 --no-large --no-cpu-baseline --no-host-legs --steps 20 --warmup 5 --profile-steps 5 --workload c4 $ARGS > $O/p$i.log 2>&1 || tail -3 $O/p$i.log
+    rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --full --overlap 0 --no-large --no-cpu-baseline --no-host-legs --steps 20 --warmup 5 --profile-steps 5 --workload c4 $ARGS > $O/p$i.log 2>&1 || tail -3 $O/p$i.log
   done
   python3 - $O $TAG <<'PY'
 import collections, csv, glob, sys

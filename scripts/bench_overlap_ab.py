@@ -11,7 +11,7 @@ def init(self, *a, **k):
     orig(self, *a, **k)
     self.eng.set_option("ray_overlap", ov)
 bench.Resident.__init__ = init
-sys.argv = ["bench.py", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline"]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     bench.main()

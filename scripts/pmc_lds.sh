@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for SET in "SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS" "SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVES" "SQ_LDS_IDX_ACTIVE SQ_LDS_UNALIGNED_STALL SQ_LDS_MEM_VIOLATIONS SQ_LDS_ATOMIC_RETURN"; do
   i=$((i+1))
-  rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --workload $W --order $ORDER --overlap 0 --no-large --no-cpu-baseline --steps 20 --warmup 5 --profile-steps 5 > $O/p$i.log 2>&1
+  rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --full --workload $W --order $ORDER --overlap 0 --no-large --no-cpu-baseline --steps 20 --warmup 5 --profile-steps 5 > $O/p$i.log 2>&1
 done
 cd $R
 python3 - $O <<'PY'

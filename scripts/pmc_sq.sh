@@ -12,7 +12,7 @@ for SET in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_MISC SQ_INSTS_FLAT SQ_INSTS_VALU_MFMA_I8 SQ_THREAD_CYCLES_VALU" \
            "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
-  rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --overlap 0 --no-large --no-cpu-baseline --steps 20 --warmup 5 --profile-steps 5 "$@" > $O/p$i.log 2>&1 || tail -3 $O/p$i.log
+  rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --full --overlap 0 --no-large --no-cpu-baseline --steps 20 --warmup 5 --profile-steps 5 "$@" > $O/p$i.log 2>&1 || tail -3 $O/p$i.log
 done
 cd $R
 python3 - $O <<'PY'

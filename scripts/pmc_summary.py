@@ -5,7 +5,7 @@ import collections, csv, glob, json, os, sys
 rd, out = sys.argv[1], sys.argv[2]
 traffic = json.load(open(os.path.join(rd, "pmc_traffic.json"))) if os.path.exists(os.path.join(rd, "pmc_traffic.json")) else {}
 lines = ["# rocprofv3 --pmc summary (mean per launch; separate --pmc passes per counter set;",
-         "# command: python bench.py --no-large --no-cpu-baseline [--workload c4]; scripts/gpu_round.sh)",
+         "# command: python bench.py --full --no-large --no-cpu-baseline [--workload c4]; scripts/gpu_round.sh)",
          "# hbm bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB  (gfx950 FETCH_SIZE reads half of a wide coalesced stream)", ""]
 for w in ("c2", "c4"):
     acc = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -9,6 +9,6 @@ SETS=("TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RD
 i=0
 for SET in "${SETS[@]}"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --no-host-legs --no-large --no-cpu-baseline --steps 40 --warmup 10 --profile-steps 4 "$@" > $O/p$i.log 2>&1 || tail -2 $O/p$i.log
+  timeout 200 rocprofv3 --pmc $SET --output-format csv -d $O/p$i -o p -- python3 $R/bench.py --full --no-host-legs --no-large --no-cpu-baseline --steps 40 --warmup 10 --profile-steps 4 "$@" > $O/p$i.log 2>&1 || tail -2 $O/p$i.log
 done
 python3 $R/scripts/pmc_traffic.py $TAG $O $OUT

@@ -19,7 +19,7 @@ import json
 for l in open('$O/stage_bench.jsonl'):
     d=json.loads(l); print(d['workload'], d['stage'][:70], d.get('gpu_ms'))
 "
-timeout 600 python3 bench.py 2>/dev/null | tail -1 > $O/bench_default.json
+timeout 600 python3 bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json
 python3 -c "import json; d=json.load(open('$O/bench_default.json')); print(d['value'], d['roofline']['frac'], d['large']['roofline']['frac'], d['large']['raycasting_on'], d['raycasting_on']['us_per_scan_hip_events'], d.get('host_points4_pool_ms_per_scan'))"
-timeout 300 python3 bench.py --workload c3 --steps 2000 --warmup 200 --no-large --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c3.json
+timeout 300 python3 bench.py --full --workload c3 --steps 2000 --warmup 200 --no-large --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c3.json
 python3 -c "import json; d=json.load(open('$O/bench_c3.json')); print('c3', d['value'], d['roofline']['frac'], d['raycasting_on'])"

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r06; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for TAG in sep fused; do
   ARGS=""; [ $TAG = sep ] && ARGS="--overlap 0"
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$TAG -o t -- python3 $R/bench.py --no-large --no-cpu-baseline --no-host-legs --steps 100 --warmup 10 --profile-steps 5 --workload c4 $ARGS > $O/kt_$TAG.log 2>&1 || tail -3 $O/kt_$TAG.log
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$TAG -o t -- python3 $R/bench.py --full --no-large --no-cpu-baseline --no-host-legs --steps 100 --warmup 10 --profile-steps 5 --workload c4 $ARGS > $O/kt_$TAG.log 2>&1 || tail -3 $O/kt_$TAG.log
   python3 - $O/kt_$TAG $TAG <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):

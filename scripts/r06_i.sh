@@ -8,7 +8,7 @@ import json; d=json.load(open('$O/timeline_c2_$T.json')); print('$V', d['grid'],
 done
 for V in "batch_max=32,batch_walk=1" "batch_max=24" "batch_max=20"; do
   A=""; for kv in $(echo $V | tr ',' ' '); do A="$A --set $kv"; done
-  timeout 300 python bench.py --no-cpu-baseline --no-host-legs --no-large $A > $O/b.json 2>/dev/null
+  timeout 300 python bench.py --full --no-cpu-baseline --no-host-legs --no-large $A > $O/b.json 2>/dev/null
   python3 -c "
 import json; d=json.load(open('$O/b.json')); print('$V', round(d['value']), d['ms_per_step'], d['roofline']['frac'])"
 done

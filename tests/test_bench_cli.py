@@ -29,6 +29,13 @@ def test_driver_arguments_are_taken_literally():
     assert (a.gpus, a.steps, a.warmup) == (1, 20, 5)
 
 
+def test_full_is_off_unless_asked_for():
+    """A plain run measures the headline alone; the legs beside it ride behind --full, which changes no step count."""
+    assert parse(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    a = parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert a.full is True and (a.gpus, a.steps, a.warmup) == (1, 20, 5)
+
+
 def test_large_scan_workloads_step_per_scan():
     a = parse(["--workload", "c4"])
     assert (a.steps, a.warmup) == (10000, 1000)

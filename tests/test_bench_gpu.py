@@ -41,7 +41,7 @@ def test_one_rank_rccl_line_certifies_its_communicator():
 
 def test_gpus_2_default_workload_prints_replicas_and_the_global_map():
     r = run_bench("--gpus", "2", "--backend", "gloo", "--devices", "0,0", "--steps", "4", "--warmup", "2",
-                  "--no-cpu-baseline", "--no-host-legs")
+                  "--full", "--no-cpu-baseline", "--no-host-legs")
     assert r["n_gpus"] == 2 and "replicas" in r["config"]["parallelism"]
     g = r["global_map"]
     assert g["n_gpus"] == 2 and g["roofline"]["achieved"] > 0 and g["value"] > 0
@@ -56,7 +56,7 @@ def test_a_failing_global_map_leg_does_not_take_the_replicas_line_with_it():
     at its start (`--fail-global-rank 1`) — rank 0 still prints the replicas' line, with the error in `global_map`, the
     top-level `global_map_ok` false, and every rank leaves with code 0."""
     r = run_bench("--gpus", "2", "--backend", "gloo", "--devices", "0,0", "--steps", "4", "--warmup", "2",
-                  "--no-cpu-baseline", "--no-host-legs", "--collective-timeout", "20", "--fail-global-rank", "1")
+                  "--full", "--no-cpu-baseline", "--no-host-legs", "--collective-timeout", "20", "--fail-global-rank", "1")
     assert r["n_gpus"] == 2 and r["value"] > 0 and "replicas" in r["config"]["parallelism"]
     assert "error" in r["global_map"] and r["global_map_ok"] is False
 
@@ -80,7 +80,7 @@ def test_gpus_4_default_workload_replicas_and_global_map():
     """`bench.py --gpus 4` (the default workload): four replicas of configs[1] + the global-map leg behind them, on a
     2 x 2 tile plan (four ranks on the one GPU here, for the reason test_gpus_4_global_map_plan_and_line_shape gives)."""
     r = run_bench("--gpus", "4", "--backend", "gloo", "--devices", "0,0,0,0", "--steps", "4", "--warmup", "2",
-                  "--no-cpu-baseline", "--no-host-legs", "--global-size-m", "100", timeout=1500)
+                  "--full", "--no-cpu-baseline", "--no-host-legs", "--global-size-m", "100", timeout=1500)
     assert r["n_gpus"] == 4 and "replicas" in r["config"]["parallelism"] and r["value"] > 0
     assert r["global_map_ok"] is True
     g = r["global_map"]
@@ -95,6 +95,25 @@ def test_one_rank_of_the_n_rank_path_reproduces_the_default_line():
     assert a["n_gpus"] == b["n_gpus"] == 1 and a["repeats"] >= 25 and b["repeats"] >= 25
     assert b["ranks"]["world_size"] == 1 and b["ranks"]["distinct_devices"] == 1 and b["ranks"]["ranks"][0]["cus"] == 256
     assert abs(a["value"] - b["value"]) / b["value"] < 0.05, (a["value"], b["value"])
+
+
+def test_a_plain_run_prints_the_headline_alone_and_full_the_other_legs():
+    """A plain run does what its headline figure needs and no more: the line has `value` / `ms_per_step` and none of
+    the objects that take runs of their own; `--full` measures those behind the same timed region (here without the
+    three longest legs)."""
+    extras = ("roofline", "kernels", "latency_path", "cache_resident", "raycasting_on", "large", "cpu_baseline",
+              "host_buffers_ms_per_scan")
+    plain = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert plain["metric"] == "M points/s integrated into ElevationMap" and plain["unit"] == "Mpts/s"
+    assert plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and (plain["steps"], plain["warmup"]) == (20, 5)
+    assert not [k for k in extras if k in plain], sorted(plain)
+    full = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-host-legs",
+                     "--no-large")
+    assert full["roofline"]["achieved"] > 0 and "k_mbatch" in full["kernels"] and full["latency_path"]["us_per_scan"] > 0
+    assert full["cache_resident"]["value"] > 0
+    assert {k: full[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup")} == \
+           {k: plain[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup")}
 
 
 def test_dump_outputs_are_reproducible_and_follow_steps(tmp_path):
