@@ -67,6 +67,15 @@ class FdmFusionConfig(C.Structure):
     ]
 
 
+class FdmImageConfig(C.Structure):
+    """fdm_image_config == fastdem::io::PngExportConfig (io/png.hpp)."""
+
+    _fields_ = [
+        ("normalize", C.c_int32), ("colormap", C.c_int32), ("align_to_world", C.c_int32),
+        ("fixed_min", C.c_float), ("fixed_max", C.c_float),
+    ]
+
+
 class FdmGeometry(C.Structure):
     _fields_ = [
         ("length_x", C.c_double), ("length_y", C.c_double), ("resolution", C.c_double),
@@ -113,6 +122,9 @@ SENSOR_CONSTANT, SENSOR_LIDAR, SENSOR_RGBD = 0, 1, 2
 MODE_LOCAL, MODE_GLOBAL = 0, 1
 EST_KALMAN, EST_P2 = 0, 1
 FDM_OK, FDM_SKIP_EMPTY_CLOUD, FDM_SKIP_ALL_FILTERED = 0, 1, 2
+FDM_ERR_INVALID, FDM_ERR_HIP, FDM_ERR_NO_LAYER, FDM_ERR_NO_DEVICE = -1, -2, -3, -4
+NORMALIZE = {"min_max": 0, "percentile_1_99": 1, "fixed_range": 2}   # PngExportConfig::Normalize
+COLORMAP = {"grayscale": 0, "viridis": 1, "jet": 2}                  # PngExportConfig::Colormap
 
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -210,6 +222,11 @@ PROTOTYPES = {
     "fdm_engine_pack_cloud_device": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(_P), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint32)]),
+    "fdm_default_image_config": (None, [C.POINTER(FdmImageConfig)]),
+    "fdm_engine_render_layer": (C.c_int, [_P, C.c_char_p, C.POINTER(FdmImageConfig), _P, C.c_uint64,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F]),
+    "fdm_engine_render_layer_device": (C.c_int, [_P, C.c_char_p, C.POINTER(FdmImageConfig), C.POINTER(_P),
+                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F]),
     "fdm_engine_enable_cell_ids": (C.c_int, [_P, C.c_int]),
     "fdm_engine_last_cell_ids": (C.c_int, [_P, _P, C.c_uint64]),
     "fdm_engine_enable_profile": (C.c_int, [_P, C.c_int]),
@@ -245,4 +262,10 @@ def load():
 def default_config():
     cfg = FdmConfig()
     load().fdm_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_image_config():
+    cfg = FdmImageConfig()
+    load().fdm_default_image_config(C.byref(cfg))
     return cfg

@@ -21,27 +21,11 @@
 #include <vector>
 
 #include "fastdem/elevation_map.hpp"
+#include "fastdem/io/crc32.hpp"
 
 namespace fastdem {
 namespace io {
 namespace detail {
-
-inline uint32_t crc32(const void* data, size_t len) {  // IEEE 802.3, reflected, poly 0xEDB88320
-  static uint32_t table[256];
-  static bool ready = false;
-  if (!ready) {
-    for (uint32_t n = 0; n < 256; ++n) {
-      uint32_t c = n;
-      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-      table[n] = c;
-    }
-    ready = true;
-  }
-  uint32_t crc = ~0u;
-  const uint8_t* p = static_cast<const uint8_t*>(data);
-  for (size_t i = 0; i < len; ++i) crc = table[(crc ^ p[i]) & 0xFFu] ^ (crc >> 8);
-  return ~crc;
-}
 
 struct ByteSink {  // little-endian serialiser
   std::string b;

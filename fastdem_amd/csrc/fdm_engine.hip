@@ -1070,6 +1070,8 @@ void fdm_engine_destroy(fdm_engine* e) {
   if (e->d_in) (void)hipFree(e->d_in);
   if (e->pack_counts) (void)hipFree(e->pack_counts);
   if (e->d_pack) (void)hipFree(e->d_pack);
+  if (e->d_image) (void)hipFree(e->d_image);
+  if (e->d_render) (void)hipFree(e->d_render);
   if (e->rc_cnt) (void)hipFree(e->rc_cnt);
   if (e->rc_min) (void)hipFree(e->rc_min);
   if (e->ray_bins) (void)hipFree(e->ray_bins);

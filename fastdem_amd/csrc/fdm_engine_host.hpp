@@ -37,6 +37,7 @@
 #include "fdm_rbatch.hpp"
 #include "fdm_rsort.hpp"
 #include "fdm_egress.hpp"
+#include "fdm_render.hpp"
 #include "fdm_ingest.hpp"
 #include "fdm_post.hpp"
 
@@ -364,6 +365,10 @@ struct fdm_engine {
   size_t pack_counts_cap = 0;
   float* d_pack = nullptr;           // packed records
   size_t pack_cap = 0;               // in floats
+  // layer images (fdm_render.hpp)
+  uint32_t* d_image = nullptr;       // RGBA8 pixels of the last render, row-major
+  size_t image_cap = 0;              // in pixels
+  RenderState* d_render = nullptr;   // histograms, ranks, the normalisation range
 };
 
 // ---- helpers shared by the library's translation units ----

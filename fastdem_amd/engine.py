@@ -76,6 +76,24 @@ def host_array(values, dtype=np.float32):
     return h
 
 
+def write_png(path, rgba):
+    """uint8[height, width, 4] -> an 8-bit RGBA PNG, filter 0 on every scanline, through the standard library's zlib."""
+    import struct
+    import zlib
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    assert rgba.ndim == 3 and rgba.shape[2] == 4 and rgba.shape[0] > 0 and rgba.shape[1] > 0, rgba.shape
+    h, w = rgba.shape[:2]
+    lines = np.zeros((h, 1 + 4 * w), dtype=np.uint8)  # column 0: the filter type
+    lines[:, 1:] = rgba.reshape(h, 4 * w)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(lines.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
 class Engine:
     # engine options (fdm_engine_set_option) every new Engine receives right after creation; the GPU test
     # suite uses it to run each test on both scan pipelines (tests/conftest.py)
@@ -492,6 +510,42 @@ class Engine:
         _ck(self._lib.fdm_engine_pack_cloud_device(self._h, elevation_layer.encode(), r0, c0, nr, nc,
                                                    C.byref(d), C.byref(n), C.byref(step)))
         return d.value, n.value, step.value
+
+    # -- layer images (fastdem::io::savePng's pixels) --
+    @staticmethod
+    def _image_config(normalize, colormap, align_to_world, fixed):
+        def enum(table, v):
+            return table[v] if isinstance(v, str) else int(v)
+        return capi.FdmImageConfig(enum(capi.NORMALIZE, normalize), enum(capi.COLORMAP, colormap),
+                                   int(bool(align_to_world)), float(fixed[0]), float(fixed[1]))
+
+    def render_layer(self, layer, normalize="percentile_1_99", colormap="viridis", align_to_world=True,
+                     fixed=(-2.0, 2.0)):
+        """One layer as savePng colours it, computed on the device: (rgba uint8[rows, cols, 4], (vmin, vmax))."""
+        cfg = self._image_config(normalize, colormap, align_to_world, fixed)
+        w, h = C.c_int32(0), C.c_int32(0)
+        name = layer.encode()
+        _ck(self._lib.fdm_engine_render_layer(self._h, name, C.byref(cfg), None, 0, C.byref(w), C.byref(h), None))
+        rgba = np.empty((h.value, w.value, 4), dtype=np.uint8)
+        rng = (C.c_float * 2)()
+        _ck(self._lib.fdm_engine_render_layer(self._h, name, C.byref(cfg), _ptr(rgba), rgba.nbytes, C.byref(w),
+                                              C.byref(h), rng))
+        return rgba, (np.float32(rng[0]), np.float32(rng[1]))
+
+    def render_layer_device(self, layer, normalize="percentile_1_99", colormap="viridis", align_to_world=True,
+                            fixed=(-2.0, 2.0), want_range=True):
+        """The image stays in HBM until the next render: (device pointer, width, height, (vmin, vmax) or None)."""
+        cfg = self._image_config(normalize, colormap, align_to_world, fixed)
+        w, h, d = C.c_int32(0), C.c_int32(0), C.c_void_p()
+        rng = (C.c_float * 2)()
+        _ck(self._lib.fdm_engine_render_layer_device(self._h, layer.encode(), C.byref(cfg), C.byref(d), C.byref(w),
+                                                     C.byref(h), rng if want_range else None))
+        return d.value, w.value, h.value, ((np.float32(rng[0]), np.float32(rng[1])) if want_range else None)
+
+    def save_png(self, path, layer, **image):
+        """fastdem::io::savePng: render `layer` (keywords as render_layer) and write it as an 8-bit RGBA PNG."""
+        rgba, _ = self.render_layer(layer, **image)
+        write_png(path, rgba)
 
     # -- raycasting stage (SURVEY.md §8 f1) --
     def apply_raycasting(self, x, y, z, sensor_origin, rc=None):

@@ -386,6 +386,33 @@ int fdm_engine_pack_cloud_device(fdm_engine* e, const char* elevation_layer, int
                                  int32_t sub_c0, int32_t sub_rows, int32_t sub_cols, void** d_out,
                                  uint64_t* n_points, uint32_t* point_step);
 
+/* ---- Layer images ----
+ * The pixels of fastdem::io::savePng (io/png.hpp, src/io_png.cpp:115-171) computed on the device: one layer
+ * -> row-major RGBA8, height = rows and width = cols of the stored window, 4 bytes per cell, a cell that is
+ * not finite transparent black.  The normalisation range is computeRange's (io_png.cpp:32-65): the two
+ * fixed numbers, min / max over the finite cells, or the order statistics of rank size_t(n * 0.01) and
+ * min(size_t(n * 0.99), n - 1) of the n finite cells (one radix select for both, no sort); {0, 1} when no
+ * cell is finite.  Pixels and range are exactly the reference's, bit for bit.
+ * Mirrors fastdem::io::PngExportConfig field for field. */
+typedef struct fdm_image_config {
+  int32_t normalize;       /* Normalize: 0 MIN_MAX, 1 PERCENTILE_1_99, 2 FIXED_RANGE */
+  int32_t colormap;        /* Colormap: 0 GRAYSCALE, 1 VIRIDIS, 2 JET */
+  int32_t align_to_world;  /* != 0: unroll the circular buffer from the start index */
+  float fixed_min, fixed_max;
+} fdm_image_config;
+void fdm_default_image_config(fdm_image_config* cfg);  /* PngExportConfig{}: PERCENTILE_1_99, VIRIDIS, aligned, -2 .. 2 */
+/* host_rgba receives width * height * 4 bytes when cap_bytes allows; pass NULL (or a too small cap) to
+ * learn width / height first — nothing is rendered then.  range2 (nullable) receives the {min, max} the
+ * image was normalised with.  Any layer renders, internal ones ('_...') included; a missing layer is
+ * FDM_ERR_NO_LAYER, an enum value out of range FDM_ERR_INVALID.  The map is not changed. */
+int fdm_engine_render_layer(fdm_engine* e, const char* layer, const fdm_image_config* cfg,
+                            void* host_rgba, uint64_t cap_bytes, int32_t* width, int32_t* height,
+                            float range2[2]);
+/* Same, the image stays in an engine-owned HBM buffer (valid until the next render call).  With
+ * range2 == NULL the call only enqueues; asking for the range waits for it. */
+int fdm_engine_render_layer_device(fdm_engine* e, const char* layer, const fdm_image_config* cfg,
+                                   void** d_rgba, int32_t* width, int32_t* height, float range2[2]);
+
 /* ---- Ingest ----
  * nanopcl::from(sensor_msgs::PointCloud2) (nanopcl/bridge/ros/impl.hpp:174-246) on the device.
  * The layout carries the byte offsets the reference parses from msg.fields (impl.hpp:65-99):

@@ -62,6 +62,17 @@ print(json.dumps({"stage": "egress_pack_cloud", "workload": a.workload, "cells":
                   "GBps": round(alg / t / 1e9, 1), "hbm_frac": round(alg / t / HBM, 4),
                   "cpu_oracle_ms": round(t_cpu * 1e3, 2), "speedup": round(t_cpu / t, 1)}))
 
+# ---- render: one layer -> RGBA8 image (savePng's pixels; radix select for the 1 % / 99 % range + colour map) beside the
+# download of the same layer, the only route to those pixels without the stage ----
+t_dev = timed(lambda: eng.render_layer_device("elevation", want_range=False), a.iters)   # image stays in HBM
+t_host = timed(lambda: eng.render_layer("elevation"), a.iters)                            # + range + one RGBA copy out
+t_down = timed(lambda: eng.layer("elevation"), a.iters)
+alg = cells * 4 * 5 + cells * 4   # four digit passes + the colour pass read the layer, the image is written once
+print(json.dumps({"stage": "render (percentile_1_99, viridis)", "workload": a.workload, "cells": cells,
+                  "gpu_ms": round(t_dev * 1e3, 4), "to_host_ms": round(t_host * 1e3, 4),
+                  "layer_download_ms": round(t_down * 1e3, 4), "algorithmic_MB": round(alg / 1e6, 2),
+                  "GBps": round(alg / t_dev / 1e9, 1), "hbm_frac": round(alg / t_dev / HBM, 4)}))
+
 # ---- ingest: PointCloud2 blob (32-byte records, x y z _ intensity ring time) already in HBM ----
 s = wl.scans[0]
 blob, lay = make_blob(s["x"], s["y"], s["z"], intensity=s["intensity"] if s["intensity"] is not None else np.zeros_like(s["x"]),
