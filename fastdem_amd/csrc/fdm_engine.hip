@@ -40,8 +40,8 @@ void poll_dense_paid(fdm_engine* e) {
 int sync_all(fdm_engine* e) {
   if (int rc = join_streams(e)) return rc;
   HIPCK(hipStreamSynchronize(e->stream));
-  for (hipStream_t rs : e->ray_stream)  // (every early stage part has its resolve on the main stream behind it by now: idle)
-    if (rs) HIPCK(hipStreamSynchronize(rs));
+  for (const RayBank& b : e->ray_bank)  // (every early stage part has its resolve on the main stream behind it by now: idle)
+    if (b.stream) HIPCK(hipStreamSynchronize(b.stream));
   e->bstage_busy = false;  // (the stream has drained: nothing reads the host-batch staging block any more)
   poll_dense_paid(e);
   return FDM_OK;
@@ -534,10 +534,10 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   if (e->profile) HIPCK(hipEventRecord(e->ev[1], e->stream));
   // (option "ray_overlap": this scan's early stage waits for its bin half — marked HERE, ahead of the previous scan's stage
   //  that run_held_ray_stage is about to put on this stream.  So this mark orders the early stage against the bin only;
-  //  against that previous stage, which uses the buffers of its bank, it is ordered by ev_ray_res[bank], which
+  //  against that previous stage, which uses the buffers of its bank, it is ordered by the bank's ev_res, which
   //  run_held_ray_stage records behind it on either path and start_ray_stage_early waits for as well)
   e->ray_bin_marked = false;
-  if (ray_held && e->opt.ray_overlap && e->ray_stream[0]) {
+  if (ray_held && e->opt.ray_overlap && e->ray_bank[0].stream) {
     HIPCK(hipEventRecord(e->ev_ray_bin, e->stream));
     e->ray_bin_marked = true;
   }
@@ -1072,30 +1072,10 @@ void fdm_engine_destroy(fdm_engine* e) {
   if (e->d_pack) (void)hipFree(e->d_pack);
   if (e->d_image) (void)hipFree(e->d_image);
   if (e->d_render) (void)hipFree(e->d_render);
-  if (e->rc_cnt) (void)hipFree(e->rc_cnt);
-  if (e->rc_min) (void)hipFree(e->rc_min);
-  if (e->ray_bins) (void)hipFree(e->ray_bins);
-  for (int k = 0; k < 2; ++k) {
-    if (e->vkeys[k]) (void)hipFree(e->vkeys[k]);
-    if (e->vidx[k]) (void)hipFree(e->vidx[k]);
-  }
-  if (e->vsel) (void)hipFree(e->vsel);
-  if (e->ray_blk) (void)hipFree(e->ray_blk);
-  if (e->sort_tmp) (void)hipFree(e->sort_tmp);
+  for (RayBank& b : e->ray_bank) b.release();  // the raycasting stage's buffers, streams and events
+  if (e->ev_ray_bin) (void)hipEventDestroy(e->ev_ray_bin);
   if (e->vs_cnt) (void)hipFree(e->vs_cnt);
   if (e->vs_rec) (void)hipFree(e->vs_rec);
-  if (e->is_buf) (void)hipFree(e->is_buf);
-  {  // the second set of the raycasting stage's buffers, its streams and events (option "ray_overlap")
-    fdm_engine::RayBank& b = e->ray_bank1;
-    for (void* p : {static_cast<void*>(b.rc_cnt), static_cast<void*>(b.rc_min), static_cast<void*>(b.ray_bins),
-                    static_cast<void*>(b.vkeys[0]), static_cast<void*>(b.vkeys[1]), static_cast<void*>(b.vidx[0]),
-                    static_cast<void*>(b.vidx[1]), static_cast<void*>(b.vsel), static_cast<void*>(b.ray_blk), b.sort_tmp,
-                    b.is_buf})
-      if (p) (void)hipFree(p);
-    for (hipStream_t rs : e->ray_stream) if (rs) (void)hipStreamDestroy(rs);
-    for (hipEvent_t ev : {e->ev_ray_pre[0], e->ev_ray_pre[1], e->ev_ray_res[0], e->ev_ray_res[1], e->ev_ray_bin})
-      if (ev) (void)hipEventDestroy(ev);
-  }
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }

@@ -160,6 +160,42 @@ struct EngineOptions {
   int dbg_post = 0;                  // measurement only: 1 = untiled feature kernel, 32 = fusion with integer samples, 64 = features with min / max chains
 };
 
+// Everything ONE raycasting stage in flight writes, and what orders its uses (fdm_engine_ray.inl).  Every helper of the
+// stage is told its bank and its stream; the engine has two banks (fdm_engine::ray_bank).
+// WHO USES WHICH: bank 0 serves every stage that runs whole on the main stream (the normal path: run_held_ray_stage,
+// fdm_engine_apply_raycasting*, fdm_engine_voxel_any) AND, with option "ray_overlap", the early part of even scans' stages
+// on `stream`; bank 1 serves the early part of odd scans' stages only.  WHAT ORDERS THEM: a bank's next early part waits
+// for `ev_res`, recorded on the main stream behind the last stage that used the bank — behind its k_ray_resolve on the
+// early path, behind the whole stage on the normal path (bank 0, once the streams exist); the main stream waits for
+// `ev_pre`, recorded behind an early part, before it resolves.  Buffers are allocated, grown and initialised on the MAIN
+// stream (ensure_*), which may drain every stream; only a stage's launches (enqueue_*) go on the bank's stream.
+struct RayBank {
+  uint32_t* rc_cnt = nullptr;        // [ncell] ray-scan points observed in the cell this frame
+  uint32_t* rc_min = nullptr;        // [ncell] ord(min ray height), kRayEmpty = not traversed
+  uint32_t* ray_bins = nullptr;      // large scans: ray-queue bucket counts | offsets | block sums (fdm_raycast.hpp)
+  unsigned long long* vkeys[2] = {nullptr, nullptr};  // voxel keys: unsorted / sorted
+  uint32_t* vidx[2] = {nullptr, nullptr};             // point indices: unsorted / sorted
+  uint32_t* vsel = nullptr;          // voxel_any output staging
+  uint32_t* ray_blk = nullptr;       // rays queued per block of k_ray_compact (large scans: block-local queue regions)
+  size_t vcap = 0;                   // points the voxel / queue buffers hold
+  void* sort_tmp = nullptr;          // the radix sort's histograms (fdm_rsort.hpp)
+  size_t sort_tmp_bytes = 0;
+  void* is_buf = nullptr;            // fdm_introsort.hpp's level buffers, rank tables, segment lists (is_layout)
+  size_t is_cap = 0;                 // pairs is_buf is laid out for
+  hipStream_t stream = nullptr;      // where the bank's early parts run (ensure_ray_streams)
+  hipEvent_t ev_pre = nullptr;       // behind the last early part, on `stream`
+  hipEvent_t ev_res = nullptr;       // behind the last stage that used the bank, on the main stream
+  bool res_pending = false;          // ev_res has been recorded
+  void release() {                   // (fdm_engine_destroy: nothing is in flight)
+    for (void* p : {(void*)rc_cnt, (void*)rc_min, (void*)ray_bins, (void*)vkeys[0], (void*)vkeys[1], (void*)vidx[0],
+                    (void*)vidx[1], (void*)vsel, (void*)ray_blk, sort_tmp, is_buf})
+      if (p) (void)hipFree(p);
+    if (stream) (void)hipStreamDestroy(stream);
+    for (hipEvent_t ev : {ev_pre, ev_res})
+      if (ev) (void)hipEventDestroy(ev);
+  }
+};
+
 struct fdm_engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -223,41 +259,19 @@ struct fdm_engine {
   bool saved_want_ids = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float last_ms[3] = {0.f, 0.f, 0.f};
-  // raycasting stage (fdm_raycast.hpp)
-  uint32_t* rc_cnt = nullptr;        // [ncell] ray-scan points observed in the cell this frame
-  uint32_t* rc_min = nullptr;        // [ncell] ord(min ray height), kRayEmpty = not traversed
-  uint32_t* ray_bins = nullptr;      // large scans: ray-queue bucket counts | offsets | block sums (fdm_raycast.hpp)
-  unsigned long long* vkeys[2] = {nullptr, nullptr};  // voxel keys: unsorted / sorted
-  uint32_t* vidx[2] = {nullptr, nullptr};             // point indices: unsorted / sorted
-  uint32_t* vsel = nullptr;          // voxel_any output staging
-  uint32_t* ray_blk = nullptr;       // rays queued per block of k_ray_compact (large scans: block-local queue regions)
-  size_t vcap = 0;
-  void* sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
+  // raycasting stage (fdm_raycast.hpp, host side: fdm_engine_ray.inl)
+  RayBank ray_bank[2];               // the stage's buffers (above): [0] the normal path's, [k] the early stage's of scans of parity k
+  hipEvent_t ev_ray_bin = nullptr;   // behind a scan's bin half on the main stream: that scan's early stage waits for it
+  bool ray_bin_marked = false;       // ev_ray_bin was recorded behind the current scan's bin half (enqueue_scan)
+  // the sort-free voxel filter of small scans (k_vs_*): normal-path stages on the main stream only, never an early stage
   uint32_t* vs_cnt = nullptr;        // fine | coarse bucket counters | valid points of k_vs_*
   uint4* vs_rec = nullptr;           // {key, point, bucket start, bucket size} by position
   size_t vs_rec_cap = 0;
-  VoxelSmall vs{};                   // the last small-scan filter's parameters (k_vs_mark runs from enqueue_ray_stage)
-  void* is_buf = nullptr;            // fdm_introsort.hpp's level buffers, rank tables, segment lists (is_layout)
-  size_t is_cap = 0;                 // pairs is_buf is laid out for
+  VoxelSmall vs{};                   // the last small-scan filter's parameters (k_vs_mark runs from enqueue_ray_walk)
   hipEvent_t ev_ray[2] = {nullptr, nullptr};
   hipEvent_t ev_timer[2] = {nullptr, nullptr};  // fdm_engine_timer_start / _stop
   bool ray_timed = false;
   bool sync_call = false;            // a synchronous entry point is running (its flush follows the enqueue at once)
-  struct RayBank {                   // the second set of the stage's buffers (ray_bank_swap)
-    uint32_t *rc_cnt = nullptr, *rc_min = nullptr, *ray_bins = nullptr;
-    unsigned long long* vkeys[2] = {nullptr, nullptr};
-    uint32_t* vidx[2] = {nullptr, nullptr};
-    uint32_t *vsel = nullptr, *ray_blk = nullptr;
-    void* sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0, vcap = 0;
-    void* is_buf = nullptr;
-    size_t is_cap = 0;
-  } ray_bank1;
-  hipStream_t ray_stream[2] = {nullptr, nullptr};
-  hipEvent_t ev_ray_pre[2] = {nullptr, nullptr}, ev_ray_res[2] = {nullptr, nullptr}, ev_ray_bin = nullptr;
-  bool ray_res_pending[2] = {false, false};  // ev_ray_res[k] has been recorded since the bank was last used
-  bool ray_bin_marked = false;       // ev_ray_bin was recorded behind the current scan's bin half (enqueue_scan)
   // update(t) || bin(t+1) in ONE launch (k_update_bin): the update of the last small scan is held back
   // until the next scan arrives (or any other entry point / sync flushes it); the scratch is
   // double-buffered by scan parity.
@@ -281,8 +295,7 @@ struct fdm_engine {
     unsigned upd_blocks = 0;
     // the scan's raycasting stage (fastdem.cpp:152-159), which runs right behind this update wherever that is launched
     bool ray = false;
-    int ray_pre = 0;        // 1 + context if the stage's first part already left on a ray stream (ray_overlap)
-    int ray_key_mode = 0;   // ... and what enqueue_voxel_sort left in the buffers
+    int ray_pre = 0;        // 1 + bank if the stage's first part already left on that bank's stream (ray_overlap)
     RayParams RQ;
     const float *ray_x = nullptr, *ray_y = nullptr, *ray_z = nullptr;  // the scan's preprocessed cloud (d_rcap[parity])
     double ray_box[6] = {0, 0, 0, 0, 0, 0};
@@ -404,13 +417,9 @@ bool voxel_size_ok(float v);
 int ensure_ray_layers(fdm_engine* e);
 VoxelCompact voxel_compact_of(float voxel_size, const double* box);
 void ray_box_of(const fdm_engine* e, const ScanParams& P, double box[6]);
-int enqueue_voxel_sort(fdm_engine* e, unsigned n, float voxel_size, int flag_slot, const float* dx,
-                       const float* dy, const float* dz, const double* box, int* key_mode);
 fdm_raycast_config ray_config_of(const fdm_config& c);
 RayParams make_ray_params(fdm_engine* e, const fdm_raycast_config& c, const float* origin, unsigned n,
                           int slot, int flag_slot);
-int enqueue_ray_stage(fdm_engine* e, const RayParams& Q, bool voxel, const float* dx, const float* dy,
-                      const float* dz, int key_mode = 0, int phase = 3);  // phase: 1 = everything but k_ray_resolve, 2 = k_ray_resolve, 3 = both
 int run_held_ray_stage(fdm_engine* e, fdm_engine::PendingUpdate& u);
 int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const ScanParams& P);
 // the large-scan pipeline (fdm_engine_tiled.hip)

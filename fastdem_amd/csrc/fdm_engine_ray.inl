@@ -1,6 +1,10 @@
 // fdm_engine_ray.inl — host side of the raycasting stage (kernels: fdm_raycast.hpp): voxel sort, ray
-// queue, resolve; entry points fdm_engine_apply_raycasting*, fdm_engine_voxel_any, fdm_engine_last_ray_ms.
+// queue, walk, resolve; entry points fdm_engine_apply_raycasting*, fdm_engine_voxel_any, fdm_engine_last_ray_ms.
 // The body of fdm_engine_ray.hip (one of the library's five translation units, fdm_engine_host.hpp).
+// A stage works in a RayBank (fdm_engine_host.hpp: its buffers, and who may use which bank when) and launches on one
+// stream; both are ARGUMENTS of every helper here (RayLane), never state of the engine.  ensure_* allocate, grow and
+// initialise a bank on the MAIN stream and may drain every stream (sync_all); enqueue_* only launch, on the lane's
+// stream: every ensure_* a stage needs comes before its first enqueue_*.
 
 namespace fdmh {
 
@@ -15,42 +19,50 @@ int ensure_ray_layers(fdm_engine* e) {
   return FDM_OK;
 }
 
-int ensure_ray_cells(fdm_engine* e) {
-  if (e->rc_cnt) return FDM_OK;
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&e->rc_cnt), e->ncell * sizeof(uint32_t)));
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&e->rc_min), e->ncell * sizeof(uint32_t)));
+// where a stage's launches go: the bank they work in, the stream they are put on
+struct RayLane {
+  RayBank& b;
+  hipStream_t s;
+};
+
+// ---- a bank's buffers (ensure_*: on the MAIN stream, whichever stream the stage then takes) ----
+int ensure_ray_cells(fdm_engine* e, RayBank& b) {
+  if (b.rc_cnt) return FDM_OK;
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.rc_cnt), e->ncell * sizeof(uint32_t)));
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.rc_min), e->ncell * sizeof(uint32_t)));
   const int blocks = int(std::min<size_t>((e->ncell + 255) / 256, 4096));
-  hipLaunchKernelGGL(k_fill_u32, dim3(blocks), dim3(256), 0, e->stream, e->rc_cnt, 0u, e->ncell);
-  hipLaunchKernelGGL(k_fill_u32, dim3(blocks), dim3(256), 0, e->stream, e->rc_min, kRayEmpty, e->ncell);
+  hipLaunchKernelGGL(k_fill_u32, dim3(blocks), dim3(256), 0, e->stream, b.rc_cnt, 0u, e->ncell);
+  hipLaunchKernelGGL(k_fill_u32, dim3(blocks), dim3(256), 0, e->stream, b.rc_min, kRayEmpty, e->ncell);
   // bucket counts (kept at zero between scans by k_ray_bin_scan) | bucket offsets | per-block sums
   const size_t bin_words = 2u * size_t(kRayBins) + kRayBins / kRayBinBlock;
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&e->ray_bins), bin_words * sizeof(uint32_t)));
-  HIPCK(hipMemsetAsync(e->ray_bins, 0, bin_words * sizeof(uint32_t), e->stream));
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.ray_bins), bin_words * sizeof(uint32_t)));
+  HIPCK(hipMemsetAsync(b.ray_bins, 0, bin_words * sizeof(uint32_t), e->stream));
   HIPCK(hipGetLastError());
   return FDM_OK;
 }
 
-int ensure_voxel_buffers(fdm_engine* e, size_t n) {
-  if (n <= e->vcap) return FDM_OK;
+// (sync_all flushes a held-back stage, which runs in bank 0 and may grow it first: everything is idle afterwards)
+int ensure_voxel_buffers(fdm_engine* e, RayBank& b, size_t n) {
+  if (n <= b.vcap) return FDM_OK;
   if (int rc_sync = sync_all(e)) return rc_sync;
   for (int k = 0; k < 2; ++k) {
-    if (e->vkeys[k]) HIPCK(hipFree(e->vkeys[k]));
-    if (e->vidx[k]) HIPCK(hipFree(e->vidx[k]));
+    if (b.vkeys[k]) HIPCK(hipFree(b.vkeys[k]));
+    if (b.vidx[k]) HIPCK(hipFree(b.vidx[k]));
   }
-  if (e->vsel) HIPCK(hipFree(e->vsel));
-  if (e->ray_blk) HIPCK(hipFree(e->ray_blk));
-  if (e->sort_tmp) HIPCK(hipFree(e->sort_tmp));
-  e->vcap = n + n / 4 + 1024;
+  if (b.vsel) HIPCK(hipFree(b.vsel));
+  if (b.ray_blk) HIPCK(hipFree(b.ray_blk));
+  if (b.sort_tmp) HIPCK(hipFree(b.sort_tmp));
+  b.vcap = n + n / 4 + 1024;
   for (int k = 0; k < 2; ++k) {
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vkeys[k]), e->vcap * sizeof(unsigned long long)));
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vidx[k]), e->vcap * sizeof(uint32_t)));
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vkeys[k]), b.vcap * sizeof(unsigned long long)));
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vidx[k]), b.vcap * sizeof(uint32_t)));
   }
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vsel), e->vcap * sizeof(uint32_t)));
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&e->ray_blk), (e->vcap / 512u + 2u) * sizeof(uint32_t)));  // (blocks of >= 512 points)
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vsel), b.vcap * sizeof(uint32_t)));
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.ray_blk), (b.vcap / 512u + 2u) * sizeof(uint32_t)));  // (blocks of >= 512 points)
   // the radix sort's histogram: 256 bins x tiles, + the 256 totals (fdm_rsort.hpp)
-  const size_t tiles = std::max((e->vcap + kRsTile - 1) / kRsTile, (size_t(kRsSmallMax) + kRsTileSmall - 1) / kRsTileSmall);
-  e->sort_tmp_bytes = (256u * tiles + 256u) * sizeof(uint32_t);
-  HIPCK(hipMalloc(&e->sort_tmp, e->sort_tmp_bytes));
+  const size_t tiles = std::max((b.vcap + kRsTile - 1) / kRsTile, (size_t(kRsSmallMax) + kRsTileSmall - 1) / kRsTileSmall);
+  b.sort_tmp_bytes = (256u * tiles + 256u) * sizeof(uint32_t);
+  HIPCK(hipMalloc(&b.sort_tmp, b.sort_tmp_bytes));
   return FDM_OK;
 }
 
@@ -59,45 +71,48 @@ int ensure_voxel_buffers(fdm_engine* e, size_t n) {
 int voxel_sort_passes(unsigned bits) { return int((bits + 7u) / 8u); }
 int voxel_sort_source(unsigned bits) { return (voxel_sort_passes(bits) & 1) ? 0 : 1; }
 template <typename KEY, unsigned TILE>
-int enqueue_radix_sort_t(fdm_engine* e, unsigned n, unsigned bits) {
+int enqueue_radix_sort_t(const RayLane& lane, unsigned n, unsigned bits) {
+  RayBank& b = lane.b;
   const unsigned tiles = (n + TILE - 1u) / TILE;
-  uint32_t* const hist = static_cast<uint32_t*>(e->sort_tmp);
+  uint32_t* const hist = static_cast<uint32_t*>(b.sort_tmp);
   uint32_t* const total = hist + size_t(256) * tiles;
   int src = voxel_sort_source(bits);
   for (int pass = 0; pass < voxel_sort_passes(bits); ++pass, src ^= 1) {
-    const KEY* kin = reinterpret_cast<const KEY*>(e->vkeys[src]);
-    KEY* kout = reinterpret_cast<KEY*>(e->vkeys[src ^ 1]);
+    const KEY* kin = reinterpret_cast<const KEY*>(b.vkeys[src]);
+    KEY* kout = reinterpret_cast<KEY*>(b.vkeys[src ^ 1]);
     const unsigned shift = unsigned(pass) * 8u;
     // (the first pass's histogram is k_voxel_keys' and its indices are the positions)
     if (pass > 0)
-      hipLaunchKernelGGL((k_rs_hist<KEY, TILE>), dim3(tiles), dim3(256), 0, e->stream, n, kin, shift, tiles, hist);
-    hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, e->stream, tiles, hist, total);
+      hipLaunchKernelGGL((k_rs_hist<KEY, TILE>), dim3(tiles), dim3(256), 0, lane.s, n, kin, shift, tiles, hist);
+    hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, lane.s, tiles, hist, total);
     if (pass > 0)
-      hipLaunchKernelGGL((k_rs_scatter<KEY, true, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, e->stream, n, kin,
-                         e->vidx[src], kout, e->vidx[src ^ 1], shift, tiles, hist, total);
+      hipLaunchKernelGGL((k_rs_scatter<KEY, true, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, lane.s, n, kin,
+                         b.vidx[src], kout, b.vidx[src ^ 1], shift, tiles, hist, total);
     else
-      hipLaunchKernelGGL((k_rs_scatter<KEY, false, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, e->stream, n, kin,
-                         static_cast<const uint32_t*>(nullptr), kout, e->vidx[src ^ 1], shift, tiles, hist, total);
+      hipLaunchKernelGGL((k_rs_scatter<KEY, false, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, lane.s, n, kin,
+                         static_cast<const uint32_t*>(nullptr), kout, b.vidx[src ^ 1], shift, tiles, hist, total);
   }
   HIPCK(hipGetLastError());
   return FDM_OK;
 }
 template <typename KEY>
-int enqueue_radix_sort(fdm_engine* e, unsigned n, unsigned bits) {
-  return rs_tile(n) == kRsTileSmall ? enqueue_radix_sort_t<KEY, kRsTileSmall>(e, n, bits)
-                                    : enqueue_radix_sort_t<KEY, kRsTile>(e, n, bits);
+int enqueue_radix_sort(const RayLane& lane, unsigned n, unsigned bits) {
+  return rs_tile(n) == kRsTileSmall ? enqueue_radix_sort_t<KEY, kRsTileSmall>(lane, n, bits)
+                                    : enqueue_radix_sort_t<KEY, kRsTile>(lane, n, bits);
 }
+// the keys of the scan's points into vkeys[src] (+ the sort's first histogram)
 template <typename KEY>
-void launch_voxel_keys(fdm_engine* e, unsigned n, float inv, int flag_slot, const VoxelCompact& C, const float* dx,
-                       const float* dy, const float* dz, KEY* keys) {
+void launch_voxel_keys(fdm_engine* e, const RayLane& lane, unsigned n, float inv, int flag_slot, const VoxelCompact& C,
+                       const float* dx, const float* dy, const float* dz, int src) {
   const unsigned tile = rs_tile(n), tiles = (n + tile - 1u) / tile;
-  uint32_t* const hist = static_cast<uint32_t*>(e->sort_tmp);
+  uint32_t* const hist = static_cast<uint32_t*>(lane.b.sort_tmp);
+  KEY* const keys = reinterpret_cast<KEY*>(lane.b.vkeys[src]);
   if (tile == kRsTileSmall)
-    hipLaunchKernelGGL((k_voxel_keys<KEY, kRsTileSmall>), dim3(tiles), dim3(256), 0, e->stream, n, inv, flag_slot, C,
-                       e->d_state, dx, dy, dz, keys, e->vsel, tiles, hist);
+    hipLaunchKernelGGL((k_voxel_keys<KEY, kRsTileSmall>), dim3(tiles), dim3(256), 0, lane.s, n, inv, flag_slot, C,
+                       e->d_state, dx, dy, dz, keys, lane.b.vsel, tiles, hist);
   else
-    hipLaunchKernelGGL((k_voxel_keys<KEY, kRsTile>), dim3(tiles), dim3(256), 0, e->stream, n, inv, flag_slot, C,
-                       e->d_state, dx, dy, dz, keys, e->vsel, tiles, hist);
+    hipLaunchKernelGGL((k_voxel_keys<KEY, kRsTile>), dim3(tiles), dim3(256), 0, lane.s, n, inv, flag_slot, C,
+                       e->d_state, dx, dy, dz, keys, lane.b.vsel, tiles, hist);
 }
 
 // ---- option "voxel_any_order" = 1: the order libstdc++'s std::sort leaves (fdm_introsort.hpp) ----
@@ -135,53 +150,47 @@ size_t is_layout(uintptr_t base, size_t cap, IsBufs<KEY>* B) {
   B->cap_tiles = unsigned(ct);
   return off;
 }
-int ensure_introsort_buffers(fdm_engine* e, size_t n) {
-  if (n <= e->is_cap) return FDM_OK;
+int ensure_introsort_buffers(fdm_engine* e, RayBank& b, size_t n) {
+  if (n <= b.is_cap) return FDM_OK;
   if (int rc_sync = sync_all(e)) return rc_sync;
-  if (e->is_buf) HIPCK(hipFree(e->is_buf));
-  e->is_buf = nullptr;
+  if (b.is_buf) HIPCK(hipFree(b.is_buf));
+  b.is_buf = nullptr;
   const size_t cap = n + n / 4u + 1024u;
   IsBufs<unsigned long long> B{};  // (the 64-bit layout is the larger one)
-  HIPCK(hipMalloc(&e->is_buf, is_layout(uintptr_t(0), cap, &B)));
-  e->is_cap = cap;
+  HIPCK(hipMalloc(&b.is_buf, is_layout(uintptr_t(0), cap, &B)));
+  b.is_cap = cap;
   return FDM_OK;
 }
 // (key, position) of the n pairs in vkeys[0] (k_voxel_keys' output) -> vkeys[1] / vidx[1] in std::sort's order, the
 // dropped points behind the valid ones
 template <typename KEY>
-int enqueue_introsort(fdm_engine* e, unsigned n) {
-  if (int rc = ensure_introsort_buffers(e, n)) return rc;
+int enqueue_introsort(const RayLane& lane, unsigned n) {
   IsBufs<KEY> B{};
-  is_layout(reinterpret_cast<uintptr_t>(e->is_buf), e->is_cap, &B);
-  B.okey = reinterpret_cast<KEY*>(e->vkeys[1]);
-  B.oidx = e->vidx[1];
-  const KEY* keys = reinterpret_cast<const KEY*>(e->vkeys[0]);
+  is_layout(reinterpret_cast<uintptr_t>(lane.b.is_buf), lane.b.is_cap, &B);
+  B.okey = reinterpret_cast<KEY*>(lane.b.vkeys[1]);
+  B.oidx = lane.b.vidx[1];
+  const KEY* keys = reinterpret_cast<const KEY*>(lane.b.vkeys[0]);
   const unsigned ct = std::max(1u, (n + kIsTile - 1u) / kIsTile);
-  hipLaunchKernelGGL(k_is_ccount<KEY>, dim3(ct), dim3(256), 0, e->stream, n, keys, B);
-  hipLaunchKernelGGL(k_is_cscan<KEY>, dim3(1), dim3(256), 0, e->stream, ct, B);
-  hipLaunchKernelGGL(k_is_cscatter<KEY>, dim3(ct), dim3(256), 0, e->stream, n, keys, B);
+  hipLaunchKernelGGL(k_is_ccount<KEY>, dim3(ct), dim3(256), 0, lane.s, n, keys, B);
+  hipLaunchKernelGGL(k_is_cscan<KEY>, dim3(1), dim3(256), 0, lane.s, ct, B);
+  hipLaunchKernelGGL(k_is_cscatter<KEY>, dim3(ct), dim3(256), 0, lane.s, n, keys, B);
   const int levels = is_levels(n);
   const unsigned tiles = unsigned(std::min<size_t>(is_cap_tiles(n), B.cap_tiles));  // bound of a level's tiles
   for (int lv = 0; lv < levels; ++lv) {
-    hipLaunchKernelGGL(k_is_plan<KEY>, dim3(1), dim3(256), 0, e->stream, lv, B);
-    hipLaunchKernelGGL(k_is_count<KEY>, dim3(tiles), dim3(256), 0, e->stream, lv, B);
-    hipLaunchKernelGGL(k_is_scan<KEY>, dim3(1), dim3(256), 0, e->stream, lv, B);
-    hipLaunchKernelGGL(k_is_pos<KEY>, dim3(tiles), dim3(256), 0, e->stream, lv, B);
-    hipLaunchKernelGGL(k_is_scatter<KEY>, dim3(tiles), dim3(256), 0, e->stream, lv, int(lv == levels - 1), B);
+    hipLaunchKernelGGL(k_is_plan<KEY>, dim3(1), dim3(256), 0, lane.s, lv, B);
+    hipLaunchKernelGGL(k_is_count<KEY>, dim3(tiles), dim3(256), 0, lane.s, lv, B);
+    hipLaunchKernelGGL(k_is_scan<KEY>, dim3(1), dim3(256), 0, lane.s, lv, B);
+    hipLaunchKernelGGL(k_is_pos<KEY>, dim3(tiles), dim3(256), 0, lane.s, lv, B);
+    hipLaunchKernelGGL(k_is_scatter<KEY>, dim3(tiles), dim3(256), 0, lane.s, lv, int(lv == levels - 1), B);
   }
   const unsigned fin_blocks = std::max(1u, std::min(2048u, n / 64u));
-  hipLaunchKernelGGL(k_is_finish<KEY>, dim3(fin_blocks), dim3(64), 0, e->stream, B);
-  if (levels > 0) hipLaunchKernelGGL(k_is_rest<KEY>, dim3(64), dim3(64), 0, e->stream, B);
+  hipLaunchKernelGGL(k_is_finish<KEY>, dim3(fin_blocks), dim3(64), 0, lane.s, B);
+  if (levels > 0) hipLaunchKernelGGL(k_is_rest<KEY>, dim3(64), dim3(64), 0, lane.s, B);
   HIPCK(hipGetLastError());
   return FDM_OK;
 }
 
-// keys -> stable sort: vkeys[1] / vidx[1] hold the voxel-ordered scan afterwards.
-// `box` (nullable): centre (3) + half extent [m] of a box that holds every finite point of the cloud, then the
-// map-frame z interval [lo, hi] they lie in (NaN, NaN if unknown);
-// with it the compact 32-bit key is used when 3 * bits <= 31.  *key_mode tells what the buffers hold:
-// 0 = sorted uint64 keys, 1 = sorted uint32 compact keys, 2 = points grouped by key bucket, unsorted (k_vs_*).
-// The compact voxel key of a scan whose points lie in `box` (see enqueue_voxel_sort): bits == 0 if the box is unknown
+// The compact voxel key of a scan whose points lie in `box` (see plan_voxel_sort): bits == 0 if the box is unknown
 // or too large for it.
 VoxelCompact voxel_compact_of(float voxel_size, const double* box) {
   const float inv = 1.0f / voxel_size;  // voxel_grid_impl.hpp:46
@@ -239,72 +248,96 @@ void ray_box_of(const fdm_engine* e, const ScanParams& P, double box[6]) {
   box[0] = P.base_x; box[1] = P.base_y; box[2] = P.base_z; box[3] = double(e->cfg.range_max); box[4] = zlo; box[5] = zhi;
 }
 
-int enqueue_voxel_sort(fdm_engine* e, unsigned n, float voxel_size, int flag_slot, const float* dx,
-                       const float* dy, const float* dz, const double* box, int* key_mode) {
-  if (int rc = ensure_voxel_buffers(e, n)) return rc;
+// How a scan's voxel filter runs, decided once per stage: ensure_voxel_sort and enqueue_voxel_sort both follow it.
+// `box` (nullable): centre (3) + half extent [m] of a box that holds every finite point of the cloud, then the
+// map-frame z interval [lo, hi] they lie in (NaN, NaN if unknown); with it the compact 32-bit key is used when
+// 3 * bits <= 31.  key_mode tells what the bank's buffers hold afterwards: 0 = sorted uint64 keys, 1 = sorted uint32
+// compact keys, 2 = points grouped by key bucket, unsorted (the sort-free filter of small scans, k_vs_*).
+struct VoxelPlan {
+  VoxelCompact C;
+  int key_bits;
+  int key_mode;
+};
+VoxelPlan plan_voxel_sort(const fdm_engine* e, unsigned n, float voxel_size, const double* box) {
+  VoxelPlan p;
+  p.C = voxel_compact_of(voxel_size, box);
+  p.key_bits = 2 * p.C.bits + p.C.zbits;
+  p.key_mode = (p.C.bits > 0 && p.key_bits <= 31) ? 1 : 0;
+  if (p.key_mode == 1 && !e->opt.voxel_any_order && e->opt.voxel_small && n <= unsigned(e->opt.voxel_small_max))
+    p.key_mode = 2;
+  return p;
+}
+
+// what enqueue_voxel_sort(plan) of n points works in
+int ensure_voxel_sort(fdm_engine* e, RayBank& b, unsigned n, const VoxelPlan& plan) {
+  if (int rc = ensure_voxel_buffers(e, b, n)) return rc;
+  if (e->opt.voxel_any_order) return ensure_introsort_buffers(e, b, n);
+  if (plan.key_mode != 2) return FDM_OK;
+  if (!e->vs_cnt) {
+    const size_t words = (size_t(1) << kVsFineBits) + kVsCoarse + 1u;
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vs_cnt), words * sizeof(uint32_t)));
+    HIPCK(hipMemsetAsync(e->vs_cnt, 0, words * sizeof(uint32_t), e->stream));
+  }
+  if (e->vs_rec_cap < n) {
+    if (int rc_sync = sync_all(e)) return rc_sync;
+    if (e->vs_rec) HIPCK(hipFree(e->vs_rec));
+    e->vs_rec = nullptr;
+    e->vs_rec_cap = std::max<size_t>(size_t(1) << 16, size_t(n) + n / 4);
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vs_rec), e->vs_rec_cap * sizeof(uint4)));
+  }
+  return FDM_OK;
+}
+
+// keys -> sort: vkeys[1] / vidx[1] of the bank hold the voxel-ordered scan afterwards (key_mode 2: see VoxelPlan)
+int enqueue_voxel_sort(fdm_engine* e, const RayLane& lane, const VoxelPlan& plan, unsigned n, float voxel_size,
+                       int flag_slot, const float* dx, const float* dy, const float* dz) {
+  RayBank& b = lane.b;
   const float inv = 1.0f / voxel_size;  // voxel_grid_impl.hpp:46
-  const VoxelCompact C = voxel_compact_of(voxel_size, box);
-  const int key_bits = 2 * C.bits + C.zbits;
-  const bool compact = C.bits > 0 && key_bits <= 31;  // true: the sorted buffer holds uint32 keys
-  *key_mode = compact ? 1 : 0;
+  const VoxelCompact& C = plan.C;
+  const bool compact = plan.key_mode != 0;  // true: uint32 keys
   if (e->opt.voxel_any_order) {  // the order std::sort leaves (fdm_introsort.hpp)
     if (compact) {
-      launch_voxel_keys<uint32_t>(e, n, inv, flag_slot, C, dx, dy, dz, reinterpret_cast<uint32_t*>(e->vkeys[0]));
-      return enqueue_introsort<uint32_t>(e, n);
+      launch_voxel_keys<uint32_t>(e, lane, n, inv, flag_slot, C, dx, dy, dz, 0);
+      return enqueue_introsort<uint32_t>(lane, n);
     }
-    launch_voxel_keys<unsigned long long>(e, n, inv, flag_slot, C, dx, dy, dz, e->vkeys[0]);
-    return enqueue_introsort<unsigned long long>(e, n);
+    launch_voxel_keys<unsigned long long>(e, lane, n, inv, flag_slot, C, dx, dy, dz, 0);
+    return enqueue_introsort<unsigned long long>(lane, n);
   }
-  if (compact && e->opt.voxel_small && n <= unsigned(e->opt.voxel_small_max)) {
+  if (plan.key_mode == 2) {
     // small scans: no sort at all (k_vs_*: fdm_raycast.hpp).  vkeys[0] = keys by point | places by point, vs_rec =
-    // {key, point, bucket start, bucket size} by position; k_vs_mark runs from enqueue_ray_stage (key_mode 2)
-    if (!e->vs_cnt) {
-      const size_t words = (size_t(1) << kVsFineBits) + kVsCoarse + 1u;
-      HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vs_cnt), words * sizeof(uint32_t)));
-      HIPCK(hipMemsetAsync(e->vs_cnt, 0, words * sizeof(uint32_t), e->stream));
-    }
+    // {key, point, bucket start, bucket size} by position; k_vs_mark runs from enqueue_ray_walk
     VoxelSmall& V = e->vs;
     // fine buckets = one (z, y) row of voxels when that fits 2^18 counters, else the key's top 18 bits
-    V.shift = unsigned(std::max(C.bits, key_bits - int(kVsFineBits)));
+    V.shift = unsigned(std::max(C.bits, plan.key_bits - int(kVsFineBits)));
     V.fine = e->vs_cnt;
     V.coarse = e->vs_cnt + (size_t(1) << kVsFineBits);
     V.total = V.coarse + kVsCoarse;
-    uint32_t* k0 = reinterpret_cast<uint32_t*>(e->vkeys[0]);
-    V.place = k0 + e->vcap;                                  // (vkeys[0] holds 2 x vcap uint32)
-    if (e->vs_rec_cap < n) {
-      if (int rc_sync = sync_all(e)) return rc_sync;
-      if (e->vs_rec) HIPCK(hipFree(e->vs_rec));
-      e->vs_rec = nullptr;
-      e->vs_rec_cap = std::max<size_t>(size_t(1) << 16, size_t(n) + n / 4);
-      HIPCK(hipMalloc(reinterpret_cast<void**>(&e->vs_rec), e->vs_rec_cap * sizeof(uint4)));
-    }
+    uint32_t* k0 = reinterpret_cast<uint32_t*>(b.vkeys[0]);
+    V.place = k0 + b.vcap;                                   // (vkeys[0] holds 2 x vcap uint32)
     V.rec = e->vs_rec;
     V.cap = unsigned(e->vs_rec_cap);
     V.ibits = 1u;
     V.dbg = (e->opt.dbg_ray >> 8) & 3;
     while ((1u << V.ibits) < n) ++V.ibits;
     const unsigned blocks = (n + 255u) / 256u;
-    hipLaunchKernelGGL(k_vs_count, dim3(blocks), dim3(256), 0, e->stream, n, inv, flag_slot, C, V, e->d_state, dx, dy,
-                       dz, k0, e->vsel);
-    hipLaunchKernelGGL(k_vs_scatter, dim3(blocks), dim3(256), 0, e->stream, n, V, k0);
+    hipLaunchKernelGGL(k_vs_count, dim3(blocks), dim3(256), 0, lane.s, n, inv, flag_slot, C, V, e->d_state, dx, dy,
+                       dz, k0, b.vsel);
+    hipLaunchKernelGGL(k_vs_scatter, dim3(blocks), dim3(256), 0, lane.s, n, V, k0);
     HIPCK(hipGetLastError());
-    *key_mode = 2;
     return FDM_OK;
   }
-  if (compact) {
-    // bits 3*bits .. 31 are zero in every valid key and one in the invalid key (all ones): sorting
-    // one bit past the fields is enough to keep the dropped points behind every voxel
-    const unsigned sort_bits = unsigned(key_bits + 1);
-    const int src = voxel_sort_source(sort_bits);
-    launch_voxel_keys<uint32_t>(e, n, inv, flag_slot, C, dx, dy, dz, reinterpret_cast<uint32_t*>(e->vkeys[src]));
-    HIPCK(hipGetLastError());
-    return enqueue_radix_sort<uint32_t>(e, n, sort_bits);
-  }
-  const unsigned sort_bits = C.bits > 0 ? unsigned(key_bits + 1) : 64u;
+  // compact keys: bits 3*bits .. 31 are zero in every valid key and one in the invalid key (all ones): sorting
+  // one bit past the fields is enough to keep the dropped points behind every voxel
+  const unsigned sort_bits = C.bits > 0 ? unsigned(plan.key_bits + 1) : 64u;
   const int src = voxel_sort_source(sort_bits);
-  launch_voxel_keys<unsigned long long>(e, n, inv, flag_slot, C, dx, dy, dz, e->vkeys[src]);
+  if (compact) {
+    launch_voxel_keys<uint32_t>(e, lane, n, inv, flag_slot, C, dx, dy, dz, src);
+    HIPCK(hipGetLastError());
+    return enqueue_radix_sort<uint32_t>(lane, n, sort_bits);
+  }
+  launch_voxel_keys<unsigned long long>(e, lane, n, inv, flag_slot, C, dx, dy, dz, src);
   HIPCK(hipGetLastError());
-  return enqueue_radix_sort<unsigned long long>(e, n, sort_bits);
+  return enqueue_radix_sort<unsigned long long>(lane, n, sort_bits);
 }
 
 fdm_raycast_config ray_config_of(const fdm_config& c) {
@@ -341,79 +374,27 @@ RayParams make_ray_params(fdm_engine* e, const fdm_raycast_config& c, const floa
   return Q;
 }
 
-// ---- two raycasting stages in flight (option "ray_overlap", large scans held back with their update) ----
-// The stage's buffers live in the engine's members; a second set is swapped in and out around the launches of a stage
-// of the other context (bank 1), so that every helper keeps working on "the" members.
-void ray_bank_swap(fdm_engine* e) {
-  fdm_engine::RayBank& b = e->ray_bank1;
-  std::swap(e->rc_cnt, b.rc_cnt); std::swap(e->rc_min, b.rc_min); std::swap(e->ray_bins, b.ray_bins);
-  std::swap(e->vkeys[0], b.vkeys[0]); std::swap(e->vkeys[1], b.vkeys[1]);
-  std::swap(e->vidx[0], b.vidx[0]); std::swap(e->vidx[1], b.vidx[1]);
-  std::swap(e->vsel, b.vsel); std::swap(e->ray_blk, b.ray_blk);
-  std::swap(e->sort_tmp, b.sort_tmp); std::swap(e->sort_tmp_bytes, b.sort_tmp_bytes);
-  std::swap(e->vcap, b.vcap);
-  std::swap(e->is_buf, b.is_buf); std::swap(e->is_cap, b.is_cap);
-}
-struct RayBankScope {  // bank `ctx` is the live one inside the scope
-  fdm_engine* e;
-  bool swapped;
-  RayBankScope(fdm_engine* e_, int ctx) : e(e_), swapped(ctx == 1) { if (swapped) ray_bank_swap(e); }
-  ~RayBankScope() { if (swapped) ray_bank_swap(e); }
-};
-int ensure_ray_streams(fdm_engine* e) {
-  if (e->ray_stream[0]) return FDM_OK;
-  for (int k = 0; k < 2; ++k) {
-    HIPCK(hipStreamCreateWithFlags(&e->ray_stream[k], hipStreamNonBlocking));
-    HIPCK(hipEventCreateWithFlags(&e->ev_ray_pre[k], hipEventDisableTiming));
-    HIPCK(hipEventCreateWithFlags(&e->ev_ray_res[k], hipEventDisableTiming));
-  }
-  HIPCK(hipEventCreateWithFlags(&e->ev_ray_bin, hipEventDisableTiming));
-  return FDM_OK;
-}
-
-// processScan + resolveGhostCells on the stream.  voxel: the points are vkeys[1]/vidx[1] runs.
-int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const float* dx, const float* dy,
-                      const float* dz, int key_mode, int phase) {
+// ---- the stage: processScan (mark, ray queue, walk), then resolveGhostCells ----
+// Everything of a stage up to the walk, in the lane's bank on the lane's stream (the bank: ensure_ray_cells and
+// ensure_voxel_buffers(Q.n) — vidx[0] doubles as the ray queue).  voxel: the points are the bank's vkeys[1] / vidx[1]
+// runs, as enqueue_voxel_sort left them (key_mode).
+int enqueue_ray_walk(fdm_engine* e, const RayLane& lane, const RayParams& Q_in, bool voxel, const float* dx,
+                     const float* dy, const float* dz, int key_mode) {
+  if (!find_layer(e, "elevation")) return FDM_OK;  // raycasting.cpp:213-216
+  RayBank& b = lane.b;
   int rc;
   RayParams Q = Q_in;
-  if ((rc = ensure_ray_cells(e))) return rc;
-  Layer* elev = find_layer(e, "elevation");
-  if (!elev) return FDM_OK;  // raycasting.cpp:213-216
-  if (phase == 2) {  // (the first part left earlier, on a ray stream: start_ray_stage_early)
-    RayLayers L{};
-    L.elevation = lptr(e, *elev);
-    L.elevation_stride = lstride(e, *elev);
-    L.logodds = find_layer(e, "_visibility_logodds")->d;
-    L.ray_min = find_layer(e, "raycasting")->d;
-    L.ghost = find_layer(e, "ghost_removal")->d;
-    L.rec = e->d_rec;
-    L.rec_floats = e->rec_floats;
-    hipLaunchKernelGGL(k_ray_resolve, dim3(unsigned((e->ncell + 255) / 256)), dim3(256), 0, e->stream, Q,
-                       e->G, e->d_state, L, e->d_layer_ptrs, e->n_layer_ptrs, e->rc_cnt, e->rc_min,
-                       unsigned(e->ncell));
-    HIPCK(hipGetLastError());
-    return FDM_OK;
-  }
-  RayLayers L{};
-  L.elevation = lptr(e, *elev);
-  L.elevation_stride = lstride(e, *elev);
-  L.logodds = find_layer(e, "_visibility_logodds")->d;
-  L.ray_min = find_layer(e, "raycasting")->d;
-  L.ghost = find_layer(e, "ghost_removal")->d;
-  L.rec = e->d_rec;
-  L.rec_floats = e->rec_floats;
   const unsigned blocks = (Q.n + 255u) / 256u;
-  if ((rc = ensure_voxel_buffers(e, Q.n))) return rc;  // vidx[0] doubles as the ray queue
-  uint32_t* ray_list = e->vidx[0];
+  uint32_t* ray_list = b.vidx[0];
   if (voxel && key_mode == 2) {
-    hipLaunchKernelGGL(k_vs_mark, dim3(blocks), dim3(256), 0, e->stream, e->vs, e->vsel);
+    hipLaunchKernelGGL(k_vs_mark, dim3(blocks), dim3(256), 0, lane.s, e->vs, b.vsel);
   } else if (voxel) {
     if (key_mode == 1)
-      hipLaunchKernelGGL(k_voxel_mark<uint32_t>, dim3(blocks), dim3(256), 0, e->stream, Q.n,
-                         reinterpret_cast<const uint32_t*>(e->vkeys[1]), e->vidx[1], e->vsel);
+      hipLaunchKernelGGL(k_voxel_mark<uint32_t>, dim3(blocks), dim3(256), 0, lane.s, Q.n,
+                         reinterpret_cast<const uint32_t*>(b.vkeys[1]), b.vidx[1], b.vsel);
     else
-      hipLaunchKernelGGL(k_voxel_mark<unsigned long long>, dim3(blocks), dim3(256), 0, e->stream, Q.n,
-                         e->vkeys[1], e->vidx[1], e->vsel);
+      hipLaunchKernelGGL(k_voxel_mark<unsigned long long>, dim3(blocks), dim3(256), 0, lane.s, Q.n,
+                         b.vkeys[1], b.vidx[1], b.vsel);
   }
   // large scans: queue bucketed by (wedge, length class) before the walk (see k_ray_compact)
   const bool large = Q.n >= unsigned(e->opt.ray_large_min);  // one lane per ray, queue bucketed by (wedge, length)
@@ -422,9 +403,9 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
   // (sector, length class) for it
   const bool wedge = sort_queue && e->opt.ray_wedge != 0;
   if (wedge) Q.by_sector = 1;
-  uint32_t* ray_key = sort_queue ? reinterpret_cast<uint32_t*>(e->vkeys[0]) : nullptr;       // vkeys hold 2 x vcap uint32
-  uint32_t* ray_rank = sort_queue ? reinterpret_cast<uint32_t*>(e->vkeys[0]) + e->vcap : nullptr;
-  uint32_t* bin_cnt = sort_queue ? e->ray_bins : nullptr;
+  uint32_t* ray_key = sort_queue ? reinterpret_cast<uint32_t*>(b.vkeys[0]) : nullptr;       // vkeys hold 2 x vcap uint32
+  uint32_t* ray_rank = sort_queue ? reinterpret_cast<uint32_t*>(b.vkeys[0]) + b.vcap : nullptr;
+  uint32_t* bin_cnt = sort_queue ? b.ray_bins : nullptr;
   if (sort_queue) {
     // points per thread of the queue builder: 8 on multi-million-point scans (the queue tail is one same-address
     // returning atomic per block), 2 below (a 272 K-point scan is 133 blocks of 2 048 points: half the chip)
@@ -433,39 +414,39 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
       constexpr unsigned kPts = decltype(PTS)::value;
       const unsigned cblocks = (Q.n + 256u * kPts - 1u) / (256u * kPts);
       if (voxel)
-        hipLaunchKernelGGL((k_ray_compact<true, int(kPts)>), dim3(cblocks), dim3(256), 0, e->stream, Q, e->G, e->d_state,
-                           dx, dy, dz, e->vsel, e->rc_cnt, ray_list, ray_key, ray_rank, bin_cnt, e->ray_blk);
+        hipLaunchKernelGGL((k_ray_compact<true, int(kPts)>), dim3(cblocks), dim3(256), 0, lane.s, Q, e->G, e->d_state,
+                           dx, dy, dz, b.vsel, b.rc_cnt, ray_list, ray_key, ray_rank, bin_cnt, b.ray_blk);
       else
-        hipLaunchKernelGGL((k_ray_compact<false, int(kPts)>), dim3(cblocks), dim3(256), 0, e->stream, Q, e->G, e->d_state,
-                           dx, dy, dz, static_cast<const uint32_t*>(nullptr), e->rc_cnt, ray_list, ray_key, ray_rank,
-                           bin_cnt, e->ray_blk);
+        hipLaunchKernelGGL((k_ray_compact<false, int(kPts)>), dim3(cblocks), dim3(256), 0, lane.s, Q, e->G, e->d_state,
+                           dx, dy, dz, static_cast<const uint32_t*>(nullptr), b.rc_cnt, ray_list, ray_key, ray_rank,
+                           bin_cnt, b.ray_blk);
       queue_blocks = cblocks;
       queue_block_points = 256u * kPts;
     };
     if (Q.n <= kRsSmallMax) compact(std::integral_constant<unsigned, 2>{});
     else compact(std::integral_constant<unsigned, 8>{});
-    uint32_t* bin_start = e->ray_bins + kRayBins;
-    uint32_t* bin_part = e->ray_bins + 2u * kRayBins;
+    uint32_t* bin_start = b.ray_bins + kRayBins;
+    uint32_t* bin_part = b.ray_bins + 2u * kRayBins;
     static_assert(kRaySectors * kRaySectorClasses == kRayScan1Threads * kRayScan1Per,
                   "k_ray_bin_scan1 scans every (sector, length class) bucket");
     if (wedge) {
-      hipLaunchKernelGGL(k_ray_bin_scan1, dim3(1), dim3(kRayScan1Threads), 0, e->stream, Q, e->G, e->d_state, bin_cnt,
+      hipLaunchKernelGGL(k_ray_bin_scan1, dim3(1), dim3(kRayScan1Threads), 0, lane.s, Q, e->G, e->d_state, bin_cnt,
                          bin_start);
     } else {
-      hipLaunchKernelGGL(k_ray_bin_sum, dim3(kRayBins / kRayBinBlock), dim3(256), 0, e->stream, Q, e->G, e->d_state,
+      hipLaunchKernelGGL(k_ray_bin_sum, dim3(kRayBins / kRayBinBlock), dim3(256), 0, lane.s, Q, e->G, e->d_state,
                          bin_cnt, bin_part);
-      hipLaunchKernelGGL(k_ray_bin_scan, dim3(kRayBins / kRayBinBlock), dim3(256), 0, e->stream, Q, e->G, e->d_state,
+      hipLaunchKernelGGL(k_ray_bin_scan, dim3(kRayBins / kRayBinBlock), dim3(256), 0, lane.s, Q, e->G, e->d_state,
                          bin_cnt, bin_part, bin_start);
     }
-    hipLaunchKernelGGL(k_ray_scatter, dim3(queue_blocks), dim3(256), 0, e->stream, Q, e->G, e->d_state, ray_list, ray_key,
-                       ray_rank, bin_start, e->ray_blk, queue_block_points, e->vidx[1]);
-    ray_list = e->vidx[1];
+    hipLaunchKernelGGL(k_ray_scatter, dim3(queue_blocks), dim3(256), 0, lane.s, Q, e->G, e->d_state, ray_list, ray_key,
+                       ray_rank, bin_start, b.ray_blk, queue_block_points, b.vidx[1]);
+    ray_list = b.vidx[1];
   } else if (voxel) {
-    hipLaunchKernelGGL((k_ray_compact<true, 1>), dim3(blocks), dim3(256), 0, e->stream, Q, e->G, e->d_state, dx,
-                       dy, dz, e->vsel, e->rc_cnt, ray_list, ray_key, ray_rank, bin_cnt, static_cast<uint32_t*>(nullptr));
+    hipLaunchKernelGGL((k_ray_compact<true, 1>), dim3(blocks), dim3(256), 0, lane.s, Q, e->G, e->d_state, dx,
+                       dy, dz, b.vsel, b.rc_cnt, ray_list, ray_key, ray_rank, bin_cnt, static_cast<uint32_t*>(nullptr));
   } else {
-    hipLaunchKernelGGL((k_ray_compact<false, 1>), dim3(blocks), dim3(256), 0, e->stream, Q, e->G, e->d_state, dx,
-                       dy, dz, static_cast<const uint32_t*>(nullptr), e->rc_cnt, ray_list, ray_key, ray_rank, bin_cnt,
+    hipLaunchKernelGGL((k_ray_compact<false, 1>), dim3(blocks), dim3(256), 0, lane.s, Q, e->G, e->d_state, dx,
+                       dy, dz, static_cast<const uint32_t*>(nullptr), b.rc_cnt, ray_list, ray_key, ray_rank, bin_cnt,
                        static_cast<uint32_t*>(nullptr));
   }
   HIPCK(hipGetLastError());
@@ -474,8 +455,8 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
   auto launch_ray = [&](auto kern, unsigned seg) {
     // upper bound of the queue: every point a ray, padded to whole wavefronts per segment
     const unsigned threads = ((Q.n + 63u) & ~63u) * seg;
-    hipLaunchKernelGGL(kern, dim3((threads + 255u) / 256u), dim3(256), 0, e->stream, Q, e->G, e->d_state, dx, dy,
-                       dz, ray_list, e->rc_min);
+    hipLaunchKernelGGL(kern, dim3((threads + 255u) / 256u), dim3(256), 0, lane.s, Q, e->G, e->d_state, dx, dy,
+                       dz, ray_list, b.rc_min);
   };
   // small scans are a few hundred wavefronts of dependent round trips: 16 / 8 lanes share a ray
   // (C2: k_ray 60 -> 25 (8) -> 16 us (16)); the point count bounds the ray count from above
@@ -488,11 +469,11 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
     // scans of that size measured 22 us against 18: every one initialises and flushes a window of its own)
     const unsigned parts = e->opt.ray_wedge_parts > 0 ? unsigned(e->opt.ray_wedge_parts)
                                                   : std::max(1u, std::min(8u, Q.n / (sectors * 8u * kRwThreads)));
-    const uint32_t* bin_start = e->ray_bins + kRayBins;
+    const uint32_t* bin_start = b.ray_bins + kRayBins;
     auto launch_wedge = [&](auto kern) -> int {
       if (int rc_lds = allow_lds(kern, lds)) return rc_lds;
-      hipLaunchKernelGGL(kern, dim3(sectors * parts), dim3(kRwThreads), lds, e->stream, Q, e->G, e->d_state, dx, dy, dz,
-                         ray_list, bin_start, e->rc_min, H, parts);
+      hipLaunchKernelGGL(kern, dim3(sectors * parts), dim3(kRwThreads), lds, lane.s, Q, e->G, e->d_state, dx, dy, dz,
+                         ray_list, bin_start, b.rc_min, H, parts);
       return FDM_OK;
     };
     const bool fwin = !(e->opt.dbg_ray & (1 << 20));  // (dbg_ray 1048576, measurement only: the integer window of round 5)
@@ -507,10 +488,27 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
     tiled ? launch_ray(k_ray<true, 1>, 1u) : launch_ray(k_ray<false, 1>, 1u);
   }
   HIPCK(hipGetLastError());
-  if (phase == 1) return FDM_OK;
-  hipLaunchKernelGGL(k_ray_resolve, dim3(unsigned((e->ncell + 255) / 256)), dim3(256), 0, e->stream, Q,
-                     e->G, e->d_state, L, e->d_layer_ptrs, e->n_layer_ptrs, e->rc_cnt, e->rc_min,
-                     unsigned(e->ncell));
+  return FDM_OK;
+}
+
+// resolveGhostCells on what a walk left in the lane's bank
+RayLayers ray_layers_of(fdm_engine* e, const Layer& elev) {
+  RayLayers L{};
+  L.elevation = lptr(e, elev);
+  L.elevation_stride = lstride(e, elev);
+  L.logodds = find_layer(e, "_visibility_logodds")->d;
+  L.ray_min = find_layer(e, "raycasting")->d;
+  L.ghost = find_layer(e, "ghost_removal")->d;
+  L.rec = e->d_rec;
+  L.rec_floats = e->rec_floats;
+  return L;
+}
+int enqueue_ray_resolve(fdm_engine* e, const RayLane& lane, const RayParams& Q) {
+  const Layer* elev = find_layer(e, "elevation");
+  if (!elev) return FDM_OK;
+  const RayLayers L = ray_layers_of(e, *elev);
+  hipLaunchKernelGGL(k_ray_resolve, dim3(unsigned((e->ncell + 255) / 256)), dim3(256), 0, lane.s, Q, e->G, e->d_state, L,
+                     e->d_layer_ptrs, e->n_layer_ptrs, lane.b.rc_cnt, lane.b.rc_min, unsigned(e->ncell));
   HIPCK(hipGetLastError());
   return FDM_OK;
 }
@@ -519,53 +517,55 @@ int enqueue_ray_stage(fdm_engine* e, const RayParams& Q_in, bool voxel, const fl
 // of the scan's preprocessed cloud, processScan, resolveGhostCells.  Everything it needs was fixed when the scan was
 // enqueued (PendingUpdate::RQ, the cloud of the scan's parity): it may run after the NEXT scan's bin half.
 // Option "ray_overlap": the part of a large scan's stage that needs the scan and the map GEOMETRY only — voxel filter,
-// ray queue, walk — is launched when the scan's bin half has been, on the ray stream of the scan's parity, with the
-// geometry derived as the update will commit it (RayParams::pre_slot).  Stages of consecutive scans then run beside
+// ray queue, walk — is launched when the scan's bin half has been, in the bank of the scan's parity on that bank's stream,
+// with the geometry derived as the update will commit it (RayParams::pre_slot).  Stages of consecutive scans then run beside
 // each other (and beside the fused launches of the main stream); k_ray_resolve stays where it was: behind the scan's
 // update, ahead of the next one, on the main stream, which waits for the early part there.
+int ensure_ray_streams(fdm_engine* e) {
+  if (e->ray_bank[0].stream) return FDM_OK;
+  for (RayBank& b : e->ray_bank) {
+    HIPCK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    HIPCK(hipEventCreateWithFlags(&b.ev_pre, hipEventDisableTiming));
+    HIPCK(hipEventCreateWithFlags(&b.ev_res, hipEventDisableTiming));
+  }
+  HIPCK(hipEventCreateWithFlags(&e->ev_ray_bin, hipEventDisableTiming));
+  return FDM_OK;
+}
 int start_ray_stage_early(fdm_engine* e, fdm_engine::PendingUpdate& u, const ScanParams& P) {
   u.ray_pre = 0;
   const bool want = e->opt.ray_overlap > 0 || (e->opt.ray_overlap < 0 && (e->sync_call || u.RQ.n >= 1000000u));
   if (!want || !u.ray || u.RQ.n < unsigned(e->opt.ray_large_min) || e->profile || !e->opt.ray_wedge) return FDM_OK;
   if (e->opt.voxel_small && !e->opt.voxel_any_order && u.RQ.n <= unsigned(e->opt.voxel_small_max))
-    return FDM_OK;  // (the sort-free filter keeps state of its own)
+    return FDM_OK;  // (the sort-free filter keeps state of its own, on the engine: main stream only)
   if (!find_layer(e, "elevation")) return FDM_OK;
   int rc;
   if ((rc = ensure_ray_streams(e))) return rc;
   const int ctx = int(P.scan_no & 1u);
-  bool fresh = false;
-  {  // allocations (they may drain the streams and, with them, flush this very scan: then the stage has run) before anything is enqueued
-    RayBankScope bank(e, ctx);
-    fresh = e->rc_cnt == nullptr || u.RQ.n > e->vcap || (e->opt.voxel_any_order && u.RQ.n > e->is_cap);
-    if ((rc = ensure_ray_cells(e)) || (rc = ensure_voxel_buffers(e, u.RQ.n))) return rc;
-    if (e->opt.voxel_any_order && (rc = ensure_introsort_buffers(e, u.RQ.n))) return rc;
-  }
+  RayBank& b = e->ray_bank[ctx];
+  const float voxel_size = static_cast<float>(e->G.res);
+  const VoxelPlan plan = plan_voxel_sort(e, u.RQ.n, voxel_size, u.ray_box);
+  // The bank first, on the main stream.  Growing it drains the streams and, with them, flushes this very scan: its
+  // stage has then run whole, in bank 0 (run_held_ray_stage), and there is nothing left to start
+  const bool fresh = !b.rc_cnt || u.RQ.n > b.vcap || (e->opt.voxel_any_order && u.RQ.n > b.is_cap);
+  if ((rc = ensure_ray_cells(e, b)) || (rc = ensure_voxel_sort(e, b, u.RQ.n, plan))) return rc;
   if (!u.ray || !e->chain) return FDM_OK;
-  hipStream_t rs = e->ray_stream[ctx];
+  const RayLane lane{b, b.stream};
   // the scan's bin half (and everything before it): marked right behind that launch (enqueue_scan) — a mark taken here
-  // would also wait for the previous scan's stage, whose resolve has been put on the main stream since
+  // would also wait for the previous scan's stage, whose resolve has been put on the main stream since.  A fresh bank's
+  // fills are on the main stream behind that mark: a new one
   if (fresh || !e->ray_bin_marked) HIPCK(hipEventRecord(e->ev_ray_bin, e->stream));
-  HIPCK(hipStreamWaitEvent(rs, e->ev_ray_bin, 0));
-  if (e->ray_res_pending[ctx]) HIPCK(hipStreamWaitEvent(rs, e->ev_ray_res[ctx], 0));  // the bank's previous stage has been resolved
+  HIPCK(hipStreamWaitEvent(lane.s, e->ev_ray_bin, 0));
+  if (b.res_pending) HIPCK(hipStreamWaitEvent(lane.s, b.ev_res, 0));  // the bank's previous stage has been resolved
   RayParams Q = u.RQ;
   Q.ctx = ctx;
   Q.pre_slot = P.slot;
   Q.pre_do_move = P.do_move;
   Q.pre_gate = P.gate_on_filter;
-  hipStream_t main_stream = e->stream;
-  int key_mode = 0;
-  {
-    RayBankScope bank(e, ctx);
-    e->stream = rs;
-    rc = enqueue_voxel_sort(e, Q.n, static_cast<float>(e->G.res), Q.flag_slot, u.ray_x, u.ray_y, u.ray_z, u.ray_box, &key_mode);
-    if (!rc) rc = enqueue_ray_stage(e, Q, true, u.ray_x, u.ray_y, u.ray_z, key_mode, 1);
-    e->stream = main_stream;
-  }
-  if (rc) return rc;
-  HIPCK(hipEventRecord(e->ev_ray_pre[ctx], rs));
+  if ((rc = enqueue_voxel_sort(e, lane, plan, Q.n, voxel_size, Q.flag_slot, u.ray_x, u.ray_y, u.ray_z))) return rc;
+  if ((rc = enqueue_ray_walk(e, lane, Q, true, u.ray_x, u.ray_y, u.ray_z, plan.key_mode))) return rc;
+  HIPCK(hipEventRecord(b.ev_pre, lane.s));
   u.RQ = Q;
   u.ray_pre = 1 + ctx;
-  u.ray_key_mode = key_mode;
   return FDM_OK;
 }
 
@@ -574,30 +574,29 @@ int run_held_ray_stage(fdm_engine* e, fdm_engine::PendingUpdate& u) {
   u.ray = false;
   int rc;
   if (u.ray_pre) {  // the first part is on its way (start_ray_stage_early): wait for it here, resolve
-    const int ctx = u.ray_pre - 1;
+    RayBank& b = e->ray_bank[u.ray_pre - 1];
     u.ray_pre = 0;
-    HIPCK(hipStreamWaitEvent(e->stream, e->ev_ray_pre[ctx], 0));
-    {
-      RayBankScope bank(e, ctx);
-      rc = enqueue_ray_stage(e, u.RQ, true, u.ray_x, u.ray_y, u.ray_z, u.ray_key_mode, 2);
-    }
-    if (rc) return rc;
-    HIPCK(hipEventRecord(e->ev_ray_res[ctx], e->stream));
-    e->ray_res_pending[ctx] = true;
+    HIPCK(hipStreamWaitEvent(e->stream, b.ev_pre, 0));
+    if ((rc = enqueue_ray_resolve(e, RayLane{b, e->stream}, u.RQ))) return rc;
+    HIPCK(hipEventRecord(b.ev_res, e->stream));
+    b.res_pending = true;
     e->ray_timed = false;
     return FDM_OK;
   }
+  // the normal path: the whole stage in bank 0 on the main stream
+  const RayLane lane{e->ray_bank[0], e->stream};
+  const float voxel_size = static_cast<float>(e->G.res);
+  const VoxelPlan plan = plan_voxel_sort(e, u.RQ.n, voxel_size, u.ray_box);
+  if ((rc = ensure_ray_cells(e, lane.b)) || (rc = ensure_voxel_sort(e, lane.b, u.RQ.n, plan))) return rc;
   if (e->profile) HIPCK(hipEventRecord(e->ev_ray[0], e->stream));
-  int key_mode = 0;
-  if ((rc = enqueue_voxel_sort(e, u.RQ.n, static_cast<float>(e->G.res), u.RQ.flag_slot, u.ray_x, u.ray_y, u.ray_z,
-                               u.ray_box, &key_mode)))
-    return rc;
-  if ((rc = enqueue_ray_stage(e, u.RQ, true, u.ray_x, u.ray_y, u.ray_z, key_mode))) return rc;
-  // (option "ray_overlap": this stage ran on the main stream in bank 0.  The next early stage of context 0 may already be
-  //  waiting only for a bin half enqueued AHEAD of this stage (enqueue_scan's ev_ray_bin): it waits for this mark too)
-  if (e->ray_stream[0]) {
-    HIPCK(hipEventRecord(e->ev_ray_res[0], e->stream));
-    e->ray_res_pending[0] = true;
+  if ((rc = enqueue_voxel_sort(e, lane, plan, u.RQ.n, voxel_size, u.RQ.flag_slot, u.ray_x, u.ray_y, u.ray_z))) return rc;
+  if ((rc = enqueue_ray_walk(e, lane, u.RQ, true, u.ray_x, u.ray_y, u.ray_z, plan.key_mode))) return rc;
+  if ((rc = enqueue_ray_resolve(e, lane, u.RQ))) return rc;
+  // (option "ray_overlap": the next early stage of bank 0 may already be waiting only for a bin half enqueued AHEAD of
+  //  this stage (enqueue_scan's ev_ray_bin): it waits for this mark too)
+  if (lane.b.stream) {
+    HIPCK(hipEventRecord(lane.b.ev_res, e->stream));
+    lane.b.res_pending = true;
   }
   if (e->profile) {
     HIPCK(hipEventRecord(e->ev_ray[1], e->stream));
@@ -626,7 +625,10 @@ int fdm_engine_apply_raycasting_device(fdm_engine* e, uint64_t n, const float* d
   if ((rc = ensure_ray_layers(e))) return rc;
   if ((rc = refresh_layer_ptrs(e))) return rc;
   const RayParams Q = make_ray_params(e, c, origin, unsigned(n), int(e->scan_no & 3), -1);
-  return enqueue_ray_stage(e, Q, false, dx, dy, dz);
+  const RayLane lane{e->ray_bank[0], e->stream};
+  if ((rc = ensure_ray_cells(e, lane.b)) || (rc = ensure_voxel_buffers(e, lane.b, Q.n))) return rc;
+  if ((rc = enqueue_ray_walk(e, lane, Q, false, dx, dy, dz, 0))) return rc;
+  return enqueue_ray_resolve(e, lane, Q);
 }
 
 int fdm_engine_apply_raycasting(fdm_engine* e, uint64_t n, const float* x, const float* y,
@@ -659,13 +661,15 @@ int fdm_engine_voxel_any(fdm_engine* e, uint64_t n, const float* x, const float*
   const uint32_t* dc;
   int rc = stage_inputs(e, n, x, y, z, nullptr, nullptr, nullptr, &dx, &dy, &dz, &da, &dc, &dv);
   if (rc) return rc;
-  int key_mode = 0;  // no box: full 63-bit keys
-  if ((rc = enqueue_voxel_sort(e, unsigned(n), voxel_size, -1, dx, dy, dz, nullptr, &key_mode))) return rc;
+  const RayLane lane{e->ray_bank[0], e->stream};
+  const VoxelPlan plan = plan_voxel_sort(e, unsigned(n), voxel_size, nullptr);  // no box: full 63-bit keys
+  if ((rc = ensure_voxel_sort(e, lane.b, unsigned(n), plan))) return rc;
+  if ((rc = enqueue_voxel_sort(e, lane, plan, unsigned(n), voxel_size, -1, dx, dy, dz))) return rc;
   hipLaunchKernelGGL(k_voxel_select, dim3(unsigned((n + 255) / 256)), dim3(256), 0, e->stream, unsigned(n),
-                     e->vkeys[1], e->vidx[1], e->vsel);
+                     lane.b.vkeys[1], lane.b.vidx[1], lane.b.vsel);
   HIPCK(hipGetLastError());
   std::vector<uint32_t> h(n);
-  HIPCK(hipMemcpyAsync(h.data(), e->vsel, n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCK(hipMemcpyAsync(h.data(), lane.b.vsel, n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   if (int rc_sync = sync_all(e)) return rc_sync;
   uint64_t w = 0;
   for (uint64_t i = 0; i < n; ++i)  // order-preserving compaction = marshalling

@@ -30,6 +30,7 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 SIZE, RES = 24.0, 0.1                     # 240 x 240 cells, LOCAL map
 VOXEL_SMALL_MAX, RAY_LARGE_MIN = 4096, 20000
+GROWING = [20000, 20000, 40000, 40000, 20000, 60000, 60000]   # L scans: a bank holds n + n/4 + 1024 points
 BIG = 1000000                             # ray_overlap -1 sends enqueue-only scans from this size up early
 SENSOR_Z = 1.1
 WIDE_REPEATS = 15                         # (M L S M L) x 15: 30 normal -> early transitions, half of them at each parity
@@ -46,8 +47,8 @@ def size_of(kind, rng):
     return BIG
 
 
-def cloud(kind, rng):
-    n = size_of(kind, rng)
+def cloud(kind, rng, n=None):
+    n = size_of(kind, rng) if n is None else n
     x = rng.uniform(-11.0, 11.0, n).astype(F32)
     y = rng.uniform(-11.0, 11.0, n).astype(F32)
     z = (rng.uniform(-0.6, 0.5, n) - SENSOR_Z).astype(F32)
@@ -252,3 +253,48 @@ def test_the_stream_reaches_every_transition(overlap, lead):
     assert any(w == "flush" for g in groups for w, _ in g) and any(w == "read" for g in groups for w, _ in g)
     assert any(kind == "E" and scans[k - 1][1] == "L" and scans[k + 1][1] == "L" for k, kind, _, _ in scans)
     assert ("L", "L", 1, "early", "early") in seen or ("L", "L", 0, "early", "early") in seen or overlap < 0
+
+
+@pytest.mark.parametrize("any_order", [0, 1], ids=["stable_order", "std_sort_order"])
+def test_banks_grow_under_a_held_stage(gpu, R, any_order):
+    """Both banks are allocated (scans 0, 1) and then grown twice (scans 2, 3 and 5, 6) by start_ray_stage_early while
+    the previous scan's stage is held back with its update: the allocation drains the streams, which flushes the held
+    stage AND the scan being enqueued (run_held_ray_stage, bank 0) before anything of its early part is launched.  With
+    `voxel_any_order` 1 the bank's introsort buffer grows with it; the oracle then sorts with std::sort
+    (tests/test_voxel_order_gpu.py).  One enqueue-only call per scan, nothing waits before the layer read in the
+    middle and the end."""
+    caps = [0, 0]
+    grown = [0, 0]
+    for k, n in enumerate(GROWING):      # the stream's definition: every bank allocated once, grown twice
+        if n > caps[k % 2]:
+            grown[k % 2] += 1
+            caps[k % 2] = n + n // 4 + 1024
+    assert grown == [3, 3] and min(GROWING) >= RAY_LARGE_MIN > VOXEL_SMALL_MAX
+    eng, ref = make_pair(gpu, R, 1)
+    eng.set_option("voxel_any_order", any_order)
+    ref.set_voxel_stable(not any_order)
+    rng = np.random.default_rng(99 + any_order)
+    Tbs = np.eye(4)
+    Tbs[2, 3] = SENSOR_Z
+    keep, stats, cleared = [], None, 0
+    for k, n in enumerate(GROWING):
+        s = cloud("L", rng, n)
+        T = np.eye(4)
+        T[0, 3], T[1, 3] = 0.3 * k, -0.15 * k
+        stats = ref.integrate(s["x"], s["y"], s["z"], Tbs, T, intensity=s["intensity"])
+        cleared += ref.last_ray_stats()["n_cleared"]
+        b = DeviceBatch(gpu, [s], Tbs, [T])
+        keep.append(b)
+        assert eng.integrate_device_batch(b.arr) == 0, k
+        if k == 3:                       # both banks have grown once: a layer read, no sync ahead of it
+            where = f"voxel_any_order {any_order}, layer read behind scan {k}"
+            try:
+                assert_layers_bit_identical(eng, ref)
+            except AssertionError as err:
+                raise AssertionError(f"{where}: {err}") from None
+            assert same_geometry(eng.geometry(), ref.geometry()), where
+            assert eng.last_stats() == stats, (where, eng.last_stats(), stats)
+            for o in (eng, ref):
+                plant_ghosts(o, 5)
+    compare(eng, ref, f"voxel_any_order {any_order}, at the end", stats)
+    assert cleared > 0, "no ghost cell cleared behind the planted blocks"
