@@ -14,7 +14,12 @@
 
 namespace fdm {
 
-constexpr int kPackMaxFields = 64;
+constexpr int kPackMaxFields = 64;                        // float layers after x, y, z
+constexpr int kPackMaxRecord = 3 + kPackMaxFields + 1;     // x, y, z, the float layers, rgb: 68 fields, 272 B
+constexpr int kPackWriteHead = 4;                          // words of k_pack_write's LDS in front of the records
+// LDS of one k_pack_write block: 256 staged records behind the head.  Above 64 KB from 64 fields on (65 552 B;
+// 69 648 B at kPackMaxRecord), which the launch has to be granted first (fdmh::allow_lds).
+constexpr unsigned pack_write_lds_bytes(unsigned n_fields) { return (kPackWriteHead + 256u * n_fields) * 4u; }
 
 struct PackParams {
   int sub_r0, sub_c0, sub_rows, sub_cols;  // buffer indices; sub_rows < 0: the whole map from the start index
@@ -119,7 +124,11 @@ inline __global__ __launch_bounds__(256) void k_pack_write(const PackParams Q, c
                                                     const DevState* __restrict__ st, const PackLayers L,
                                                     const uint32_t* __restrict__ offsets,
                                                     float* __restrict__ out) {
-  __shared__ unsigned s_w[4];
+  // all of the kernel's LDS is the dynamic buffer (pack_write_lds_bytes): the four wave counts, then the records.
+  // No static LDS, so the size the host grants is the size the kernel has.
+  extern __shared__ float s_dyn[];
+  unsigned* s_w = reinterpret_cast<unsigned*>(s_dyn);
+  float* s_rec = s_dyn + kPackWriteHead;
   const DevGeom g = st->geom[Q.slot];
   const unsigned long long t = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
   const PackCell pc = pack_cell(Q, G, g, L, t, pack_total(Q, G));
@@ -128,7 +137,6 @@ inline __global__ __launch_bounds__(256) void k_pack_write(const PackParams Q, c
   if (lane == 0) s_w[w] = unsigned(__popcll(m));
   __syncthreads();
   // records are staged in LDS (rank-major) and leave as one contiguous, fully coalesced run
-  extern __shared__ float s_rec[];
   const int nf = 3 + Q.n_float + (Q.has_color ? 1 : 0);
   if (pc.valid) {
     unsigned rank = unsigned(__popcll(m & ((1ull << lane) - 1ull)));

@@ -92,7 +92,7 @@ int add_layer(fdm_engine* e, const char* name, float value, bool pending) {
     l->pending = l->pending && pending;
     return fill_async(e, lptr(e, *l), value, e->ncell, lstride(e, *l));
   }
-  if (e->layers.size() >= size_t(kMaxLayers)) return fail(FDM_ERR_INVALID, "too many layers (max 64)");
+  if (e->layers.size() >= size_t(kMaxLayers)) return fail(FDM_ERR_INVALID, "too many layers (max 128)");
   Layer l;
   l.name = name;
   l.pending = pending;

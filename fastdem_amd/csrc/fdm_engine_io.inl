@@ -239,7 +239,9 @@ int pack_write(fdm_engine* e, const PackPlan& pl, uint64_t n_points) {
     HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_pack), e->pack_cap * sizeof(float)));
   }
   if (n_points == 0) return FDM_OK;
-  const size_t lds = 256 * pl.fields.size() * sizeof(float);  // <= 256 * 68 * 4 = 68 KB of the CU's 160 KB
+  // the kernel's whole LDS (it has no static part): up to 69 648 B of the CU's 160 KB, above 64 KB from 64 fields on
+  const unsigned lds = pack_write_lds_bytes(unsigned(pl.fields.size()));
+  if (int rc_lds = allow_lds(k_pack_write, lds)) return rc_lds;
   hipLaunchKernelGGL(k_pack_write, dim3(pl.blocks), dim3(256), lds, e->stream, pl.Q, e->G, e->d_state, pl.L,
                      e->pack_counts, e->d_pack);
   HIPCK(hipGetLastError());

@@ -34,7 +34,9 @@
 namespace fdm {
 
 
-constexpr int kMaxLayers = 64;  // layers per map
+// layers per map, the internal ones included.  Nothing is sized by it; it has to leave room for the widest record egress
+// packs (kPackMaxFields = 64 float layers + the elevation layer + color) next to an estimator's internal layers (P2: 10)
+constexpr int kMaxLayers = 128;
 constexpr int kTileShift = 8;   // k_update tile = 256 storage-linear cells
 
 // Device-resident per-cell scratch of one scan + per-tile stamps.

@@ -447,12 +447,16 @@ class Engine:
         return FdmCloud2Layout(int(point_step), int(x), int(y), int(z), int(intensity),
                                int(intensity_type), int(rgb))
 
-    def ingest_cloud2(self, blob, n_points, layout):
-        """nanopcl::from(PointCloud2): decode a host byte blob into SoA channels in HBM.
-        Returns dict of numpy copies of the kept points' channels (for tests)."""
-        b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8))
+    def ingest_cloud2(self, blob, n_points, layout, on_device_ptr=None):
+        """nanopcl::from(PointCloud2): decode a host byte blob (or one already in HBM, `on_device_ptr`) into SoA
+        channels in HBM.  Returns dict of numpy copies of the kept points' channels (for tests)."""
         n = C.c_uint64(0)
-        _ck(self._lib.fdm_engine_ingest_cloud2(self._h, _ptr(b), 0, int(n_points), C.byref(layout),
+        if on_device_ptr is not None:
+            data, dev = C.c_void_p(on_device_ptr), 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8))
+            data, dev = _ptr(b), 0
+        _ck(self._lib.fdm_engine_ingest_cloud2(self._h, data, dev, int(n_points), C.byref(layout),
                                                C.byref(n)))
         ptrs = [C.c_void_p() for _ in range(5)]
         m = C.c_uint64(0)
@@ -488,14 +492,15 @@ class Engine:
         return rc, st.as_dict()
 
     # -- egress --
-    def pack_cloud(self, elevation_layer="elevation", sub=None):
-        """toPointCloud2Impl on the device: (fields, point_step, data[n_points, n_fields] float32)."""
+    def pack_cloud(self, elevation_layer="elevation", sub=None, names_cap=4096):
+        """toPointCloud2Impl on the device: (fields, point_step, data[n_points, n_fields] float32).
+        names_cap: bytes of the buffer the field names are received in."""
         r0, c0, nr, nc = sub if sub is not None else (0, 0, -1, -1)
         n, step = C.c_uint64(0), C.c_uint32(0)
-        names = C.create_string_buffer(4096)
+        names = C.create_string_buffer(names_cap)
         name = elevation_layer.encode()
         _ck(self._lib.fdm_engine_pack_cloud(self._h, name, r0, c0, nr, nc, None, 0, C.byref(n),
-                                            C.byref(step), names, 4096))
+                                            C.byref(step), names, names_cap))
         fields = names.value.decode().split("\n")
         data = np.empty((n.value, len(fields)), dtype=np.float32)
         if n.value:

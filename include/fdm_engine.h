@@ -243,7 +243,9 @@ int fdm_engine_get_geometry(fdm_engine* e, fdm_geometry* out);       /* getPosit
 int fdm_engine_set_position(fdm_engine* e, double x, double y);      /* GridMap::setPosition */
 int fdm_engine_set_start_index(fdm_engine* e, int32_t row, int32_t col);
 
-/* GridMap::getLayers / exists / add / get / clear / clearAll (FastDEM::reset = clear(NULL)). */
+/* GridMap::getLayers / exists / add / get / clear / clearAll (FastDEM::reset = clear(NULL)).
+ * A map holds at most 128 layers, the estimator's own among them; adding one more is FDM_ERR_INVALID
+ * (the reference has no such bound). */
 int fdm_engine_num_layers(fdm_engine* e);
 const char* fdm_engine_layer_name(fdm_engine* e, int i);
 int fdm_engine_layer_exists(fdm_engine* e, const char* name);
@@ -371,7 +373,9 @@ int fdm_engine_last_ray_ms(fdm_engine* e, float* ms);
  * with a finite `elevation_layer` value, in the reference's visiting order (column by column through
  * the submap, starting at sub_start), each record = x, y, z, every non-internal layer (name not
  * starting with '_', elevation_map.hpp:42-45) in getLayers() order, then the packed colour as `rgb`.
- * All fields are 4 bytes (FLOAT32): point_step = 4 * n_fields.
+ * All fields are 4 bytes (FLOAT32): point_step = 4 * n_fields.  A record holds at most 64 float layers besides
+ * x, y, z and rgb (67 fields, 68 with a `color` layer: point_step <= 272); a map with more visible layers is
+ * refused with FDM_ERR_INVALID before anything is written (the reference has no such bound).
  *   sub_rows < 0 : the whole map (sub_start = start index, sub_size = size), impl.hpp:160-166
  *   fields_buf   : receives the field names separated by '\n' (nullable)
  *   host_out     : receives n_points * point_step bytes when cap_bytes allows; pass NULL (or a
