@@ -329,25 +329,24 @@ void sensor_params(const fdm_config& cfg, int& type, float* sp) {
   }
 }
 
-int ensure_stage(fdm_engine* e, size_t n);
-
-// One scan = k_bin + k_update on the stream.  All pointers are device pointers.
-// `gather` (nullable): where the UPDATE kernel reads the winning points from.  Set when dx..dvar are
-// pinned host arrays seen through PCIe: the bin kernel then writes the scan through to these HBM
-// arrays as it reads it (Scratch::wt_x), so the scan crosses the link exactly once and no copy is
-// queued.  Null: the update gathers from dx..dvar themselves.
-int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, const float* dy,
-                 const float* dz, const float* dint, const uint32_t* drgb, const float* dvar,
-                 const ScanInputs* gather) {
+// One scan = k_bin + k_update on the stream.  `in`: the scan's channels as the bin half reads them, device pointers
+// (ScanInputs{} for a scan with no points).
+// `gather` (nullable; one whose x is null counts as none): where the UPDATE kernel reads the winning points from.  Set
+// when `in` is pinned host arrays seen through PCIe: the bin kernel then writes the scan through to these HBM arrays as
+// it reads it (Scratch::wt_x), so the scan crosses the link exactly once and no copy is queued.  None: the update
+// gathers from `in` itself, or from a staging slot taken here (below).
+// `in_engine_slot`: `in` already lies in a staging slot, which outlives the held-back update: no slot is taken here.
+int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const ScanInputs& in, const ScanInputs* gather,
+                 bool in_engine_slot) {
   if (n >= 0x7FFFFFFFull) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
   int rc;
   poll_dense_paid(e);
   P.n = uint32_t(n);
   P.scan_no = uint32_t(e->scan_no);
   P.slot = int(e->scan_no & 3);
-  P.has_intensity = dint != nullptr;
-  P.has_color = drgb != nullptr;
-  P.has_var = dvar != nullptr;
+  P.has_intensity = in.intensity != nullptr;
+  P.has_color = in.rgb != nullptr;
+  P.has_var = in.var != nullptr;
   sensor_params(e->cfg, P.sensor_type, P.sp);
   if (!e->estimator_ready) {  // a bare map: behave as if FastDEM(map) had been constructed
     if ((rc = ensure_estimator_layers(e))) return rc;
@@ -367,17 +366,6 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   e->S.cap_stride = 0;
   e->S.ras_z = nullptr;
   e->S.cap_drop_nan = ray_on ? 1 : 0;
-  e->S.wt_x = e->S.wt_y = e->S.wt_z = e->S.wt_var = nullptr;
-  e->S.wt_rgb = nullptr;
-  e->S.wt_src_var = nullptr;
-  e->S.wt_src_rgb = nullptr;
-  if (gather && n) {
-    e->S.wt_x = const_cast<float*>(gather->x);
-    e->S.wt_y = const_cast<float*>(gather->y);
-    e->S.wt_z = const_cast<float*>(gather->z);
-    if (dvar) { e->S.wt_var = const_cast<float*>(gather->var); e->S.wt_src_var = dvar; }
-    if (drgb) { e->S.wt_rgb = const_cast<uint32_t*>(gather->rgb); e->S.wt_src_rgb = drgb; }
-  }
   // (a scan with raycasting and nothing else optional is held back like a plain one: its stage runs behind its update)
   const bool ray_held = ray_on && e->opt.ray_hold && e->opt.overlap && e->key2[1] && !e->cap_pre && !e->cap_ras;
   if (ray_held && n) {
@@ -417,7 +405,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   const int parity = int(e->scan_no & 1);
   // float4 loads need 16-byte aligned channels
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  const bool aligned = al16(dx) && al16(dy) && al16(dz) && al16(dint);
+  const bool aligned = al16(in.x) && al16(in.y) && al16(in.z) && al16(in.intensity);
   // large scans: per-tile record pools (fdm_tiled.hpp); needs the cell-record layout
   // ... and a map with enough 32x32 tiles to keep the chip busy with one block per tile (configs[2], 49 tiles:
   // 31 us against 13.8 us through the per-cell scratch; configs[3], 1444 tiles: 40.7 against 51.3 us).  Measured
@@ -449,20 +437,26 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   // written through to the engine's rotating staging block by the bin kernel (12 B/point), and the update
   // gathers from that copy: the caller's arrays are free as soon as the bin kernel has run, which is the
   // ordinary stream contract.  (The tiled pipeline never looks at a scan twice.)
-  ScanInputs auto_gather{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!tiled && plain && !gather && n && !e->opt.borrow_inputs) {
-    if ((rc = ensure_stage(e, n))) return rc;
-    e->stage_rr = (e->stage_rr + 1) % kStageSlots;
-    float* base = e->d_stage + size_t(e->stage_rr) * 6 * e->stage_cap;
-    const size_t cap = e->stage_cap;
-    auto_gather = ScanInputs{base, base + cap, base + cap * 2, nullptr,
-                             reinterpret_cast<const uint32_t*>(base + cap * 4), base + cap * 5};
-    gather = &auto_gather;
-    e->S.wt_x = base;
-    e->S.wt_y = base + cap;
-    e->S.wt_z = base + cap * 2;
-    if (dvar) { e->S.wt_var = base + cap * 5; e->S.wt_src_var = dvar; }
-    if (drgb) { e->S.wt_rgb = reinterpret_cast<uint32_t*>(base + cap * 4); e->S.wt_src_rgb = drgb; }
+  if (gather && (!gather->x || !n)) gather = nullptr;
+  ScanInputs slot_gather;
+  if (!tiled && plain && !gather && n && !in_engine_slot && !e->opt.borrow_inputs) {
+    StageSlot slot;
+    if ((rc = next_stage_slot(e, n, &slot))) return rc;
+    slot_gather = slot.as_gather();
+    gather = &slot_gather;
+  }
+  // the bin kernel's write-through to the gather target, the caller's or the slot: x / y / z, and the channels that
+  // only the update consumes where the scan has them
+  e->S.wt_x = e->S.wt_y = e->S.wt_z = e->S.wt_var = nullptr;
+  e->S.wt_rgb = nullptr;
+  e->S.wt_src_var = nullptr;
+  e->S.wt_src_rgb = nullptr;
+  if (gather) {
+    e->S.wt_x = const_cast<float*>(gather->x);
+    e->S.wt_y = const_cast<float*>(gather->y);
+    e->S.wt_z = const_cast<float*>(gather->z);
+    if (in.var) { e->S.wt_var = const_cast<float*>(gather->var); e->S.wt_src_var = in.var; }
+    if (in.rgb) { e->S.wt_rgb = const_cast<uint32_t*>(gather->rgb); e->S.wt_src_rgb = in.rgb; }
   }
 
   // k_bin4 (1024-point blocks, 16 B loads) needs enough blocks to hide a block's latency chain: since k_bin folds
@@ -492,7 +486,6 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   P.drop_nonfinite = e->next_drop_nonfinite;
   e->next_drop_nonfinite = 0;
   int32_t* ids = e->want_ids ? e->d_cell_ids : nullptr;
-  const ScanInputs in_b{dx, dy, dz, dint, drgb, dvar};
   // a scan that asks for nothing optional takes the LEAN bin body (fdm_kernels.hpp)
   // (2: lean, but x / y / z written through for the held-back update's gather)
   const int lean = (ids || e->S.cap_x || P.drop_nonfinite || P.dbg_no_atomics) ? 0 : (e->S.wt_x ? 2 : 1);
@@ -511,19 +504,19 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
     P.prev_do_move = e->last_do_move;
     P.prev_gate = e->last_gate;
     e->chain = false;
-    if ((rc = launch_update_fused(e, e->pend, P, in_b, tiled ? e->pool[parity] : TilePool{}, ids, bin_blocks, bv)))
+    if ((rc = launch_update_fused(e, e->pend, P, in, tiled ? e->pool[parity] : TilePool{}, ids, bin_blocks, bv)))
       return rc;
   } else if (tiled) {
-    if ((rc = launch_tbin(e, P, in_b, e->pool[parity], ids, bin_blocks, bv))) return rc;
+    if ((rc = launch_tbin(e, P, in, e->pool[parity], ids, bin_blocks, bv))) return rc;
   } else if (use_bin4) {
     with_constants([&](auto hi, auto hc) {
       hipLaunchKernelGGL((k_bin4<hi(), hc(), 256>), dim3(bin_blocks), dim3(bin_threads), 0, e->stream, P, e->G,
-                         e->d_state, dx, dy, dz, dint, e->S, ids);
+                         e->d_state, in.x, in.y, in.z, in.intensity, e->S, ids);
     }, bv.has_int, bv.has_col);
   } else {
     auto launch_bin = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(bin_blocks), dim3(256), 0, e->stream, P, e->G, e->d_state, dx, dy,
-                         dz, dint, e->S, ids);
+      hipLaunchKernelGGL(kern, dim3(bin_blocks), dim3(256), 0, e->stream, P, e->G, e->d_state, in.x, in.y,
+                         in.z, in.intensity, e->S, ids);
     };
     with_constants([&](auto merge, auto ch) {  // ch: intensity | colour << 1, compiled in with the wavefront merge only
       if constexpr (merge()) launch_bin(k_bin<true, ch()>);
@@ -559,9 +552,9 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, cons
   u.tiled = tiled;
   u.P = P;
   u.S = e->S;
-  u.in = (gather && n) ? ScanInputs{gather->x, gather->y, gather->z, nullptr, drgb ? gather->rgb : nullptr,
-                                    dvar ? gather->var : nullptr}
-                       : in_b;
+  u.in = gather ? ScanInputs{gather->x, gather->y, gather->z, nullptr, in.rgb ? gather->rgb : nullptr,
+                             in.var ? gather->var : nullptr}
+                : in;
   u.upd_blocks = e->n_tiles;
   if (tiled) {
     u.Q = e->pool[parity];
@@ -647,15 +640,19 @@ void fill_update_params(fdm_engine* e, ScanParams& P, double rx, double ry, bool
 }
 
 
-// Staging for host-array entry points: kStageSlots rotating blocks of 6 channels.  A block is reused
-// three scans later, when the update that gathers from it (held back by at most one scan) has long
-// been launched ahead of the new copy on the same stream.
-int ensure_stage(fdm_engine* e, size_t n) {
-  if (n <= e->stage_cap) return FDM_OK;
-  if (int rc_sync = sync_all(e)) return rc_sync;
-  if (e->d_stage) HIPCK(hipFree(e->d_stage));
-  e->stage_cap = ((n + n / 4 + 1024) + 3) & ~size_t(3);  // channels stay 16-byte aligned (k_bin4's float4 loads)
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_stage), e->stage_cap * 6 * kStageSlots * sizeof(float)));
+// The engine's staging block: kStageSlots rotating slots of 6 channels (StageSlot), for the scans of the host-array
+// entry points, the de-interleaved ones of the record-layout entries and the held-back update's gather copy.  Takes the
+// next slot, grown to hold n points.  A slot is reused three scans later, when the update that gathers from it (held back
+// by at most one scan) has long been launched ahead of the new copy on the same stream.
+int next_stage_slot(fdm_engine* e, size_t n, StageSlot* s) {
+  if (n > e->stage_cap) {
+    if (int rc_sync = sync_all(e)) return rc_sync;
+    if (e->d_stage) HIPCK(hipFree(e->d_stage));
+    e->stage_cap = ((n + n / 4 + 1024) + 3) & ~size_t(3);  // channels stay 16-byte aligned (k_bin4's float4 loads)
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_stage), e->stage_cap * 6 * kStageSlots * sizeof(float)));
+  }
+  e->stage_rr = (e->stage_rr + 1) % kStageSlots;
+  *s = StageSlot{e->d_stage + size_t(e->stage_rr) * 6 * e->stage_cap, e->stage_cap};
   return FDM_OK;
 }
 
@@ -673,59 +670,50 @@ const void* pinned_alias(const void* p) {
   return a.type == hipMemoryTypeHost ? a.devicePointer : nullptr;
 }
 
-// Host SoA channels -> what the kernels read.  PINNED arrays (up to `zero_copy` points) are not copied:
-// the bin kernel reads them in place through their device-visible alias and writes them through to
-// the staging block, which is where the update kernel gathers from (*gather; see enqueue_scan) — no
-// copy commands, the scan crosses PCIe exactly once.  Anything else is copied into the staging block
-// with hipMemcpyAsync and *gather stays unset (x = null); so is everything when gather == nullptr (callers
-// whose kernels have no write-through).  Nullable channels stay null.
-int stage_inputs(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
-                 const float* a, const uint32_t* rgb, const float* v, const float** dx,
-                 const float** dy, const float** dz, const float** da, const uint32_t** drgb,
-                 const float** dv, ScanInputs* gather) {
-  int rc;
-  if ((rc = ensure_stage(e, n))) return rc;
-  e->stage_rr = (e->stage_rr + 1) % kStageSlots;
-  const size_t cap = e->stage_cap;
-  float* base = e->d_stage + size_t(e->stage_rr) * 6 * cap;
-  if (gather) *gather = ScanInputs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (gather && e->opt.zero_copy && n <= uint64_t(e->opt.zero_copy)) {
-    const float* mx = static_cast<const float*>(pinned_alias(x));
-    const float* my = mx ? static_cast<const float*>(pinned_alias(y)) : nullptr;
-    const float* mz = my ? static_cast<const float*>(pinned_alias(z)) : nullptr;
-    const float* ma = (mz && a) ? static_cast<const float*>(pinned_alias(a)) : nullptr;
-    const uint32_t* mc = (mz && rgb) ? static_cast<const uint32_t*>(pinned_alias(rgb)) : nullptr;
-    const float* mv = (mz && v) ? static_cast<const float*>(pinned_alias(v)) : nullptr;
-    if (mz && (!a || ma) && (!rgb || mc) && (!v || mv)) {
-      *dx = mx; *dy = my; *dz = mz; *da = ma; *drgb = mc; *dv = mv;
-      *gather = ScanInputs{base, base + cap, base + cap * 2, nullptr,
-                           reinterpret_cast<const uint32_t*>(base + cap * 4), base + cap * 5};
-      return FDM_OK;
-    }
-  }
-  auto up = [&](const void* src, int k) -> int {
-    HIPCK(hipMemcpyAsync(base + cap * k, src, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+// The device-visible aliases of a host scan's channels, if the scan may be read in place: at most `zero_copy` points
+// (the option is a point-count BOUND: larger clouds are staged also from pinned memory) and EVERY channel it has pinned.
+bool pinned_inputs(const fdm_engine* e, uint64_t n, const ScanInputs& host, ScanInputs* aliases) {
+  if (!e->opt.zero_copy || n > uint64_t(e->opt.zero_copy)) return false;
+  bool ok = host.x && host.y && host.z;
+  auto alias = [&ok](auto* p) {  // (after the first channel that is not pinned nothing more is looked up)
+    auto* d = (ok && p) ? static_cast<decltype(p)>(pinned_alias(p)) : nullptr;
+    ok = ok && (d || !p);
+    return d;
+  };
+  const ScanInputs a{alias(host.x), alias(host.y), alias(host.z), alias(host.intensity), alias(host.rgb), alias(host.var)};
+  if (ok) *aliases = a;
+  return ok;
+}
+
+// hipMemcpyAsync of the channels a host scan has to their places in a staging slot
+int upload_channels(fdm_engine* e, uint64_t n, const ScanInputs& host, const StageSlot& s) {
+  auto up = [&](void* dst, const void* src) -> int {
+    if (src) HIPCK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
     return FDM_OK;
   };
-  if ((rc = up(x, 0)) || (rc = up(y, 1)) || (rc = up(z, 2))) return rc;
-  *dx = base;
-  *dy = base + cap;
-  *dz = base + cap * 2;
-  *da = nullptr;
-  *drgb = nullptr;
-  *dv = nullptr;
-  if (a) {
-    if ((rc = up(a, 3))) return rc;
-    *da = base + cap * 3;
+  int rc;
+  if ((rc = up(s.x(), host.x)) || (rc = up(s.y(), host.y)) || (rc = up(s.z(), host.z)) ||
+      (rc = up(s.intensity(), host.intensity)) || (rc = up(s.rgb(), host.rgb)) || (rc = up(s.var(), host.var)))
+    return rc;
+  return FDM_OK;
+}
+
+// Host SoA channels -> *dev, what the kernels read.  A staging slot is taken either way.  PINNED arrays (pinned_inputs)
+// are not copied: *dev is their device-visible aliases, the bin kernel reads them in place and writes them through to
+// the slot, which is where the update kernel gathers from (*gather; see enqueue_scan) — no copy commands, the scan
+// crosses PCIe exactly once.  Anything else is copied into the slot with hipMemcpyAsync, *dev is the slot and *gather
+// stays unset (x = null); so is everything when gather == nullptr (callers whose kernels have no write-through).
+// Channels that `host` does not have stay null.
+int stage_inputs(fdm_engine* e, uint64_t n, const ScanInputs& host, ScanInputs* dev, ScanInputs* gather) {
+  StageSlot slot;
+  if (int rc = next_stage_slot(e, n, &slot)) return rc;
+  if (gather) *gather = ScanInputs{};
+  if (gather && pinned_inputs(e, n, host, dev)) {
+    *gather = slot.as_gather();
+    return FDM_OK;
   }
-  if (rgb) {
-    if ((rc = up(rgb, 4))) return rc;
-    *drgb = reinterpret_cast<const uint32_t*>(base + cap * 4);
-  }
-  if (v) {
-    if ((rc = up(v, 5))) return rc;
-    *dv = base + cap * 5;
-  }
+  if (int rc = upload_channels(e, n, host, slot)) return rc;
+  *dev = slot.as_inputs(host.intensity != nullptr, host.rgb != nullptr, host.var != nullptr);
   return FDM_OK;
 }
 
@@ -1105,6 +1093,17 @@ int fdm_engine_set_stream(fdm_engine* e, void* hip_stream) {
   return FDM_OK;
 }
 
+// An integrate() of an empty cloud (or of one that reached no map tile) leaves the map alone and consumes no scan slot;
+// last_stats reports SKIP_EMPTY_CLOUD.
+static int note_empty_integrate(fdm_engine* e) {
+  e->have_scan = true;
+  e->last_n = 0;
+  e->last_n_input = 0;
+  e->ingest_blocks = 0;
+  e->last_was_integrate = 1;
+  return FDM_OK;
+}
+
 int fdm_engine_integrate_device(fdm_engine* e, uint64_t n, const float* dx, const float* dy,
                                 const float* dz, const float* dint, const uint32_t* drgb,
                                 const float* dvar, const double Tbs[16], const double Twb[16]) {
@@ -1113,16 +1112,8 @@ int fdm_engine_integrate_device(fdm_engine* e, uint64_t n, const float* dx, cons
   HIPCK(hipSetDevice(e->device));
   ScanParams P;
   fill_integrate_params(e, P, Tbs, Twb);
-  if (n == 0) {  // fastdem.cpp:125-128: nothing is touched, not even the move
-    e->have_scan = true;
-    e->last_n = 0;
-    e->last_n_input = 0;
-    e->ingest_blocks = 0;
-    e->last_was_integrate = 1;
-    // consume no slot; last_stats reports SKIP_EMPTY_CLOUD
-    return FDM_OK;
-  }
-  return enqueue_scan(e, P, n, dx, dy, dz, dint, drgb, dvar);
+  if (n == 0) return note_empty_integrate(e);  // fastdem.cpp:125-128: nothing is touched, not even the move
+  return enqueue_scan(e, P, n, {dx, dy, dz, dint, drgb, dvar});
 }
 
 int fdm_engine_integrate_device_batch(fdm_engine* e, uint32_t count, const fdm_device_scan* scans) {
@@ -1161,15 +1152,9 @@ int fdm_engine_integrate_host_batch(fdm_engine* e, uint32_t count, const fdm_dev
     if (s.n == 0) continue;
     if (!s.x || !s.y || !s.z) return fail(FDM_ERR_INVALID, "null xyz");
     if (s.n >= 0x7FFFFFFFull) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
-    // (option zero_copy is a point-count BOUND, as in stage_inputs: larger clouds are staged also from pinned memory)
-    const float* mx = (e->opt.zero_copy && s.n <= uint64_t(e->opt.zero_copy)) ? static_cast<const float*>(pinned_alias(s.x)) : nullptr;
-    const float* my = mx ? static_cast<const float*>(pinned_alias(s.y)) : nullptr;
-    const float* mz = my ? static_cast<const float*>(pinned_alias(s.z)) : nullptr;
-    const float* ma = (mz && s.intensity) ? static_cast<const float*>(pinned_alias(s.intensity)) : nullptr;
-    const uint32_t* mc = (mz && s.rgb) ? static_cast<const uint32_t*>(pinned_alias(s.rgb)) : nullptr;
-    const float* mv = (mz && s.sigma_z2) ? static_cast<const float*>(pinned_alias(s.sigma_z2)) : nullptr;
-    if (mz && (!s.intensity || ma) && (!s.rgb || mc) && (!s.sigma_z2 || mv)) {
-      s.x = mx; s.y = my; s.z = mz; s.intensity = ma; s.rgb = mc; s.sigma_z2 = mv;
+    ScanInputs alias;
+    if (pinned_inputs(e, s.n, {s.x, s.y, s.z, s.intensity, s.rgb, s.sigma_z2}, &alias)) {
+      s.x = alias.x; s.y = alias.y; s.z = alias.z; s.intensity = alias.intensity; s.rgb = alias.rgb; s.sigma_z2 = alias.var;
     } else {
       stage[k] = 1;
       const size_t pad = (size_t(s.n) + 3u) & ~size_t(3);  // (every channel 16-byte aligned)
@@ -1233,15 +1218,13 @@ int fdm_engine_integrate(fdm_engine* e, uint64_t n, const float* x, const float*
   }
   if (!x || !y || !z) return fail(FDM_ERR_INVALID, "null xyz");
   HIPCK(hipSetDevice(e->device));
-  const float *dx, *dy, *dz, *da, *dv;
-  const uint32_t* dc;
-  ScanInputs gather;
-  int rc = stage_inputs(e, n, x, y, z, intensity, rgb, sigma_z2, &dx, &dy, &dz, &da, &dc, &dv, &gather);
+  ScanInputs dev, gather;
+  int rc = stage_inputs(e, n, {x, y, z, intensity, rgb, sigma_z2}, &dev, &gather);
   if (rc) return rc;
   ScanParams P;
   fill_integrate_params(e, P, Tbs, Twb);
   e->sync_call = true;  // (the flush follows at once: the scan's raycasting stage may start beside its update, "ray_overlap")
-  rc = enqueue_scan(e, P, n, dx, dy, dz, da, dc, dv, gather.x ? &gather : nullptr);
+  rc = enqueue_scan(e, P, n, dev, &gather);
   e->sync_call = false;
   if (rc) return rc;
   int status = FDM_OK;
@@ -1267,10 +1250,8 @@ int fdm_engine_integrate_points4(fdm_engine* e, uint64_t n, const float* xyz1, c
   if (reinterpret_cast<uintptr_t>(xyz1) & 15u) return fail(FDM_ERR_INVALID, "points not 16-byte aligned");
   HIPCK(hipSetDevice(e->device));
   int rc;
-  if ((rc = ensure_stage(e, n))) return rc;
-  e->stage_rr = (e->stage_rr + 1) % kStageSlots;
-  const size_t cap = e->stage_cap;
-  float* base = e->d_stage + size_t(e->stage_rr) * 6 * cap;
+  StageSlot slot;
+  if ((rc = next_stage_slot(e, n, &slot))) return rc;
   const float4* src = static_cast<const float4*>(pinned_alias(xyz1));
   if (!src) {  // pageable: one copy of the records, then the de-interleave reads HBM
     if (n > e->aos_cap) {
@@ -1283,30 +1264,18 @@ int fdm_engine_integrate_points4(fdm_engine* e, uint64_t n, const float* xyz1, c
     src = e->d_aos;
   }
   const int blocks = int(std::min<uint64_t>((n + 255) / 256, 8192));
-  hipLaunchKernelGGL(k_points4_to_soa, dim3(blocks), dim3(256), 0, e->stream, src, size_t(n), base, base + cap, base + cap * 2,
+  hipLaunchKernelGGL(k_points4_to_soa, dim3(blocks), dim3(256), 0, e->stream, src, size_t(n), slot.x(), slot.y(), slot.z(),
                      static_cast<float*>(nullptr));  // (the fourth component is the homogeneous 1: not a channel)
   HIPCK(hipGetLastError());
-  auto up = [&](const void* h, int k) -> int {
-    HIPCK(hipMemcpyAsync(base + cap * k, h, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    return FDM_OK;
-  };
-  const float* da = nullptr;
-  const uint32_t* dc = nullptr;
-  const float* dv = nullptr;
-  if (intensity) { if ((rc = up(intensity, 3))) return rc; da = base + cap * 3; }
-  if (rgb) { if ((rc = up(rgb, 4))) return rc; dc = reinterpret_cast<const uint32_t*>(base + cap * 4); }
-  if (sigma_z2) { if ((rc = up(sigma_z2, 5))) return rc; dv = base + cap * 5; }
+  if ((rc = upload_channels(e, n, {nullptr, nullptr, nullptr, intensity, rgb, sigma_z2}, slot))) return rc;
   ScanParams P;
   fill_integrate_params(e, P, Tbs, Twb);
-  // (the channels already sit in the engine's own staging slot, which stays valid until read_stats below has flushed the
-  // held-back update: the update gathers from the slot itself — without this a plain non-tiled scan took a SECOND slot
-  // and had the bin kernel write x / y / z through to it, 12 B per point for nothing: ADVICE r05)
-  const bool borrow = e->opt.borrow_inputs;
-  e->opt.borrow_inputs = true;
+  // (in_engine_slot: the channels already sit in the engine's own staging slot, which stays valid until read_stats below
+  // has flushed the held-back update: the update gathers from the slot itself — without this a plain non-tiled scan took
+  // a SECOND slot and had the bin kernel write x / y / z through to it, 12 B per point for nothing: ADVICE r05)
   e->sync_call = true;
-  rc = enqueue_scan(e, P, n, base, base + cap, base + cap * 2, da, dc, dv);
+  rc = enqueue_scan(e, P, n, slot.as_inputs(intensity != nullptr, rgb != nullptr, sigma_z2 != nullptr), nullptr, true);
   e->sync_call = false;
-  e->opt.borrow_inputs = borrow;
   if (rc) return rc;
   int status = FDM_OK;
   if ((rc = read_stats(e, out, &status))) return rc;
@@ -1320,14 +1289,12 @@ int fdm_engine_integrate_async(fdm_engine* e, uint64_t n, const float* x, const 
   if (n == 0) return fdm_engine_integrate_device(e, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, Tbs, Twb);
   if (!x || !y || !z) return fail(FDM_ERR_INVALID, "null xyz");
   HIPCK(hipSetDevice(e->device));
-  const float *dx, *dy, *dz, *da, *dv;
-  const uint32_t* dc;
-  ScanInputs gather;
-  int rc = stage_inputs(e, n, x, y, z, intensity, rgb, sigma_z2, &dx, &dy, &dz, &da, &dc, &dv, &gather);
+  ScanInputs dev, gather;
+  int rc = stage_inputs(e, n, {x, y, z, intensity, rgb, sigma_z2}, &dev, &gather);
   if (rc) return rc;
   ScanParams P;
   fill_integrate_params(e, P, Tbs, Twb);
-  return enqueue_scan(e, P, n, dx, dy, dz, da, dc, dv, gather.x ? &gather : nullptr);
+  return enqueue_scan(e, P, n, dev, &gather);
 }
 
 // ---- scan routing for spatially tiled global maps (include/fdm_engine.h) ----
@@ -1414,8 +1381,7 @@ int fdm_engine_integrate_soa4_device(fdm_engine* e, uint64_t n, const float* d_b
   fill_integrate_params(e, P, Tbs, Twb);
   P.force_inside = any_in_map ? 1 : 0;
   const size_t stride = (size_t(n) + 3u) & ~size_t(3);  // the share's channel blocks: x | y | z | intensity
-  return enqueue_scan(e, P, n, d_block, d_block + stride, d_block + 2 * stride,
-                      has_intensity ? d_block + 3 * stride : nullptr, nullptr, nullptr);
+  return enqueue_scan(e, P, n, {d_block, d_block + stride, d_block + 2 * stride, has_intensity ? d_block + 3 * stride : nullptr});
 }
 
 int fdm_engine_integrate_points4_device(fdm_engine* e, uint64_t n, const float* d_points4, int has_intensity,
@@ -1428,29 +1394,20 @@ int fdm_engine_integrate_points4_device(fdm_engine* e, uint64_t n, const float* 
   fill_integrate_params(e, P, Tbs, Twb);
   P.force_inside = any_in_map ? 1 : 0;
   if (n == 0) {
-    if (!any_in_map) {  // nothing of the scan reached any map tile: fastdem.cpp:145-161 leaves the map untouched
-      e->have_scan = true;
-      e->last_n = 0;
-      e->last_n_input = 0;
-      e->ingest_blocks = 0;
-      e->last_was_integrate = 1;
-      return FDM_OK;
-    }
+    // nothing of the scan reached any map tile: fastdem.cpp:145-161 leaves the map untouched
+    if (!any_in_map) return note_empty_integrate(e);
     // this tile saw none of the scan's points, but the scan did observe cells elsewhere: update() still runs
     // (the whole-layer obstacle clear, elevation_mapping.cpp:144-146)
-    return enqueue_scan(e, P, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return enqueue_scan(e, P, 0, ScanInputs{});
   }
-  int rc;
-  if ((rc = ensure_stage(e, n))) return rc;
-  e->stage_rr = (e->stage_rr + 1) % kStageSlots;  // (a held-back update never reads this block: see ensure_stage)
-  const size_t cap = e->stage_cap;
-  float* base = e->d_stage + size_t(e->stage_rr) * 6 * cap;
-  float* di = has_intensity ? base + cap * 3 : nullptr;
+  StageSlot slot;
+  if (int rc = next_stage_slot(e, n, &slot)) return rc;
   const int blocks = int(std::min<uint64_t>((n + 255) / 256, 8192));
   hipLaunchKernelGGL(k_points4_to_soa, dim3(blocks), dim3(256), 0, e->stream, reinterpret_cast<const float4*>(d_points4),
-                     size_t(n), base, base + cap, base + cap * 2, di);
+                     size_t(n), slot.x(), slot.y(), slot.z(), has_intensity ? slot.intensity() : nullptr);
   HIPCK(hipGetLastError());
-  return enqueue_scan(e, P, n, base, base + cap, base + cap * 2, di, nullptr, nullptr);
+  // (not in_engine_slot: a held-back update of this entry gathers from a second slot, which enqueue_scan takes)
+  return enqueue_scan(e, P, n, slot.as_inputs(has_intensity != 0, false, false));
 }
 
 int fdm_engine_update_device(fdm_engine* e, uint64_t n, const float* dx, const float* dy,
@@ -1461,7 +1418,7 @@ int fdm_engine_update_device(fdm_engine* e, uint64_t n, const float* dx, const f
   HIPCK(hipSetDevice(e->device));
   ScanParams P;
   fill_update_params(e, P, rx, ry, false);
-  return enqueue_scan(e, P, n, dx, dy, dz, dint, drgb, dvar);
+  return enqueue_scan(e, P, n, {dx, dy, dz, dint, drgb, dvar});
 }
 
 int fdm_engine_update(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
@@ -1471,15 +1428,12 @@ int fdm_engine_update(fdm_engine* e, uint64_t n, const float* x, const float* y,
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
   if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null xyz");
   HIPCK(hipSetDevice(e->device));
-  const float *dx = nullptr, *dy = nullptr, *dz = nullptr, *da = nullptr, *dv = nullptr;
-  const uint32_t* dc = nullptr;
   int rc;
-  ScanInputs gather{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (n && (rc = stage_inputs(e, n, x, y, z, intensity, rgb, z_var, &dx, &dy, &dz, &da, &dc, &dv, &gather)))
-    return rc;
+  ScanInputs dev, gather;
+  if (n && (rc = stage_inputs(e, n, {x, y, z, intensity, rgb, z_var}, &dev, &gather))) return rc;
   ScanParams P;
   fill_update_params(e, P, rx, ry, false);
-  if ((rc = enqueue_scan(e, P, n, dx, dy, dz, da, dc, dv, gather.x ? &gather : nullptr))) return rc;
+  if ((rc = enqueue_scan(e, P, n, dev, &gather))) return rc;
   int status = FDM_OK;
   if ((rc = read_stats(e, out, &status))) return rc;
   return FDM_OK;

@@ -402,16 +402,32 @@ int resolve_pending(fdm_engine* e);
 float* L(fdm_engine* e, const char* n);
 float* Lany(fdm_engine* e, const char* n, int* stride);
 void fill_integrate_params(fdm_engine* e, ScanParams& P, const double* Tbs, const double* Twb);
-int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const float* dx, const float* dy, const float* dz,
-                 const float* dint, const uint32_t* drgb, const float* dvar, const ScanInputs* gather = nullptr);
+int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const ScanInputs& in, const ScanInputs* gather = nullptr,
+                 bool in_engine_slot = false);
 int read_stats(fdm_engine* e, fdm_scan_stats* out, int* status);
-int ensure_stage(fdm_engine* e, size_t n);
 const void* pinned_alias(const void* p);
-constexpr int kStageSlots = 3;  // rotating staging blocks (see ensure_stage)
-int stage_inputs(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
-                 const float* a, const uint32_t* rgb, const float* v, const float** dx,
-                 const float** dy, const float** dz, const float** da, const uint32_t** drgb,
-                 const float** dv, ScanInputs* gather = nullptr);
+constexpr int kStageSlots = 3;  // rotating staging slots (see next_stage_slot)
+// One slot of the engine's staging block: six channels of `cap` points each, in the order x, y, z, intensity, rgb,
+// variance, at base + cap * 0..5 (cap is a multiple of 4 points: every channel starts 16-byte aligned).
+struct StageSlot {
+  float* base = nullptr;
+  size_t cap = 0;
+  float* x() const { return base; }
+  float* y() const { return base + cap; }
+  float* z() const { return base + cap * 2; }
+  float* intensity() const { return base + cap * 3; }
+  uint32_t* rgb() const { return reinterpret_cast<uint32_t*>(base + cap * 4); }
+  float* var() const { return base + cap * 5; }
+  // the slot as a scan's channels: x, y, z and those of the optional ones that it holds
+  ScanInputs as_inputs(bool has_intensity, bool has_rgb, bool has_var) const {
+    return {x(), y(), z(), has_intensity ? intensity() : nullptr, has_rgb ? rgb() : nullptr, has_var ? var() : nullptr};
+  }
+  // ... as the target of the bin kernel's write-through, which the held-back update gathers from: it never takes intensity
+  ScanInputs as_gather() const { return as_inputs(false, true, true); }
+};
+int next_stage_slot(fdm_engine* e, size_t n, StageSlot* s);
+int upload_channels(fdm_engine* e, uint64_t n, const ScanInputs& host, const StageSlot& s);
+int stage_inputs(fdm_engine* e, uint64_t n, const ScanInputs& host, ScanInputs* dev, ScanInputs* gather = nullptr);
 // the raycasting stage (fdm_engine_ray.hip), called from the scan path
 bool voxel_size_ok(float v);
 int ensure_ray_layers(fdm_engine* e);

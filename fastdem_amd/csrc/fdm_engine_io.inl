@@ -134,10 +134,8 @@ int fdm_engine_integrate_cloud2(fdm_engine* e, const void* data, int on_device, 
     }
   }
   L.aligned = L.aligned && (reinterpret_cast<uintptr_t>(blob) & 3u) == 0;
-  if ((rc = ensure_stage(e, n_points))) return rc;
-  e->stage_rr = (e->stage_rr + 1) % kStageSlots;
-  const size_t cap = e->stage_cap;
-  float* base = e->d_stage + size_t(e->stage_rr) * 6 * cap;
+  StageSlot slot;
+  if ((rc = next_stage_slot(e, n_points, &slot))) return rc;
   const unsigned blocks = unsigned((n_points + 255) / 256);
   if (size_t(blocks) + 1 > e->pack_counts_cap) {
     if (int rc_sync = sync_all(e)) return rc_sync;
@@ -146,16 +144,15 @@ int fdm_engine_integrate_cloud2(fdm_engine* e, const void* data, int on_device, 
     HIPCK(hipMalloc(reinterpret_cast<void**>(&e->pack_counts), e->pack_counts_cap * sizeof(uint32_t)));
   }
   const bool hi = lay->off_intensity >= 0, hc = lay->off_rgb >= 0;
-  float* di = hi ? base + cap * 3 : nullptr;
-  uint32_t* dc = hc ? reinterpret_cast<uint32_t*>(base + cap * 4) : nullptr;
-  hipLaunchKernelGGL(k_ingest_soa, dim3(blocks), dim3(256), 0, e->stream, blob, L, n_points, e->pack_counts, base,
-                     base + cap, base + cap * 2, di, dc);
+  hipLaunchKernelGGL(k_ingest_soa, dim3(blocks), dim3(256), 0, e->stream, blob, L, n_points, e->pack_counts, slot.x(),
+                     slot.y(), slot.z(), hi ? slot.intensity() : nullptr, hc ? slot.rgb() : nullptr);
   HIPCK(hipGetLastError());
   ScanParams P;
   fill_integrate_params(e, P, Tbs, Twb);
   e->next_drop_nonfinite = 1;
   e->sync_call = true;
-  rc = enqueue_scan(e, P, n_points, base, base + cap, base + cap * 2, di, dc, nullptr);
+  // (not in_engine_slot: a held-back update of this entry gathers from a second slot, which enqueue_scan takes)
+  rc = enqueue_scan(e, P, n_points, slot.as_inputs(hi, hc, false));
   e->sync_call = false;
   if (rc) return rc;
   e->ingest_blocks = blocks;  // read_stats sums the finite counts with the scan's other statistics

@@ -10,7 +10,7 @@ int fdm_engine_move(fdm_engine* e, double x, double y) {
   HIPCK(hipSetDevice(e->device));
   ScanParams P;
   fill_update_params(e, P, x, y, true);
-  return enqueue_scan(e, P, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return enqueue_scan(e, P, 0, ScanInputs{});
 }
 
 int fdm_engine_get_geometry(fdm_engine* e, fdm_geometry* out) {

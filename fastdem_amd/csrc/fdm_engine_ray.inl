@@ -638,11 +638,10 @@ int fdm_engine_apply_raycasting(fdm_engine* e, uint64_t n, const float* x, const
   if (!(rcfg ? rcfg->enabled : e->cfg.raycast_enabled) || n == 0) return FDM_OK;
   if (!x || !y || !z) return fail(FDM_ERR_INVALID, "null xyz");
   HIPCK(hipSetDevice(e->device));
-  const float *dx, *dy, *dz, *da, *dv;
-  const uint32_t* dc;
-  int rc = stage_inputs(e, n, x, y, z, nullptr, nullptr, nullptr, &dx, &dy, &dz, &da, &dc, &dv);
+  ScanInputs dev;
+  int rc = stage_inputs(e, n, {x, y, z}, &dev);
   if (rc) return rc;
-  if ((rc = fdm_engine_apply_raycasting_device(e, n, dx, dy, dz, origin, rcfg))) return rc;
+  if ((rc = fdm_engine_apply_raycasting_device(e, n, dev.x, dev.y, dev.z, origin, rcfg))) return rc;
   if (int rc_sync = sync_all(e)) return rc_sync;
   return FDM_OK;
 }
@@ -657,14 +656,13 @@ int fdm_engine_voxel_any(fdm_engine* e, uint64_t n, const float* x, const float*
   if (!x || !y || !z || !out_idx) return fail(FDM_ERR_INVALID, "null argument");
   if (n >= 0xFFFFFFFEull) return fail(FDM_ERR_INVALID, "point count exceeds 2^32-2");
   HIPCK(hipSetDevice(e->device));
-  const float *dx, *dy, *dz, *da, *dv;
-  const uint32_t* dc;
-  int rc = stage_inputs(e, n, x, y, z, nullptr, nullptr, nullptr, &dx, &dy, &dz, &da, &dc, &dv);
+  ScanInputs dev;
+  int rc = stage_inputs(e, n, {x, y, z}, &dev);
   if (rc) return rc;
   const RayLane lane{e->ray_bank[0], e->stream};
   const VoxelPlan plan = plan_voxel_sort(e, unsigned(n), voxel_size, nullptr);  // no box: full 63-bit keys
   if ((rc = ensure_voxel_sort(e, lane.b, unsigned(n), plan))) return rc;
-  if ((rc = enqueue_voxel_sort(e, lane, plan, unsigned(n), voxel_size, -1, dx, dy, dz))) return rc;
+  if ((rc = enqueue_voxel_sort(e, lane, plan, unsigned(n), voxel_size, -1, dev.x, dev.y, dev.z))) return rc;
   hipLaunchKernelGGL(k_voxel_select, dim3(unsigned((n + 255) / 256)), dim3(256), 0, e->stream, unsigned(n),
                      lane.b.vkeys[1], lane.b.vidx[1], lane.b.vsel);
   HIPCK(hipGetLastError());

@@ -1135,11 +1135,13 @@ inline __global__ __launch_bounds__(256) void k_collect_stats(const unsigned lon
 // t+1 (its bin).  The two halves share nothing — the scratch is double-buffered by scan parity and
 // the chained bin derives its base geometry from slot t (ScanParams::chain_prev) — so a stream of
 // small scans costs one launch and max(bin, update) per scan instead of two launches and their sum.
-struct ScanInputs {
-  const float *x, *y, *z, *intensity;
-  const uint32_t* rgb;
-  const float* var;
+struct ScanInputs {  // a scan's channels; an absent channel is null
+  const float *x = nullptr, *y = nullptr, *z = nullptr, *intensity = nullptr;
+  const uint32_t* rgb = nullptr;
+  const float* var = nullptr;
 };
+static_assert(__is_trivially_copyable(ScanInputs) && sizeof(ScanInputs) == 6 * sizeof(void*),
+              "ScanInputs is a kernel argument, passed by value: six pointers and nothing else");
 // STAMPED (stamp-gated maps) is a template parameter, not a branch on Su.dense: carrying both update bodies
 // in one kernel cost the dense configs[2] launch 4 % (14.9 -> 15.4 us).
 template <typename POLICY, bool HAS_INT, bool HAS_COL, int THREADS, bool STAMPED = false, int LEAN = 0>
