@@ -104,6 +104,10 @@ class FdmScanStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FdmRasterStats(C.Structure):  # fdm_raster_stats (include/fdm_engine.h)
+    _fields_ = [("n_points_used", C.c_uint64), ("n_cells_written", C.c_uint64)]
+
+
 class FdmRoutePlan(C.Structure):  # fdm_route_plan (include/fdm_engine.h)
     _fields_ = [("world", C.c_int32), ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("pad", C.c_int32),
                 ("row_edge", C.c_int32 * 17), ("col_edge", C.c_int32 * 17)]
@@ -121,7 +125,8 @@ class FdmDeviceScan(C.Structure):  # fdm_device_scan (include/fdm_engine.h)
 SENSOR_CONSTANT, SENSOR_LIDAR, SENSOR_RGBD = 0, 1, 2
 MODE_LOCAL, MODE_GLOBAL = 0, 1
 EST_KALMAN, EST_P2 = 0, 1
-FDM_OK, FDM_SKIP_EMPTY_CLOUD, FDM_SKIP_ALL_FILTERED = 0, 1, 2
+FDM_OK, FDM_SKIP_EMPTY_CLOUD, FDM_SKIP_ALL_FILTERED, FDM_SKIP_NO_CELL, FDM_SKIP_BUFFER_TOO_SMALL = 0, 1, 2, 3, 4
+RASTER_METHOD = {"max": 0, "min": 1, "mean": 2, "minmax": 3}        # fastdem::RasterMethod
 FDM_ERR_INVALID, FDM_ERR_HIP, FDM_ERR_NO_LAYER, FDM_ERR_NO_DEVICE = -1, -2, -3, -4
 NORMALIZE = {"min_max": 0, "percentile_1_99": 1, "fixed_range": 2}   # PngExportConfig::Normalize
 COLORMAP = {"grayscale": 0, "viridis": 1, "jet": 2}                  # PngExportConfig::Colormap
@@ -222,6 +227,17 @@ PROTOTYPES = {
     "fdm_engine_pack_cloud_device": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(_P), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint32)]),
+    "fdm_engine_from_point_cloud": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(FdmRasterStats)]),
+    "fdm_engine_from_point_cloud_device": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.c_int,
+                                                     C.POINTER(FdmRasterStats)]),
+    "fdm_engine_create_from_point_cloud": (C.c_int, [C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int,
+                                                     C.POINTER(_P), C.POINTER(FdmRasterStats)]),
+    "fdm_engine_to_point_cloud": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "fdm_engine_to_point_cloud_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                                   C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32)]),
+    "fdm_engine_last_raster_ms": (C.c_int, [_P, _F]),
     "fdm_default_image_config": (None, [C.POINTER(FdmImageConfig)]),
     "fdm_engine_render_layer": (C.c_int, [_P, C.c_char_p, C.POINTER(FdmImageConfig), _P, C.c_uint64,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F]),

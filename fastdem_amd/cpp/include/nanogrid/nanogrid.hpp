@@ -160,6 +160,18 @@ class GridMap {
     move_clear_basic_ = on;
     if (eng_) ck(fdm_engine_set_option(eng_, "move_clear_basic", on ? 1 : 0), "set_option(move_clear_basic)");
   }
+  // takes over an engine the C ABI created itself (fdm_engine_create_from_point_cloud): geometry and layers are its
+  void adoptEngine(fdm_engine* e) {
+    release();
+    eng_ = e;
+    if (!eng_) return;
+    serial_ = nextSerial();
+    fdm_geometry out{};
+    ck(fdm_engine_get_geometry(eng_, &out), "get_geometry");
+    rows_ = out.rows; cols_ = out.cols; res_ = out.resolution;
+    length_ = Length(out.length_x, out.length_y);
+    if (move_clear_basic_) setMoveClearBasic(true);
+  }
   bool hasEngine() const { return eng_ != nullptr; }
   fdm_engine* engine() const { return eng_; }
   // changes whenever the map gets another engine (setGeometry, copy or move assignment): mappers bound to the map

@@ -1060,6 +1060,11 @@ void fdm_engine_destroy(fdm_engine* e) {
   if (e->d_pack) (void)hipFree(e->d_pack);
   if (e->d_image) (void)hipFree(e->d_image);
   if (e->d_render) (void)hipFree(e->d_render);
+  for (void* p : {(void*)e->pc_keys[0], (void*)e->pc_keys[1], (void*)e->pc_idx[0], (void*)e->pc_idx[1], (void*)e->pc_hist,
+                  (void*)e->pc_stat, (void*)e->pc_in, (void*)e->pc_out})
+    if (p) (void)hipFree(p);
+  for (auto& ev : e->pc_ev)
+    if (ev) (void)hipEventDestroy(ev);
   for (RayBank& b : e->ray_bank) b.release();  // the raycasting stage's buffers, streams and events
   if (e->ev_ray_bin) (void)hipEventDestroy(e->ev_ray_bin);
   if (e->vs_cnt) (void)hipFree(e->vs_cnt);

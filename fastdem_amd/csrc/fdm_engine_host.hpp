@@ -38,6 +38,7 @@
 #include "fdm_rsort.hpp"
 #include "fdm_egress.hpp"
 #include "fdm_render.hpp"
+#include "fdm_raster.hpp"
 #include "fdm_ingest.hpp"
 #include "fdm_post.hpp"
 
@@ -382,6 +383,18 @@ struct fdm_engine {
   uint32_t* d_image = nullptr;       // RGBA8 pixels of the last render, row-major
   size_t image_cap = 0;              // in pixels
   RenderState* d_render = nullptr;   // histograms, ranks, the normalisation range
+  // static point clouds (fdm_raster.hpp, host side: fdm_engine_raster.inl); grown on demand, kept for the next call
+  uint32_t* pc_keys[2] = {nullptr, nullptr};  // (cell id, point index) pairs: the two sides of the radix sort
+  uint32_t* pc_idx[2] = {nullptr, nullptr};
+  uint32_t* pc_hist = nullptr;       // the sort's histograms
+  size_t pc_cap = 0;                 // points the pair buffers hold
+  RasterStat* pc_stat = nullptr;     // counters / flags / bounding box the kernels leave
+  float* pc_in = nullptr;            // fdm_engine_from_point_cloud: the host cloud's five channels, pc_in_cap points each
+  size_t pc_in_cap = 0;
+  float* pc_out = nullptr;           // toPointCloud's five channels, pc_out_cap points each
+  size_t pc_out_cap = 0;
+  float pc_ms[3] = {0.f, 0.f, 0.f};  // ids / grouping / walk of the last fromPointCloud (profile on)
+  hipEvent_t pc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ... and the events they are taken with (created on first use)
 };
 
 // ---- helpers shared by the library's translation units ----

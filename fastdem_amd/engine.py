@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import FdmCloud2Layout, FdmConfig, FdmGeometry, FdmScanStats, FdmTile
+from .capi import FdmCloud2Layout, FdmConfig, FdmGeometry, FdmRasterStats, FdmScanStats, FdmTile
 
 
 class EngineError(RuntimeError):
@@ -94,6 +94,14 @@ def write_png(path, rgba):
                 chunk(b"IDAT", zlib.compress(lines.tobytes(), 6)) + chunk(b"IEND", b""))
 
 
+def _is_torch(a):
+    return hasattr(a, "data_ptr")
+
+
+def _raster_method(method):
+    return capi.RASTER_METHOD[method] if isinstance(method, str) else int(method)
+
+
 class Engine:
     # engine options (fdm_engine_set_option) every new Engine receives right after creation; the GPU test
     # suite uses it to run each test on both scan pipelines (tests/conftest.py)
@@ -124,6 +132,36 @@ class Engine:
         self.s_cols = self._tile.cols if self._tile else self.cols
         for key, value in type(self).default_options.items():
             self.set_option(key, value)
+
+    @classmethod
+    def _adopt(cls, handle):
+        """An Engine over a handle the library created itself (fdm_engine_create_from_point_cloud): a map-only engine."""
+        self = cls.__new__(cls)
+        self._lib = capi.load()
+        self.cfg = capi.default_config()
+        self._tile = None
+        self._h = handle
+        try:
+            geo = self.geometry()
+            self.rows, self.cols = geo.rows, geo.cols
+            self.s_rows, self.s_cols = self.rows, self.cols
+            for key, value in cls.default_options.items():
+                self.set_option(key, value)
+        except Exception:
+            self.close()  # (the handle is this object's alone: nobody else would destroy it)
+            raise
+        return self
+
+    @classmethod
+    def create_map(cls, width, height, resolution, position=(0.0, 0.0), device=0):
+        """ElevationMap(width, height, resolution) alone (fdm_engine_create_map): the three basic layers, no estimator."""
+        g = FdmGeometry()
+        g.length_x, g.length_y = float(np.float32(width)), float(np.float32(height))
+        g.resolution = float(np.float32(resolution))
+        g.position_x, g.position_y = float(position[0]), float(position[1])
+        h = C.c_void_p()
+        _ck(capi.load().fdm_engine_create_map(C.byref(g), None, int(device), C.byref(h)))
+        return cls._adopt(h)
 
     # -- lifetime --
     def close(self):
@@ -491,6 +529,53 @@ class Engine:
             C.byref(st)))
         return rc, st.as_dict()
 
+    # -- static point clouds (fastdem/io/pcd_convert.hpp) --
+    def from_point_cloud(self, x, y, z, intensity=None, rgb=None, method="max"):
+        """fastdem::fromPointCloud(cloud, map, method): numpy arrays (staged) or torch device tensors (read in place).
+        Synchronous.  Returns (status, {"n_points_used", "n_cells_written"}); status 0 = written, 1 = empty cloud,
+        3 = no point landed in a cell (the map, its layer list included, is untouched)."""
+        st = FdmRasterStats()
+        m = _raster_method(method)
+        if _is_torch(x):
+            import torch
+            torch.cuda.current_stream().synchronize()  # the call reads the tensors at once, on the engine's stream
+            rc = _ck(self._lib.fdm_engine_from_point_cloud_device(
+                self._h, x.numel(), _dptr(x), _dptr(y), _dptr(z), _dptr(intensity), _dptr(rgb), m, C.byref(st)))
+        else:
+            x, y, z = _f32(x), _f32(y), _f32(z)
+            a, c = _f32(intensity), _u32(rgb)
+            rc = _ck(self._lib.fdm_engine_from_point_cloud(self._h, x.size, _ptr(x), _ptr(y), _ptr(z), _ptr(a), _ptr(c),
+                                                           m, C.byref(st)))
+        return rc, {"n_points_used": int(st.n_points_used), "n_cells_written": int(st.n_cells_written)}
+
+    def last_raster_ms(self):
+        """(ids, grouping, walk) device ms of the last from_point_cloud (enable_profile() first)."""
+        ms = (C.c_float * 3)()
+        _ck(self._lib.fdm_engine_last_raster_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def to_point_cloud(self):
+        """fastdem::toPointCloud(map): dict x, y, z (float32), intensity (float32 or None), rgb (uint32 0x00RRGGBB or
+        None) — one point per cell whose elevation is not NaN; a channel is None when no emitted cell has a value."""
+        n, hi, hc = C.c_uint64(0), C.c_int32(0), C.c_int32(0)
+        cap = self.rows * self.cols
+        x, y, z, a = (np.empty(cap, dtype=np.float32) for _ in range(4))
+        c = np.empty(cap, dtype=np.uint32)
+        _ck(self._lib.fdm_engine_to_point_cloud(self._h, cap, _ptr(x), _ptr(y), _ptr(z), _ptr(a), _ptr(c), C.byref(n),
+                                                C.byref(hi), C.byref(hc)))
+        k = n.value
+        return {"x": x[:k].copy(), "y": y[:k].copy(), "z": z[:k].copy(),
+                "intensity": a[:k].copy() if hi.value else None, "rgb": c[:k].copy() if hc.value else None}
+
+    def to_point_cloud_device(self):
+        """The same with the channels left in HBM until the next call: (device pointers x, y, z, intensity, rgb; count;
+        has_intensity; has_color)."""
+        ptrs = [C.c_void_p() for _ in range(5)]
+        n, hi, hc = C.c_uint64(0), C.c_int32(0), C.c_int32(0)
+        _ck(self._lib.fdm_engine_to_point_cloud_device(self._h, *[C.byref(p) for p in ptrs], C.byref(n), C.byref(hi),
+                                                       C.byref(hc)))
+        return [p.value for p in ptrs], n.value, bool(hi.value), bool(hc.value)
+
     # -- egress (SURVEY.md §8 f3) --
     def pack_cloud(self, elevation_layer="elevation", sub=None, names_cap=4096):
         """toPointCloud2Impl on the device: (fields, point_step, data[n_points, n_fields] float32).
@@ -620,3 +705,27 @@ class Engine:
         ms = (C.c_float * 2)()
         _ck(self._lib.fdm_engine_last_kernel_ms(self._h, ms))
         return float(ms[0]), float(ms[1])
+
+
+def from_point_cloud(x, y, z, resolution, intensity=None, rgb=None, method="max", device=0):
+    """fastdem::fromPointCloud(cloud, resolution, method): a map-only Engine sized to the cloud's x / y bounding box
+    (found on the device) with the cloud rasterized into it; None for an empty cloud.  numpy arrays or torch device
+    tensors.  A cloud without a finite, positive extent (every x or y NaN, an infinite coordinate) raises EngineError."""
+    lib = capi.load()
+    h, st = C.c_void_p(), FdmRasterStats()
+    m = _raster_method(method)
+    if _is_torch(x):
+        import torch
+        torch.cuda.current_stream().synchronize()
+        n, on_device = x.numel(), 1
+        args = [_dptr(v) for v in (x, y, z, intensity, rgb)]
+    else:
+        x, y, z = _f32(x), _f32(y), _f32(z)
+        keep = (x, y, z, _f32(intensity), _u32(rgb))
+        n, on_device = x.size, 0
+        args = [_ptr(v) for v in keep]
+    rc = _ck(lib.fdm_engine_create_from_point_cloud(n, *args, on_device, float(np.float32(resolution)), m, int(device),
+                                                    C.byref(h), C.byref(st)))
+    if rc != 0 or not h.value:
+        return None
+    return Engine._adopt(h)

@@ -88,6 +88,8 @@ enum {
   FDM_OK = 0,
   FDM_SKIP_EMPTY_CLOUD = 1,   /* fastdem.cpp:125-128 -> false */
   FDM_SKIP_ALL_FILTERED = 2,  /* fastdem.cpp:138     -> false */
+  FDM_SKIP_NO_CELL = 3,       /* pcd_convert.cpp:103: no point of the cloud landed in a cell */
+  FDM_SKIP_BUFFER_TOO_SMALL = 4, /* fdm_engine_to_point_cloud: the cloud has more points than the arrays hold */
   FDM_ERR_INVALID = -1,
   FDM_ERR_HIP = -2,
   FDM_ERR_NO_LAYER = -3,
@@ -480,6 +482,52 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
 int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* cfg);
 int fdm_engine_apply_feature_extraction(fdm_engine* e, float analysis_radius, int min_valid_neighbors,
                                         float step_lower_percentile, float step_upper_percentile);
+
+/* ---- static point clouds: fastdem/io/pcd_convert.hpp (src/pcd_convert.cpp:63-185, 327-373) ----
+ * No sensor model, poses or estimator: a world-frame cloud is binned into the map as it stands (position and circular
+ * start index included).  Per touched cell: elevation per `method` (0 Max, 1 Min, 2 Mean, 3 MinMax = RasterMethod),
+ * elevation_min, elevation_max, variance (Welford in fp32 over the cell's points IN INPUT ORDER, m2 / (count - 1),
+ * 0 for one point), n_points, intensity (the first value, then any strictly greater one) and color (the cell's last
+ * point, 0x00RRGGBB) when the cloud has the channel.  A point with NaN z, or for which getIndex fails (outside, NaN
+ * x / y), is skipped; an infinite z is not.  Missing layers are added in the reference's order (elevation_min,
+ * elevation_max, variance, n_points, intensity, color); untouched cells keep what they held.  Works on map-only engines
+ * and on engines with an estimator (record fields are written in place); a held-back map update is applied first.
+ * Synchronous.  Returns FDM_SKIP_EMPTY_CLOUD for n == 0 and FDM_SKIP_NO_CELL when no point lands: nothing is written and
+ * no layer is created.  FDM_ERR_INVALID: a tiled engine, n >= 2^31, an unknown method. */
+typedef struct fdm_raster_stats {
+  uint64_t n_points_used;    /* points that landed in a cell */
+  uint64_t n_cells_written;  /* cells that received at least one */
+} fdm_raster_stats;
+/* SoA host arrays (intensity / rgb = 0x00RRGGBB nullable), staged by the engine; `out` may be NULL */
+int fdm_engine_from_point_cloud(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
+                                const float* intensity, const uint32_t* rgb, int method, fdm_raster_stats* out);
+/* ... device arrays, read in place.  They must be complete when the call is made (it does not wait for other streams). */
+int fdm_engine_from_point_cloud_device(fdm_engine* e, uint64_t n, const float* dx, const float* dy, const float* dz,
+                                       const float* dintensity, const uint32_t* drgb, int method,
+                                       fdm_raster_stats* out);
+/* fromPointCloud(cloud, resolution, method): a map-only engine sized to the cloud's x / y bounding box (a min / max
+ * reduction on the device over the points whose x and y are both non-NaN), then the call above.  In fp32 as the
+ * reference: width = max_x - min_x + resolution (height likewise), position = ((min_x + max_x) / 2.0, (min_y + max_y) /
+ * 2.0).  The arrays are host (on_device 0) or device arrays.  n == 0: FDM_SKIP_EMPTY_CLOUD and *out_engine = NULL (the
+ * reference returns a map without geometry).  An extent that is not finite and positive (no point with both
+ * coordinates, an infinite coordinate) is undefined in the reference and refused here with FDM_ERR_INVALID. */
+int fdm_engine_create_from_point_cloud(uint64_t n, const void* x, const void* y, const void* z, const void* intensity,
+                                       const void* rgb, int on_device, float resolution, int method, int device,
+                                       fdm_engine** out_engine, fdm_raster_stats* out);
+/* toPointCloud(map): one point per cell whose elevation is not NaN — x, y the cell centre (fp64 from the unwrapped index,
+ * cast to float), z the elevation — in the visiting order of fdm_engine_pack_cloud over the whole map (unwrapped column by
+ * column from the start index; nanoGrid's cells() order is ASSUMED to be that).  *has_intensity / *has_color: some emitted
+ * cell holds a non-NaN intensity / colour (the reference's cloud has the channel exactly then); cells without one carry
+ * 0.  Host arrays of `cap` points each (any may be NULL): *n_points is always the cloud's size; when that is more than
+ * `cap` nothing is copied and the status is FDM_SKIP_BUFFER_TOO_SMALL. */
+int fdm_engine_to_point_cloud(fdm_engine* e, uint64_t cap, float* x, float* y, float* z, float* intensity,
+                              uint32_t* rgb, uint64_t* n_points, int32_t* has_intensity, int32_t* has_color);
+/* ... the channels stay in an engine-owned device buffer, valid until the next call of either variant */
+int fdm_engine_to_point_cloud_device(fdm_engine* e, const float** dx, const float** dy, const float** dz,
+                                     const float** dintensity, const uint32_t** drgb, uint64_t* n_points,
+                                     int32_t* has_intensity, int32_t* has_color);
+/* with fdm_engine_enable_profile on: device ms of the last fromPointCloud's cell ids, grouping (sort) and walk */
+int fdm_engine_last_raster_ms(fdm_engine* e, float* ms3);
 
 /* Pinned host memory for input clouds (the arrays fdm_engine_integrate* read in place, see
  * fdm_engine_integrate_async).  Blocks come from a process-wide pool of hipHostMalloc'ed memory in

@@ -19,6 +19,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("workload", nargs="?", default="c4")
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--cpu-iters", type=int, default=3)
+ap.add_argument("--only", default=None, choices=["raster"], help="'raster': the fromPointCloud row, and nothing else")
 a = ap.parse_args()
 wl = synth.make(a.workload)
 res = bench.Resident(wl, 0)
@@ -38,6 +39,41 @@ def timed(fn, iters):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters
 
+
+# ---- fromPointCloud: the workload's first scan as a static world-frame cloud, rasterized from device arrays onto a
+# map-only engine of the workload's size; beside it fdm_engine_integrate_device of the same cloud on the same map size ----
+def raster_row():
+    from fastdem_amd import Engine
+    s = wl.scan(0)
+    T = (wl.pose(0) @ wl.T_base_sensor).astype(np.float64)
+    p = np.stack([s["x"], s["y"], s["z"], np.ones_like(s["x"])]).astype(np.float64)
+    w = (T @ p).astype(np.float32)
+    d = [torch.from_numpy(np.ascontiguousarray(w[k])).cuda() for k in range(3)]
+    di = None if s["intensity"] is None else torch.from_numpy(s["intensity"]).cuda()
+    m = Engine.create_map(wl.width, wl.height, wl.resolution)
+    m.enable_profile()
+    rc, st = m.from_point_cloud(d[0], d[1], d[2], intensity=di, method="mean")
+    assert rc == 0, rc
+    t_call = timed(lambda: m.from_point_cloud(d[0], d[1], d[2], intensity=di, method="mean"), a.iters)
+    ids_ms, group_ms, walk_ms = m.last_raster_ms()
+    counts = m.layer("n_points")
+    res.eng.sync()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.iters):
+        res.step(0)
+    res.eng.sync()
+    t_int = (time.perf_counter() - t0) / a.iters
+    print(json.dumps({"stage": "from_point_cloud (device arrays, mean)", "workload": a.workload, "points": int(s["x"].size),
+                      "cells": m.rows * m.cols, "points_used": st["n_points_used"], "cells_written": st["n_cells_written"],
+                      "max_points_per_cell": int(counts.max()), "call_ms": round(t_call * 1e3, 4),
+                      "ids_ms": round(ids_ms, 4), "grouping_ms": round(group_ms, 4), "walk_ms": round(walk_ms, 4),
+                      "integrate_device_ms": round(t_int * 1e3, 4), "ratio": round(t_call / t_int, 2)}))
+
+
+if a.only == "raster":   # (a second 1200 x 1200 engine and 20 synchronous calls: only when asked for)
+    raster_row()
+    sys.exit(0)
 
 # ---- egress: toPointCloud2 compaction + packing, records stay in HBM ----
 d_ptr, n_pts, step = eng.pack_cloud_device()
