@@ -9,6 +9,8 @@ Layout (only what the path needs):
   cpp/         C++17 host mirror of fastdem::FastDEM / ElevationMap over the C ABI
 """
 from . import capi, synth  # noqa: F401
-from .engine import Engine, EngineError, HostArray, from_point_cloud, host_array  # noqa: F401
+from .engine import (DEMConfig, Engine, EngineError, HostArray, build_dem, from_point_cloud, host_array,  # noqa: F401
+                     sor_last_stats, statistical_outlier_removal)
 
-__all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud", "capi", "synth"]
+__all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud", "DEMConfig", "build_dem",
+           "statistical_outlier_removal", "sor_last_stats", "capi", "synth"]

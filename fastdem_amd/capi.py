@@ -108,6 +108,24 @@ class FdmRasterStats(C.Structure):  # fdm_raster_stats (include/fdm_engine.h)
     _fields_ = [("n_points_used", C.c_uint64), ("n_cells_written", C.c_uint64)]
 
 
+class FdmSorStats(C.Structure):  # fdm_sor_stats (include/fdm_engine.h)
+    _fields_ = [("n_queries", C.c_uint64), ("n_fallback", C.c_uint64), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
+                ("voxel", C.c_float), ("ms", C.c_float * 4)]
+
+
+class FdmDemConfig(C.Structure):
+    """fdm_dem_config == fastdem::DEMConfig (io/pcd_convert.hpp:28-42)."""
+
+    _fields_ = [("resolution", C.c_float), ("method", C.c_int32), ("sor_k", C.c_int32), ("sor_std_mul", C.c_float),
+                ("height_threshold", C.c_float), ("bin_size", C.c_float), ("inpaint_iterations", C.c_int32)]
+
+
+class FdmDemStats(C.Structure):  # fdm_dem_stats (include/fdm_engine.h)
+    _fields_ = [("n_input", C.c_uint64), ("n_after_sor", C.c_uint64), ("n_after_height", C.c_uint64),
+                ("n_sor_fallback", C.c_uint64), ("sor_threshold", C.c_float), ("stage_ms", C.c_float * 7),
+                ("raster", FdmRasterStats)]
+
+
 class FdmRoutePlan(C.Structure):  # fdm_route_plan (include/fdm_engine.h)
     _fields_ = [("world", C.c_int32), ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("pad", C.c_int32),
                 ("row_edge", C.c_int32 * 17), ("col_edge", C.c_int32 * 17)]
@@ -238,6 +256,14 @@ PROTOTYPES = {
                                                    C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                                    C.POINTER(C.c_int32)]),
     "fdm_engine_last_raster_ms": (C.c_int, [_P, _F]),
+    "fdm_statistical_outlier_removal": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P,
+                                                  _F, C.POINTER(C.c_uint64)]),
+    "fdm_sor_last_stats": (C.c_int, [C.POINTER(FdmSorStats)]),
+    "fdm_engine_remove_floating_points": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P,
+                                                    C.POINTER(C.c_uint64)]),
+    "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),
+    "fdm_engine_build_dem": (C.c_int, [C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(FdmDemConfig), C.c_int,
+                                       C.POINTER(_P), C.POINTER(FdmDemStats)]),
     "fdm_default_image_config": (None, [C.POINTER(FdmImageConfig)]),
     "fdm_engine_render_layer": (C.c_int, [_P, C.c_char_p, C.POINTER(FdmImageConfig), _P, C.c_uint64,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F]),
@@ -278,6 +304,12 @@ def load():
 def default_config():
     cfg = FdmConfig()
     load().fdm_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_dem_config():
+    cfg = FdmDemConfig()
+    load().fdm_default_dem_config(C.byref(cfg))
     return cfg
 
 

@@ -2,7 +2,7 @@
 // (fastdem/include/fastdem/io/pcd_convert.hpp, src/pcd_convert.cpp:63-185, 327-373), on the device: the three calls
 // forward to fdm_engine_from_point_cloud / fdm_engine_create_from_point_cloud / fdm_engine_to_point_cloud.
 // No sensor model, transforms or estimator.  The offline DEM pipeline of the same reference header (DEMConfig, buildDEM:
-// outlier removal, the per-cell histogram filter) is out of scope and deliberately NOT declared here.
+// outlier removal, the per-cell histogram filter) is NOT declared here: it lives in fastdem/io/build_dem.hpp.
 #pragma once
 #include <cstdint>
 #include <string>

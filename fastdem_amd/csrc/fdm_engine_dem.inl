@@ -1,0 +1,523 @@
+// fdm_engine_dem.inl — host side of buildDEM (pcd_convert.cpp:275-323) and of its two filter stages: statistical outlier
+// removal (fdm_knn.hpp; nanoPCL outlier_removal_impl.hpp:83-142) and floating-point removal (fdm_dem.hpp).
+// Part of fdm_engine_post.hip, behind fdm_engine_raster.inl, whose helpers it uses.  Offline calls: synchronous, scratch
+// is allocated per call and freed on return; the stages before a map exists run on the null stream.
+
+namespace {
+struct DevBuf {  // a device allocation that lives as long as its scope
+  void* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t bytes) {
+    HIPCK(hipMalloc(&p, bytes ? bytes : 4));
+    return FDM_OK;
+  }
+  template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+struct Events {
+  hipEvent_t ev[12] = {};
+  ~Events() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+  int init(int count) {
+    for (int k = 0; k < count; ++k) HIPCK(hipEventCreate(&ev[k]));
+    return FDM_OK;
+  }
+  float ms(int a, int b) const {
+    float t = 0.f;
+    return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.f;
+  }
+};
+
+// the two sides of a radix sort of n (key, index) pairs and its histograms (fdm_rsort.hpp)
+struct SortBufs {
+  DevBuf mem;
+  uint32_t* keys[2] = {nullptr, nullptr};
+  uint32_t* idx[2] = {nullptr, nullptr};
+  uint32_t* hist = nullptr;
+  int alloc(unsigned n) {
+    const size_t cap = (size_t(n) + 3) & ~size_t(3);
+    const size_t tiles = (size_t(n) + rs_tile(n) - 1) / rs_tile(n);
+    if (int rc = mem.alloc((4 * cap + 256 * tiles + 256) * sizeof(uint32_t))) return rc;
+    uint32_t* const b = mem.as<uint32_t>();
+    keys[0] = b; keys[1] = b + cap; idx[0] = b + 2 * cap; idx[1] = b + 3 * cap; hist = b + 4 * cap;
+    return FDM_OK;
+  }
+};
+// stable sort of (keys[0], idx[0] or the position) by the low `bits` bits; returns the side the result is on
+template <unsigned TILE>
+int dem_sort_t(hipStream_t s, const SortBufs& B, unsigned n, unsigned bits, bool has_idx) {
+  const unsigned tiles = (n + TILE - 1u) / TILE;
+  uint32_t* const total = B.hist + size_t(256) * tiles;
+  int src = 0;
+  for (unsigned shift = 0; shift < bits; shift += 8u, src ^= 1) {
+    hipLaunchKernelGGL((k_rs_hist<uint32_t, TILE>), dim3(tiles), dim3(256), 0, s, n, B.keys[src], shift, tiles, B.hist);
+    hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, tiles, B.hist, total);
+    if (shift || has_idx)
+      hipLaunchKernelGGL((k_rs_scatter<uint32_t, true, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, s, n, B.keys[src],
+                         B.idx[src], B.keys[src ^ 1], B.idx[src ^ 1], shift, tiles, B.hist, total);
+    else
+      hipLaunchKernelGGL((k_rs_scatter<uint32_t, false, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, s, n,
+                         B.keys[src], static_cast<const uint32_t*>(nullptr), B.keys[src ^ 1], B.idx[src ^ 1], shift,
+                         tiles, B.hist, total);
+  }
+  return src;
+}
+int dem_sort(hipStream_t s, const SortBufs& B, unsigned n, unsigned bits, bool has_idx) {
+  return rs_tile(n) == kRsTileSmall ? dem_sort_t<kRsTileSmall>(s, B, n, bits, has_idx)
+                                    : dem_sort_t<kRsTile>(s, B, n, bits, has_idx);
+}
+unsigned bits_of(uint64_t max_value) {  // bits a key of 0 .. max_value needs, at least one
+  unsigned bits = 1;
+  while (bits < 32u && (max_value >> bits) != 0u) ++bits;
+  return bits;
+}
+float unord_h(uint32_t u) {
+  const uint32_t b = u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+  float f;
+  std::memcpy(&f, &b, sizeof(f));
+  return f;
+}
+
+thread_local fdm_sor_stats g_sor_stats = {};
+
+// effective_k (outlier_removal_impl.hpp:90) or 0 where the reference returns an empty cloud (:86, :91)
+uint64_t sor_effective_k(uint64_t n, int k) {
+  if (n < 2 || k == 0) return 0;
+  return k < 0 ? n - 1 : std::min<uint64_t>(uint64_t(k), n - 1);  // (a negative int converts to a huge size_t)
+}
+
+// The column size: about `per` = max(4, k / 2) points per column were the cloud spread evenly over its x / y bounding
+// box (a real cloud is denser where it has points: more per occupied column, never fewer), and at most kKnnGridMax
+// columns per axis.  A box without area (a line of points, one point repeated) falls back to the points per length, then
+// to one column.
+KnnGrid sor_grid(float min_x, float min_y, float max_x, float max_y, uint64_t n, unsigned k) {
+  const double ex = double(max_x) - double(min_x), ey = double(max_y) - double(min_y);
+  const double per = std::max(4.0, 0.5 * double(k));
+  double h = std::sqrt(per * ex * ey / double(n));
+  if (!(h > 0.0)) h = per * std::max(ex, ey) / double(n);
+  h = std::max(h, std::max(ex, ey) / double(kKnnGridMax - 1u));
+  KnnGrid G{};
+  G.min_x = min_x;
+  G.min_y = min_y;
+  G.h = float(h);
+  G.inv_h = 1.0f / G.h;
+  if (!(G.h > 0.0f) || !std::isfinite(G.h) || !std::isfinite(G.inv_h) || !(G.inv_h > 0.0f)) { G.h = 1.0f; G.inv_h = 1.0f; }
+  // the column of the box's far corner, by the device's own arithmetic (knn_u / knn_col)
+  auto cols = [&](float mx, float mn) {
+    const float u = (mx - mn) * G.inv_h;
+    const double c = std::isfinite(u) && u > 0.0f ? std::floor(double(u)) : 0.0;
+    return int(std::min(c, double(kKnnGridMax - 1u))) + 1;
+  };
+  G.gx = cols(max_x, min_x);
+  G.gy = cols(max_y, min_y);
+  return G;
+}
+
+template <int KB>
+void sor_search(hipStream_t s, unsigned n, int k, const float4* pts, const uint32_t* start, const KnnGrid& G,
+                float* mean, uint32_t* queue, KnnStat* st) {
+  hipLaunchKernelGGL((k_knn_search<KB>), dim3((n + 255u) / 256u), dim3(256), 0, s, n, k, pts, start, G, mean, queue, st);
+}
+template <int KB>
+void sor_brute(hipStream_t s, unsigned nq, unsigned n, int k, const uint32_t* queue, const float4* pts, float* mean) {
+  hipLaunchKernelGGL((k_knn_brute<KB>), dim3(nq), dim3(kKnnBruteThreads), 0, s, queue, n, k, pts, mean);
+}
+
+// SOR of n >= 2 device points with 1 <= k <= min(64, n - 1): d_mean[n] and d_keep[n] are filled, *threshold and *n_kept
+// set, g_sor_stats left for fdm_sor_last_stats.  Synchronous on stream s.
+int sor_device(hipStream_t s, unsigned n, const float* dx, const float* dy, const float* dz, int k, float std_mul,
+               float* d_mean, uint8_t* d_keep, float* threshold, uint64_t* n_kept) {
+  g_sor_stats = fdm_sor_stats{};
+  g_sor_stats.n_queries = n;
+  Events E;
+  if (int rc = E.init(6)) return rc;
+  DevBuf b_stat;
+  if (int rc = b_stat.alloc(sizeof(KnnStat))) return rc;
+  KnnStat* const st = b_stat.as<KnnStat>();
+  const unsigned blocks = (n + 255u) / 256u;
+  HIPCK(hipEventRecord(E.ev[0], s));
+  hipLaunchKernelGGL(k_knn_init, dim3(1), dim3(64), 0, s, st);
+  hipLaunchKernelGGL(k_knn_bounds, dim3(std::min(blocks, 2048u)), dim3(256), 0, s, n, dx, dy, dz, st);
+  HIPCK(hipGetLastError());
+  KnnStat hs{};
+  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIPCK(hipStreamSynchronize(s));
+  if (hs.nonfinite)
+    return fail(FDM_ERR_INVALID, "the cloud has a coordinate that is not finite (undefined in the reference's k-d tree)");
+  const KnnGrid G = sor_grid(unord_h(hs.min_x), unord_h(hs.min_y), unord_h(hs.max_x), unord_h(hs.max_y), n, unsigned(k));
+  const unsigned ncol = unsigned(G.gx) * unsigned(G.gy);
+  g_sor_stats.grid_x = G.gx;
+  g_sor_stats.grid_y = G.gy;
+  g_sor_stats.voxel = G.h;
+  SortBufs S;
+  DevBuf b_pts, b_start, b_queue;
+  if (int rc = S.alloc(n)) return rc;
+  if (int rc = b_pts.alloc(size_t(n) * sizeof(float4))) return rc;
+  if (int rc = b_start.alloc((size_t(ncol) + 1) * sizeof(uint32_t))) return rc;
+  if (int rc = b_queue.alloc(size_t(n) * sizeof(uint32_t))) return rc;
+  hipLaunchKernelGGL(k_knn_keys, dim3(blocks), dim3(256), 0, s, n, dx, dy, G, S.keys[0]);
+  const int side = dem_sort(s, S, n, bits_of(ncol - 1u), false);
+  hipLaunchKernelGGL(k_knn_gather, dim3(blocks), dim3(256), 0, s, n, S.idx[side], dx, dy, dz, b_pts.as<float4>());
+  hipLaunchKernelGGL(k_knn_starts, dim3((ncol + 1u + 255u) / 256u), dim3(256), 0, s, n, S.keys[side], ncol,
+                     b_start.as<uint32_t>());
+  HIPCK(hipGetLastError());
+  HIPCK(hipEventRecord(E.ev[1], s));
+  const int bucket = k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
+  switch (bucket) {
+    case 4: sor_search<4>(s, n, k, b_pts.as<float4>(), b_start.as<uint32_t>(), G, d_mean, b_queue.as<uint32_t>(), st); break;
+    case 16: sor_search<16>(s, n, k, b_pts.as<float4>(), b_start.as<uint32_t>(), G, d_mean, b_queue.as<uint32_t>(), st); break;
+    case 32: sor_search<32>(s, n, k, b_pts.as<float4>(), b_start.as<uint32_t>(), G, d_mean, b_queue.as<uint32_t>(), st); break;
+    default: sor_search<64>(s, n, k, b_pts.as<float4>(), b_start.as<uint32_t>(), G, d_mean, b_queue.as<uint32_t>(), st); break;
+  }
+  HIPCK(hipGetLastError());
+  HIPCK(hipEventRecord(E.ev[2], s));
+  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIPCK(hipStreamSynchronize(s));
+  const unsigned nq = hs.n_queue;
+  if (nq > n) return fail(FDM_ERR_HIP, "k-NN queue overran the cloud");
+  g_sor_stats.n_fallback = nq;
+  if (nq) {
+    switch (bucket) {
+      case 4: sor_brute<4>(s, nq, n, k, b_queue.as<uint32_t>(), b_pts.as<float4>(), d_mean); break;
+      case 16: sor_brute<16>(s, nq, n, k, b_queue.as<uint32_t>(), b_pts.as<float4>(), d_mean); break;
+      case 32: sor_brute<32>(s, nq, n, k, b_queue.as<uint32_t>(), b_pts.as<float4>(), d_mean); break;
+      default: sor_brute<64>(s, nq, n, k, b_queue.as<uint32_t>(), b_pts.as<float4>(), d_mean); break;
+    }
+    HIPCK(hipGetLastError());
+  }
+  HIPCK(hipEventRecord(E.ev[3], s));
+  // the two global sums, fp64, in input order (outlier_removal_impl.hpp:118-129): on the host, after one download
+  std::vector<float> means(n);
+  HIPCK(hipMemcpyAsync(means.data(), d_mean, size_t(n) * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCK(hipStreamSynchronize(s));
+  double sum = 0.0;
+  for (unsigned i = 0; i < n; ++i) sum += means[i];
+  const double global_mean = sum / double(n);
+  double sum_sq_diff = 0.0;
+  for (unsigned i = 0; i < n; ++i) {
+    const double diff = means[i] - global_mean;
+    sum_sq_diff += diff * diff;
+  }
+  const float global_std = float(std::sqrt(sum_sq_diff / double(n)));
+  const float thr = float(global_mean) + std_mul * global_std;
+  hipLaunchKernelGGL(k_sor_keep, dim3(blocks), dim3(256), 0, s, n, d_mean, thr, d_keep, st);
+  HIPCK(hipGetLastError());
+  HIPCK(hipEventRecord(E.ev[4], s));
+  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIPCK(hipStreamSynchronize(s));
+  *threshold = thr;
+  *n_kept = hs.n_kept;
+  for (int q = 0; q < 4; ++q) g_sor_stats.ms[q] = E.ms(q, q + 1);
+  return FDM_OK;
+}
+
+// keep[i] of n device points on e's geometry; synchronous on e's stream
+int height_filter_device(fdm_engine* e, unsigned n, const float* dx, const float* dy, const float* dz,
+                         float height_threshold, float bin, uint8_t* d_keep, uint64_t* n_kept) {
+  int rc;
+  if ((rc = resolve_pending(e))) return rc;
+  hipStream_t s = e->stream;
+  const uint32_t ncell = uint32_t(e->ncell);
+  const unsigned blocks = (n + 255u) / 256u;
+  const int slot = int(e->scan_no & 3);
+  DevBuf b_stat, b_rstat, b_cell, b_bins, b_cmin, b_cmax;
+  SortBufs S;
+  if ((rc = b_stat.alloc(sizeof(DemStat)))) return rc;
+  if ((rc = b_rstat.alloc(sizeof(RasterStat)))) return rc;
+  if ((rc = b_cell.alloc(size_t(n) * sizeof(uint32_t)))) return rc;
+  if ((rc = b_bins.alloc(size_t(n) * sizeof(uint32_t)))) return rc;
+  if ((rc = b_cmin.alloc(size_t(ncell) * sizeof(uint32_t)))) return rc;
+  if ((rc = b_cmax.alloc(size_t(ncell) * sizeof(uint32_t)))) return rc;
+  if ((rc = S.alloc(n))) return rc;
+  DemStat* const st = b_stat.as<DemStat>();
+  uint32_t* const cell = b_cell.as<uint32_t>();
+  uint32_t* const bins = b_bins.as<uint32_t>();
+  uint32_t* const cmin = b_cmin.as<uint32_t>();
+  uint32_t* const cmax = b_cmax.as<uint32_t>();
+  const unsigned fill_blocks = unsigned(std::min<size_t>((size_t(ncell) + 255) / 256, 4096));
+  hipLaunchKernelGGL(k_dem_stat_init, dim3(1), dim3(64), 0, s, st);
+  hipLaunchKernelGGL(k_ras_stat_init, dim3(1), dim3(64), 0, s, b_rstat.as<RasterStat>());
+  hipLaunchKernelGGL(k_fill_u32, dim3(fill_blocks), dim3(256), 0, s, cmin, 0xFFFFFFFFu, size_t(ncell));
+  hipLaunchKernelGGL(k_fill_u32, dim3(fill_blocks), dim3(256), 0, s, cmax, 0u, size_t(ncell));
+  hipLaunchKernelGGL(k_ras_ids, dim3(blocks), dim3(256), 0, s, n, dx, dy, dz, e->G, e->d_state, slot, ncell, cell,
+                     b_rstat.as<RasterStat>());
+  hipLaunchKernelGGL(k_hf_minmax, dim3(blocks), dim3(256), 0, s, n, cell, dz, ncell, cmin, cmax);
+  hipLaunchKernelGGL(k_hf_bins, dim3(blocks), dim3(256), 0, s, n, cell, dz, ncell, cmin, cmax, bin, bins, st);
+  HIPCK(hipGetLastError());
+  DemStat hs{};
+  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  if ((rc = sync_all(e))) return rc;
+  if (hs.bad)
+    return fail(FDM_ERR_INVALID, "a cell's z range over the bin size does not fit an int32 (undefined in the reference)");
+  // by bin, then (stable) by cell: the pairs end up ordered by (cell, bin, index)
+  HIPCK(hipMemcpyAsync(S.keys[0], bins, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  const int side1 = dem_sort(s, S, n, bits_of(hs.max_bin), false);
+  if (side1 != 0) HIPCK(hipMemcpyAsync(S.idx[0], S.idx[side1], size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(k_dem_gather_u32, dim3(blocks), dim3(256), 0, s, n, S.idx[0], cell, S.keys[0]);
+  const int side2 = dem_sort(s, S, n, bits_of(ncell), true);
+  hipLaunchKernelGGL(k_hf_peak, dim3(blocks), dim3(256), 0, s, n, S.keys[side2], S.idx[side2], ncell, bins, cmin, bin,
+                     height_threshold, cmax);
+  hipLaunchKernelGGL(k_hf_keep, dim3(blocks), dim3(256), 0, s, n, cell, dz, ncell, cmax, d_keep, st);
+  HIPCK(hipGetLastError());
+  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  if ((rc = sync_all(e))) return rc;
+  *n_kept = hs.n_kept;
+  return FDM_OK;
+}
+
+// the kept points of five channels (ch[k] nullptr = absent) into out[k], in input order; *n_out = how many.  Synchronous.
+int compact_device(hipStream_t s, unsigned n, const uint8_t* d_keep, const float* const ch[5], float* const out[5]) {
+  const unsigned blocks = (n + 255u) / 256u;
+  DevBuf b_counts;
+  if (int rc = b_counts.alloc((size_t(blocks) + 1) * sizeof(uint32_t))) return rc;
+  DemChannels C{};
+  for (int k = 0; k < 5; ++k) { C.in[k] = ch[k]; C.out[k] = out[k]; }
+  hipLaunchKernelGGL(k_dem_count, dim3(blocks), dim3(256), 0, s, n, d_keep, b_counts.as<uint32_t>());
+  hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, s, b_counts.as<uint32_t>(), blocks);
+  hipLaunchKernelGGL(k_dem_compact, dim3(blocks), dim3(256), 0, s, n, d_keep, b_counts.as<uint32_t>(), C);
+  HIPCK(hipGetLastError());
+  HIPCK(hipStreamSynchronize(s));
+  return FDM_OK;
+}
+
+int pick_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(FDM_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(FDM_ERR_INVALID, "bad device ordinal");
+  HIPCK(hipSetDevice(device));
+  return FDM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void fdm_default_dem_config(fdm_dem_config* c) {  // DEMConfig{} (io/pcd_convert.hpp:28-42)
+  if (!c) return;
+  c->resolution = 0.1f;
+  c->method = 0;
+  c->sor_k = 10;
+  c->sor_std_mul = 1.0f;
+  c->height_threshold = 2.0f;
+  c->bin_size = 0.0f;
+  c->inpaint_iterations = 3;
+}
+
+int fdm_sor_last_stats(fdm_sor_stats* out) {
+  if (!out) return fail(FDM_ERR_INVALID, "null argument");
+  *out = g_sor_stats;
+  return FDM_OK;
+}
+
+int fdm_statistical_outlier_removal(uint64_t n, const float* x, const float* y, const float* z, int on_device, int k,
+                                    float std_mul, int device, uint8_t* keep, float* mean_dist, float* threshold,
+                                    uint64_t* n_kept) {
+  if (!keep || !threshold || !n_kept) return fail(FDM_ERR_INVALID, "null argument");
+  *threshold = 0.0f;
+  *n_kept = 0;
+  g_sor_stats = fdm_sor_stats{};
+  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
+  if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null coordinate array");
+  const uint64_t k_eff = sor_effective_k(n, k);
+  if (k_eff > uint64_t(kKnnMaxK)) return fail(FDM_ERR_INVALID, "statistical outlier removal takes at most 64 neighbours");
+  if (n == 0) return FDM_OK;
+  if (int rc = pick_device(device)) return rc;
+  const unsigned np = unsigned(n);
+  if (k_eff == 0) {  // k == 0, one point: nothing is kept
+    if (on_device) {
+      HIPCK(hipMemset(keep, 0, size_t(n)));
+      if (mean_dist) HIPCK(hipMemset(mean_dist, 0, size_t(n) * sizeof(float)));
+    } else {
+      std::memset(keep, 0, size_t(n));
+      if (mean_dist) std::memset(mean_dist, 0, size_t(n) * sizeof(float));
+    }
+    return FDM_OK;
+  }
+  DevBuf b_in, b_mean, b_keep;
+  const float* d[3] = {x, y, z};
+  if (!on_device) {
+    const size_t cap = (size_t(n) + 3) & ~size_t(3);
+    if (int rc = b_in.alloc(cap * 3 * sizeof(float))) return rc;
+    const float* src[3] = {x, y, z};
+    for (int q = 0; q < 3; ++q) {
+      HIPCK(hipMemcpy(b_in.as<float>() + cap * size_t(q), src[q], size_t(n) * sizeof(float), hipMemcpyHostToDevice));
+      d[q] = b_in.as<float>() + cap * size_t(q);
+    }
+  }
+  float* d_mean = mean_dist;
+  uint8_t* d_keep = keep;
+  if (!on_device || !mean_dist) {
+    if (int rc = b_mean.alloc(size_t(n) * sizeof(float))) return rc;
+    d_mean = b_mean.as<float>();
+  }
+  if (!on_device) {
+    if (int rc = b_keep.alloc(size_t(n))) return rc;
+    d_keep = b_keep.as<uint8_t>();
+  }
+  if (int rc = sor_device(nullptr, np, d[0], d[1], d[2], int(k_eff), std_mul, d_mean, d_keep, threshold, n_kept)) return rc;
+  if (!on_device) {
+    HIPCK(hipMemcpy(keep, d_keep, size_t(n), hipMemcpyDeviceToHost));
+    if (mean_dist) HIPCK(hipMemcpy(mean_dist, d_mean, size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return FDM_OK;
+}
+
+int fdm_engine_remove_floating_points(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
+                                      int on_device, float height_threshold, float bin_size, uint8_t* keep,
+                                      uint64_t* n_kept) {
+  if (int rc = join_streams(e)) return rc;
+  if (!e || !keep || !n_kept) return fail(FDM_ERR_INVALID, "null argument");
+  *n_kept = 0;
+  if (!whole_map(e)) return fail(FDM_ERR_INVALID, "removeFloatingPoints is not defined for tiled engines");
+  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
+  if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null coordinate array");
+  const float bin = bin_size > 0.0f ? bin_size : float(e->G.res);  // pcd_convert.cpp:308-309
+  if (!(bin > 0.0f) || !std::isfinite(bin)) return fail(FDM_ERR_INVALID, "the bin size must be positive");
+  if (n == 0) return FDM_OK;
+  HIPCK(hipSetDevice(e->device));
+  DevBuf b_in, b_keep;
+  const float* d[3] = {x, y, z};
+  uint8_t* d_keep = keep;
+  if (!on_device) {
+    const size_t cap = (size_t(n) + 3) & ~size_t(3);
+    if (int rc = b_in.alloc(cap * 3 * sizeof(float))) return rc;
+    if (int rc = b_keep.alloc(size_t(n))) return rc;
+    const float* src[3] = {x, y, z};
+    for (int q = 0; q < 3; ++q) {
+      HIPCK(hipMemcpyAsync(b_in.as<float>() + cap * size_t(q), src[q], size_t(n) * sizeof(float), hipMemcpyHostToDevice,
+                           e->stream));
+      d[q] = b_in.as<float>() + cap * size_t(q);
+    }
+    d_keep = b_keep.as<uint8_t>();
+  }
+  if (int rc = height_filter_device(e, unsigned(n), d[0], d[1], d[2], height_threshold, bin, d_keep, n_kept)) return rc;
+  if (!on_device) {
+    HIPCK(hipMemcpyAsync(keep, d_keep, size_t(n), hipMemcpyDeviceToHost, e->stream));
+    return sync_all(e);
+  }
+  return FDM_OK;
+}
+
+// buildDEM(cloud, config): pcd_convert.cpp:275-323
+int fdm_engine_build_dem(uint64_t n, const void* x, const void* y, const void* z, const void* intensity, const void* rgb,
+                         int on_device, const fdm_dem_config* cfg, int device, fdm_engine** out_engine,
+                         fdm_dem_stats* stats) {
+  fdm_dem_stats local{};
+  fdm_dem_stats& S = stats ? *stats : local;
+  S = fdm_dem_stats{};
+  S.n_input = n;
+  if (!out_engine) return fail(FDM_ERR_INVALID, "null argument");
+  *out_engine = nullptr;
+  fdm_dem_config c;
+  fdm_default_dem_config(&c);
+  if (cfg) c = *cfg;
+  if (n == 0) return FDM_SKIP_EMPTY_CLOUD;  // :276 `return {}`: no map
+  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
+  if (c.method < 0 || c.method > 3) return fail(FDM_ERR_INVALID, "method must be 0 (Max), 1 (Min), 2 (Mean) or 3 (MinMax)");
+  if (!x || !y || !z) return fail(FDM_ERR_INVALID, "null coordinate array");
+  if (!(c.resolution > 0.0f) || !std::isfinite(c.resolution)) return fail(FDM_ERR_INVALID, "resolution must be positive");
+  const float bin = c.bin_size > 0.0f ? c.bin_size : c.resolution;  // :308-309
+  if (!std::isfinite(bin)) return fail(FDM_ERR_INVALID, "the bin size must be finite");
+  const uint64_t k_eff = sor_effective_k(n, c.sor_k);
+  if (k_eff > uint64_t(kKnnMaxK)) return fail(FDM_ERR_INVALID, "statistical outlier removal takes at most 64 neighbours");
+  if (k_eff == 0) return FDM_SKIP_ALL_FILTERED;  // :282: SOR returned an empty cloud
+  if (int rc = pick_device(device)) return rc;
+  const unsigned np = unsigned(n);
+  Events E;
+  if (int rc = E.init(8)) return rc;
+  // 0. the cloud on the device
+  const void* src[5] = {x, y, z, intensity, rgb};
+  const float* ch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf b_stage;
+  if (on_device) {
+    for (int q = 0; q < 5; ++q) ch[q] = static_cast<const float*>(src[q]);
+  } else {
+    const size_t cap = (size_t(n) + 3) & ~size_t(3);
+    if (int rc = b_stage.alloc(cap * 5 * sizeof(float))) return rc;
+    for (int q = 0; q < 5; ++q) {
+      if (!src[q]) continue;
+      HIPCK(hipMemcpy(b_stage.as<float>() + cap * size_t(q), src[q], size_t(n) * sizeof(float), hipMemcpyHostToDevice));
+      ch[q] = b_stage.as<float>() + cap * size_t(q);
+    }
+  }
+  // 1. statistical outlier removal (:279-282)
+  DevBuf b_mean, b_keep, b_a;
+  if (int rc = b_mean.alloc(size_t(n) * sizeof(float))) return rc;
+  if (int rc = b_keep.alloc(size_t(n))) return rc;
+  if (int rc = sor_device(nullptr, np, ch[0], ch[1], ch[2], int(k_eff), c.sor_std_mul, b_mean.as<float>(),
+                          b_keep.as<uint8_t>(), &S.sor_threshold, &S.n_after_sor))
+    return rc;
+  S.n_sor_fallback = g_sor_stats.n_fallback;
+  for (int q = 0; q < 4; ++q) S.stage_ms[q] = g_sor_stats.ms[q];
+  if (S.n_after_sor == 0) return FDM_SKIP_ALL_FILTERED;
+  const unsigned n1 = unsigned(S.n_after_sor);
+  const size_t cap1 = (size_t(n1) + 3) & ~size_t(3);
+  if (int rc = b_a.alloc(cap1 * 5 * sizeof(float))) return rc;
+  const float* a[5];
+  float* a_out[5];
+  for (int q = 0; q < 5; ++q) {
+    a_out[q] = b_a.as<float>() + cap1 * size_t(q);
+    a[q] = ch[q] ? a_out[q] : nullptr;
+  }
+  if (int rc = compact_device(nullptr, np, b_keep.as<uint8_t>(), ch, a_out)) return rc;
+  // 2. the map over the survivors' bounding box (:285-305), as fdm_engine_create_from_point_cloud sizes it
+  DevBuf b_rstat;
+  if (int rc = b_rstat.alloc(sizeof(RasterStat))) return rc;
+  hipLaunchKernelGGL(k_ras_stat_init, dim3(1), dim3(64), 0, nullptr, b_rstat.as<RasterStat>());
+  hipLaunchKernelGGL(k_ras_bounds, dim3(std::min((n1 + 255u) / 256u, 2048u)), dim3(256), 0, nullptr, n1, a[0], a[1],
+                     b_rstat.as<RasterStat>());
+  HIPCK(hipGetLastError());
+  RasterStat hs{};
+  HIPCK(hipMemcpy(&hs, b_rstat.as<RasterStat>(), sizeof(hs), hipMemcpyDeviceToHost));
+  const float min_x = unord_h(hs.min_x), min_y = unord_h(hs.min_y), max_x = unord_h(hs.max_x), max_y = unord_h(hs.max_y);
+  const float width = max_x - min_x + c.resolution, height = max_y - min_y + c.resolution;
+  if (!std::isfinite(width) || !std::isfinite(height) || !(width > 0.0f) || !(height > 0.0f))
+    return fail(FDM_ERR_INVALID, "the cloud's x / y extent is not a positive finite number");
+  fdm_geometry g{};
+  g.length_x = double(width);
+  g.length_y = double(height);
+  g.resolution = double(c.resolution);
+  g.position_x = double(min_x + max_x) / 2.0;
+  g.position_y = double(min_y + max_y) / 2.0;
+  fdm_engine* e = nullptr;
+  if (int rc = fdm_engine_create_map(&g, nullptr, device, &e)) return rc;
+  auto drop = [&](int rc) { fdm_engine_destroy(e); return rc; };
+  // 3. floating-point removal (:308-311)
+  DevBuf b_keep2, b_b;
+  if (int rc = b_keep2.alloc(size_t(n1))) return drop(rc);
+  (void)hipEventRecord(E.ev[0], e->stream);
+  if (int rc = height_filter_device(e, n1, a[0], a[1], a[2], c.height_threshold, bin, b_keep2.as<uint8_t>(),
+                                    &S.n_after_height))
+    return drop(rc);
+  const unsigned n2 = unsigned(S.n_after_height);
+  const size_t cap2 = (size_t(n2) + 3) & ~size_t(3);
+  if (int rc = b_b.alloc(cap2 * 5 * sizeof(float))) return drop(rc);
+  const float* b[5];
+  float* b_out[5];
+  for (int q = 0; q < 5; ++q) {
+    b_out[q] = b_b.as<float>() + cap2 * size_t(q);
+    b[q] = a[q] ? b_out[q] : nullptr;
+  }
+  if (n2)
+    if (int rc = compact_device(e->stream, n1, b_keep2.as<uint8_t>(), a, b_out)) return drop(rc);
+  (void)hipEventRecord(E.ev[1], e->stream);
+  // 4. rasterization (:314; an empty cloud leaves the map as it is), 5. inpainting (:317-320)
+  if (n2) {
+    const int rc = fdm_engine_from_point_cloud_device(e, n2, b[0], b[1], b[2], b[3],
+                                                      reinterpret_cast<const uint32_t*>(b[4]), c.method, &S.raster);
+    if (rc < 0) return drop(rc);
+  }
+  (void)hipEventRecord(E.ev[2], e->stream);
+  if (c.inpaint_iterations > 0) {
+    const int rc = fdm_engine_apply_inpainting(e, c.inpaint_iterations, 2, 1);
+    if (rc < 0) return drop(rc);
+  }
+  (void)hipEventRecord(E.ev[3], e->stream);
+  if (int rc = sync_all(e)) return drop(rc);
+  for (int q = 0; q < 3; ++q) S.stage_ms[4 + q] = E.ms(q, q + 1);
+  *out_engine = e;
+  return FDM_OK;
+}
+
+}  // extern "C"

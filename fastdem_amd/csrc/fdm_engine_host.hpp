@@ -39,6 +39,8 @@
 #include "fdm_egress.hpp"
 #include "fdm_render.hpp"
 #include "fdm_raster.hpp"
+#include "fdm_knn.hpp"
+#include "fdm_dem.hpp"
 #include "fdm_ingest.hpp"
 #include "fdm_post.hpp"
 

@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import FdmCloud2Layout, FdmConfig, FdmGeometry, FdmRasterStats, FdmScanStats, FdmTile
+from .capi import (FdmCloud2Layout, FdmConfig, FdmDemConfig, FdmDemStats, FdmGeometry, FdmRasterStats, FdmScanStats,
+                   FdmSorStats, FdmTile)
 
 
 class EngineError(RuntimeError):
@@ -548,6 +549,26 @@ class Engine:
                                                            m, C.byref(st)))
         return rc, {"n_points_used": int(st.n_points_used), "n_cells_written": int(st.n_cells_written)}
 
+    def remove_floating_points(self, x, y, z, height_threshold=2.0, bin_size=0.0):
+        """removeFloatingPoints(cloud, map, height_threshold, bin) on this map's geometry: the keep mask (bool[n], or a
+        torch uint8 device tensor for device tensors).  bin_size 0 = the resolution.  The map is not touched."""
+        n_kept = C.c_uint64(0)
+        if _is_torch(x):
+            import torch
+            torch.cuda.current_stream().synchronize()
+            keep = torch.zeros(x.numel(), dtype=torch.uint8, device=x.device)
+            _ck(self._lib.fdm_engine_remove_floating_points(self._h, x.numel(), _dptr(x), _dptr(y), _dptr(z), 1,
+                                                            float(height_threshold), float(bin_size), _dptr(keep),
+                                                            C.byref(n_kept)))
+            return keep
+        x, y, z = _f32(x), _f32(y), _f32(z)
+        keep = np.zeros(x.size, dtype=np.uint8)
+        _ck(self._lib.fdm_engine_remove_floating_points(self._h, x.size, _ptr(x), _ptr(y), _ptr(z), 0,
+                                                        float(height_threshold), float(bin_size), _ptr(keep),
+                                                        C.byref(n_kept)))
+        assert int(keep.sum()) == n_kept.value
+        return keep.astype(bool)
+
     def last_raster_ms(self):
         """(ids, grouping, walk) device ms of the last from_point_cloud (enable_profile() first)."""
         ms = (C.c_float * 3)()
@@ -729,3 +750,83 @@ def from_point_cloud(x, y, z, resolution, intensity=None, rgb=None, method="max"
     if rc != 0 or not h.value:
         return None
     return Engine._adopt(h)
+
+
+class DEMConfig:
+    """fastdem::DEMConfig (io/pcd_convert.hpp:28-42), with the reference's defaults."""
+
+    def __init__(self, resolution=0.1, method="max", sor_k=10, sor_std_mul=1.0, height_threshold=2.0, bin_size=0.0,
+                 inpaint_iterations=3):
+        self.resolution, self.method = resolution, method
+        self.sor_k, self.sor_std_mul = sor_k, sor_std_mul
+        self.height_threshold, self.bin_size = height_threshold, bin_size
+        self.inpaint_iterations = inpaint_iterations
+
+    def as_struct(self):
+        return FdmDemConfig(float(np.float32(self.resolution)), _raster_method(self.method), int(self.sor_k),
+                            float(np.float32(self.sor_std_mul)), float(np.float32(self.height_threshold)),
+                            float(np.float32(self.bin_size)), int(self.inpaint_iterations))
+
+
+def sor_last_stats():
+    """What this thread's last outlier removal did: n_queries, n_fallback (queries the brute-force queue took), grid_x,
+    grid_y, voxel, ms (grid build, search, fallback queue, statistics)."""
+    st = FdmSorStats()
+    _ck(capi.load().fdm_sor_last_stats(C.byref(st)))
+    return {"n_queries": int(st.n_queries), "n_fallback": int(st.n_fallback), "grid_x": int(st.grid_x),
+            "grid_y": int(st.grid_y), "voxel": float(st.voxel), "ms": tuple(float(v) for v in st.ms)}
+
+
+def statistical_outlier_removal(x, y, z, k=10, std_mul=1.0, device=0, return_details=False):
+    """nanopcl::filters::statisticalOutlierRemoval(cloud, k, std_mul) as a keep mask over the input points: bool[n] for
+    numpy arrays, a torch uint8 device tensor for torch device tensors.  return_details: (keep, mean_dist, threshold)
+    with mean_dist the per-point mean distance to its k nearest neighbours (float32) and threshold a np.float32."""
+    lib = capi.load()
+    thr, n_kept = C.c_float(0.0), C.c_uint64(0)
+    if _is_torch(x):
+        import torch
+        torch.cuda.current_stream().synchronize()
+        n = x.numel()
+        keep = torch.zeros(n, dtype=torch.uint8, device=x.device)
+        mean = torch.zeros(n, dtype=torch.float32, device=x.device)
+        _ck(lib.fdm_statistical_outlier_removal(n, _dptr(x), _dptr(y), _dptr(z), 1, int(k), float(np.float32(std_mul)),
+                                                int(device), _dptr(keep), _dptr(mean), C.byref(thr), C.byref(n_kept)))
+    else:
+        x, y, z = _f32(x), _f32(y), _f32(z)
+        n = x.size
+        keep8 = np.zeros(n, dtype=np.uint8)
+        mean = np.zeros(n, dtype=np.float32)
+        _ck(lib.fdm_statistical_outlier_removal(n, _ptr(x), _ptr(y), _ptr(z), 0, int(k), float(np.float32(std_mul)),
+                                                int(device), _ptr(keep8), _ptr(mean), C.byref(thr), C.byref(n_kept)))
+        assert int(keep8.sum()) == n_kept.value
+        keep = keep8.astype(bool)
+    return (keep, mean, np.float32(thr.value)) if return_details else keep
+
+
+def build_dem(x, y, z, intensity=None, rgb=None, config=None, device=0, return_stats=False):
+    """fastdem::buildDEM(cloud, config): outlier removal, floating-point removal, rasterization and inpainting on the
+    device.  Returns a map-only Engine, or None where the reference returns an uninitialised map (an empty cloud, a
+    cloud the outlier removal empties).  numpy arrays or torch device tensors.  return_stats: (engine, dict of
+    fdm_dem_stats)."""
+    lib = capi.load()
+    cfg = (config if config is not None else DEMConfig()).as_struct()
+    h, st = C.c_void_p(), FdmDemStats()
+    if _is_torch(x):
+        import torch
+        torch.cuda.current_stream().synchronize()
+        n, on_device = x.numel(), 1
+        args = [_dptr(v) for v in (x, y, z, intensity, rgb)]
+    else:
+        x, y, z = _f32(x), _f32(y), _f32(z)
+        keep = (x, y, z, _f32(intensity), _u32(rgb))
+        n, on_device = x.size, 0
+        args = [_ptr(v) for v in keep]
+    rc = _ck(lib.fdm_engine_build_dem(n, *args, on_device, C.byref(cfg), int(device), C.byref(h), C.byref(st)))
+    eng = Engine._adopt(h) if rc == 0 and h.value else None
+    if not return_stats:
+        return eng
+    stats = {"status": rc, "n_input": int(st.n_input), "n_after_sor": int(st.n_after_sor),
+             "n_after_height": int(st.n_after_height), "n_sor_fallback": int(st.n_sor_fallback),
+             "sor_threshold": np.float32(st.sor_threshold), "stage_ms": tuple(float(v) for v in st.stage_ms),
+             "n_points_used": int(st.raster.n_points_used), "n_cells_written": int(st.raster.n_cells_written)}
+    return eng, stats

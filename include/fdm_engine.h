@@ -529,6 +529,66 @@ int fdm_engine_to_point_cloud_device(fdm_engine* e, const float** dx, const floa
 /* with fdm_engine_enable_profile on: device ms of the last fromPointCloud's cell ids, grouping (sort) and walk */
 int fdm_engine_last_raster_ms(fdm_engine* e, float* ms3);
 
+/* ---- buildDEM: a clean DEM from a merged cloud (src/pcd_convert.cpp:194-323) and its two filter stages ----
+ * Statistical outlier removal = nanopcl::filters::statisticalOutlierRemoval(cloud, k, std_mul)
+ * (outlier_removal_impl.hpp:83-142).  effective_k = min(k, n - 1), a negative k counting as "every other point" (the
+ * reference converts it to size_t).  Per point: the effective_k smallest squared distances to the OTHER points
+ * (duplicates of the point count, at distance 0), each ((dx*dx) + (dy*dy)) + (dz*dz) in fp32 without contraction;
+ * mean = (sum of their correctly rounded sqrt, ascending, fp32) / effective_k.  The global mean and the sum of squared
+ * differences are fp64 sums in input order; threshold = float(mean) + std_mul * float(sqrt(ss / n)); keep[i] = mean[i]
+ * <= threshold.  The search is EXACT k-NN; nanoflann's pruning bound is rounded and can miss a neighbour within
+ * rounding of the k-th (ASSUMED equal otherwise: DESIGN.md §7).  k == 0, n == 0 and n == 1 keep nothing (*n_kept = 0,
+ * FDM_OK).  FDM_ERR_INVALID: effective_k > 64; a coordinate that is NaN or infinite (undefined in the reference).
+ * keep[n] and mean_dist[n] (nullable) are host arrays when the coordinates are (on_device 0), device arrays otherwise;
+ * threshold and n_kept are host words.  Synchronous. */
+int fdm_statistical_outlier_removal(uint64_t n, const float* x, const float* y, const float* z, int on_device, int k,
+                                    float std_mul, int device, uint8_t* keep, float* mean_dist, float* threshold,
+                                    uint64_t* n_kept);
+/* what the calling thread's last outlier removal (the call above, or the one inside fdm_engine_build_dem) did */
+typedef struct fdm_sor_stats {
+  uint64_t n_queries;   /* points searched */
+  uint64_t n_fallback;  /* ... of which the grid search left to the brute-force queue */
+  int32_t grid_x, grid_y;  /* columns of the search grid */
+  float voxel;          /* their edge, metres */
+  float ms[4];          /* device ms: grid build, search, fallback queue, statistics (download and host sums included) */
+} fdm_sor_stats;
+int fdm_sor_last_stats(fdm_sor_stats* out);
+/* removeFloatingPoints(cloud, map, height_threshold, bin) on e's geometry (pcd_convert.cpp:194-269): per cell a histogram
+ * of z over bins of `bin` = bin_size > 0 ? bin_size : resolution from the cell's z_min, n_bins = max(1, int((z_max -
+ * z_min) / bin) + 1), a point's bin min(int((z - z_min) / bin), n_bins - 1); the LOWEST bin with the largest count is
+ * the ground; keep[i] = z <= (z_min + (best_bin + 0.5f) * bin) + height_threshold.  Points with NaN z or outside the
+ * map are not kept.  FDM_ERR_INVALID: a cell whose (z_max - z_min) / bin does not fit an int32; a tiled engine.
+ * keep[n] is a host array when the coordinates are (on_device 0), a device array otherwise.  The map is not touched. */
+int fdm_engine_remove_floating_points(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
+                                      int on_device, float height_threshold, float bin_size, uint8_t* keep,
+                                      uint64_t* n_kept);
+typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
+  float resolution;
+  int32_t method;              /* RasterMethod: 0 Max, 1 Min, 2 Mean, 3 MinMax */
+  int32_t sor_k;
+  float sor_std_mul;
+  float height_threshold;
+  float bin_size;              /* 0 = the resolution */
+  int32_t inpaint_iterations;  /* 0 = no inpainting */
+} fdm_dem_config;
+void fdm_default_dem_config(fdm_dem_config* cfg);  /* 0.1, Max, 10, 1.0, 2.0, 0.0, 3 */
+typedef struct fdm_dem_stats {
+  uint64_t n_input, n_after_sor, n_after_height;
+  uint64_t n_sor_fallback;   /* queries of the outlier removal that took the brute-force queue */
+  float sor_threshold;
+  float stage_ms[7];         /* device ms: k-NN grid build, search, fallback queue, statistics, height filter, raster, inpaint */
+  fdm_raster_stats raster;
+} fdm_dem_stats;
+/* buildDEM(cloud, config): outlier removal, a map over the survivors' x / y bounding box (sized as
+ * fdm_engine_create_from_point_cloud sizes it), floating-point removal on that map, fromPointCloud with `method`,
+ * applyInpainting(map, inpaint_iterations, 2, inplace) when inpaint_iterations > 0.  The cloud stays on the device
+ * between the stages; the survivors keep their input order, intensity and colour.  cfg NULL = the defaults.  The result
+ * is a map-only engine.  FDM_SKIP_EMPTY_CLOUD (n == 0) and FDM_SKIP_ALL_FILTERED (the outlier removal keeps nothing:
+ * one point, sor_k == 0) leave *out_engine NULL, where the reference returns a map without geometry. */
+int fdm_engine_build_dem(uint64_t n, const void* x, const void* y, const void* z, const void* intensity,
+                         const void* rgb, int on_device, const fdm_dem_config* cfg, int device,
+                         fdm_engine** out_engine, fdm_dem_stats* stats);
+
 /* Pinned host memory for input clouds (the arrays fdm_engine_integrate* read in place, see
  * fdm_engine_integrate_async).  Blocks come from a process-wide pool of hipHostMalloc'ed memory in
  * power-of-two size classes — a cloud allocated per sensor message costs a free-list pop, not a

@@ -1,0 +1,172 @@
+"""Plain NumPy restatement of fastdem::buildDEM and its two filters, written from the reference's sources and not from the
+engine — the reading the engine's build_dem / statistical_outlier_removal / remove_floating_points are held to
+(tests/test_sor_gpu.py, tests/test_build_dem_gpu.py); its own known answers are in tests/test_dem_restate.py.  Test
+data, not product.
+
+  restate_sor             nanopcl::filters::statisticalOutlierRemoval   outlier_removal_impl.hpp:83-142
+  restate_ground_peak     findGroundPeak                                pcd_convert.cpp:194-220
+  restate_floating        removeFloatingPoints                          pcd_convert.cpp:228-269
+  restate_build_dem       buildDEM                                      pcd_convert.cpp:275-323
+
+The k-NN is brute force (every pair), in fp32 with the reference's operation order ((dx*dx) + (dy*dy)) + (dz*dz); the two
+global sums are SEQUENTIAL fp64 sums (np.cumsum: np.sum is pairwise and rounds differently).  A point's cell comes from
+the oracle's grid, rasterization from tests/raster_restate.py, inpainting from the oracle as tests/test_post_gpu.py uses it.
+"""
+import numpy as np
+
+import raster_restate as RR
+
+F32 = np.float32
+MAX_K = 64
+
+
+def effective_k(n, k):
+    """min(size_t(k), n - 1); 0 where the reference returns an empty cloud (:86-92)."""
+    if n < 2 or k == 0:
+        return 0
+    return n - 1 if k < 0 else min(int(k), n - 1)    # a negative int converts to a huge size_t
+
+
+def knn_mean_distances(x, y, z, k, chunk=512):
+    """float32[n]: (sum of sqrt of the k smallest squared distances to the OTHER points, ascending, fp32) / float(k)."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    n = x.size
+    out = np.empty(n, dtype=F32)
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        dx = x[a:b, None] - x[None, :]
+        dy = y[a:b, None] - y[None, :]
+        dz = z[a:b, None] - z[None, :]
+        d2 = ((dx * dx) + (dy * dy)) + (dz * dz)                     # float32 throughout: one rounding per operation
+        assert d2.dtype == F32
+        d2[np.arange(b - a), np.arange(a, b)] = np.inf               # only the query's own index is left out
+        best = np.sort(np.partition(d2, k - 1, axis=1)[:, :k], axis=1)
+        root = np.sqrt(best)                                         # correctly rounded in fp32
+        acc = np.zeros(b - a, dtype=F32)
+        for j in range(k):                                           # sum += sqrt(dist_sq), nearest first
+            acc = (acc + root[:, j]).astype(F32)
+        out[a:b] = acc / F32(k)
+    return out
+
+
+def sor_threshold(mean, std_mul):
+    """(:118-129) two sequential fp64 sums, then fp32."""
+    m64 = mean.astype(np.float64)
+    n = mean.size
+    global_mean = np.cumsum(m64)[-1] / np.float64(n)
+    diff = m64 - global_mean
+    ss = np.cumsum(diff * diff)[-1]
+    global_std = F32(np.sqrt(ss / np.float64(n)))
+    return F32(F32(global_mean) + F32(F32(std_mul) * global_std))
+
+
+def restate_sor(x, y, z, k, std_mul=1.0):
+    """(keep bool[n], mean float32[n] or None, threshold float32 or None); None where no neighbour search happens."""
+    n = np.asarray(x).size
+    ke = effective_k(n, k)
+    if ke == 0:
+        return np.zeros(n, dtype=bool), None, None
+    mean = knn_mean_distances(x, y, z, ke)
+    thr = sor_threshold(mean, std_mul)
+    return mean <= thr, mean, thr
+
+
+def ulp_gap_to_threshold(mean, thr):
+    """Smallest distance, in units of the threshold's ulp, between a mean distance and the threshold."""
+    return float(np.min(np.abs(mean.astype(np.float64) - np.float64(thr))) / np.float64(np.spacing(F32(thr))))
+
+
+def _int_cast(v):
+    """static_cast<int>(float): truncation; out of range is undefined in C++ and an error here."""
+    v = float(v)
+    if not (-2147483649.0 < v < 2147483648.0):
+        raise OverflowError("float does not fit an int")
+    return int(v)
+
+
+def restate_ground_peak(z_values, bin_size):
+    """findGroundPeak: the centre of the LOWEST bin holding the largest count, fp32."""
+    zs = np.asarray(z_values, dtype=F32)
+    if zs.size == 0:
+        return F32(0.0)
+    b = F32(bin_size)
+    z_min, z_max = zs.min(), zs.max()
+    n_bins = max(1, _int_cast(F32(F32(z_max - z_min) / b)) + 1)
+    counts = {}
+    for v in zs:
+        i = min(_int_cast(F32(F32(v - z_min) / b)), n_bins - 1)
+        counts[i] = counts.get(i, 0) + 1
+    best_bin, best_count = 0, 0
+    for i in sorted(counts):                                         # ascending bins, strict '>'
+        if counts[i] > best_count:
+            best_count, best_bin = counts[i], i
+    return F32(z_min + F32(F32(F32(best_bin) + F32(0.5)) * b))
+
+
+def restate_floating(grid, x, y, z, height_threshold, bin_size):
+    """removeFloatingPoints: keep bool[n]."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    cells = {}
+    for i in range(x.size):
+        if np.isnan(z[i]):
+            continue
+        ok, rc = grid.get_index(float(x[i]), float(y[i]))
+        if ok:
+            cells.setdefault(rc, []).append(i)
+    keep = np.zeros(x.size, dtype=bool)
+    for idx in cells.values():
+        cutoff = F32(restate_ground_peak(z[idx], bin_size) + F32(height_threshold))
+        for i in idx:
+            if z[i] <= cutoff:
+                keep[i] = True
+    return keep
+
+
+class DEM:
+    """What restate_build_dem returns: geometry tuple (restate_auto_geometry), grid, layers in order, the stage counts."""
+
+    def __init__(self):
+        self.geometry = self.grid = None
+        self.order, self.store = [], {}
+        self.n_after_sor = self.n_after_height = 0
+        self.threshold = None
+
+    def layers(self):
+        return list(self.order)
+
+    def layer(self, name):
+        return self.store[name]
+
+
+def restate_build_dem(R, x, y, z, intensity=None, rgb=None, resolution=0.1, method="max", sor_k=10, sor_std_mul=1.0,
+                      height_threshold=2.0, bin_size=0.0, inpaint_iterations=3):
+    """A DEM, or None where the reference returns an uninitialised map (:276, :282)."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    if x.size == 0:
+        return None
+    keep, _, thr = restate_sor(x, y, z, sor_k, sor_std_mul)
+    if not keep.any():
+        return None
+    sel = lambda a: None if a is None else np.asarray(a)[keep]       # noqa: E731
+    x, y, z, intensity, rgb = x[keep], y[keep], z[keep], sel(intensity), sel(rgb)
+    out = DEM()
+    out.threshold, out.n_after_sor = thr, int(x.size)
+    res = F32(resolution)
+    geo = RR.restate_auto_geometry(x, y, res)                        # :285-305: the same arithmetic as :160-181
+    out.geometry = geo
+    out.grid = R.RefEngine(float(F32(geo[0])), float(F32(geo[1])), float(res), position=(geo[3], geo[4]))
+    g = out.grid.geometry()
+    assert (g.length_x, g.length_y, g.resolution, g.rows, g.cols) == (geo[0], geo[1], geo[2], geo[5], geo[6])
+    b = F32(bin_size) if bin_size > 0 else res                       # :308-309
+    keep2 = restate_floating(out.grid, x, y, z, height_threshold, b)
+    sel2 = lambda a: None if a is None else a[keep2]                 # noqa: E731
+    x, y, z, intensity, rgb = x[keep2], y[keep2], z[keep2], sel2(intensity), sel2(rgb)
+    out.n_after_height = int(x.size)
+    out.order = list(RR.BASIC_LAYERS)
+    out.store = {n: np.full((geo[5], geo[6]), np.nan, dtype=F32) for n in out.order}
+    RR.restate_raster(out.grid, out.store, out.order, x, y, z, intensity, rgb, method)
+    if inpaint_iterations > 0:                                       # :317-320: in place, on `elevation`
+        out.grid.set_layer("elevation", out.store["elevation"])
+        out.grid.apply_inpainting(int(inpaint_iterations), 2, True)
+        out.store["elevation"] = np.array(out.grid.layer("elevation"), dtype=F32)
+    return out
