@@ -4,6 +4,7 @@ Layout (only what the path needs):
   csrc/        hand-written HIP kernels + the C ABI (include/fdm_engine.h) -> lib/libfdm_engine.so
   capi.py      ctypes declarations of that ABI (plumbing)
   engine.py    Python handle used by tests / bench.py
+  pcd.py       PCD files: load_pcd, save_pcd, pcd2dem, Engine.to_pcd
   synth.py     synthetic scans of the BASELINE.json configurations
   tiling.py    multi-GPU spatial tiling + RCCL halo exchange of one global map
   cpp/         C++17 host mirror of fastdem::FastDEM / ElevationMap over the C ABI
@@ -11,6 +12,7 @@ Layout (only what the path needs):
 from . import capi, synth  # noqa: F401
 from .engine import (DEMConfig, Engine, EngineError, HostArray, build_dem, from_point_cloud, host_array,  # noqa: F401
                      sor_last_stats, statistical_outlier_removal)
+from . import pcd  # noqa: F401,E402
 
 __all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud", "DEMConfig", "build_dem",
-           "statistical_outlier_removal", "sor_last_stats", "capi", "synth"]
+           "statistical_outlier_removal", "sor_last_stats", "capi", "synth", "pcd"]

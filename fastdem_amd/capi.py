@@ -126,6 +126,19 @@ class FdmDemStats(C.Structure):  # fdm_dem_stats (include/fdm_engine.h)
                 ("raster", FdmRasterStats)]
 
 
+class FdmPcdField(C.Structure):  # fdm_pcd_field (include/fdm_engine.h)
+    _fields_ = [("name", C.c_char * 64), ("type", C.c_char), ("reserved", C.c_uint8 * 3), ("size", C.c_uint32),
+                ("count", C.c_uint32), ("offset", C.c_uint32)]
+
+
+class FdmPcdHeader(C.Structure):  # fdm_pcd_header (include/fdm_engine.h)
+    _fields_ = [("fields", FdmPcdField * 64), ("n_fields", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("point_size", C.c_uint32), ("viewpoint", C.c_double * 7), ("format", C.c_int32),
+                ("idx_x", C.c_int32), ("idx_y", C.c_int32), ("idx_z", C.c_int32), ("idx_intensity", C.c_int32),
+                ("idx_rgb", C.c_int32), ("idx_nx", C.c_int32), ("idx_ny", C.c_int32), ("idx_nz", C.c_int32),
+                ("data_offset", C.c_uint64)]
+
+
 class FdmRoutePlan(C.Structure):  # fdm_route_plan (include/fdm_engine.h)
     _fields_ = [("world", C.c_int32), ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("pad", C.c_int32),
                 ("row_edge", C.c_int32 * 17), ("col_edge", C.c_int32 * 17)]
@@ -147,6 +160,7 @@ FDM_OK, FDM_SKIP_EMPTY_CLOUD, FDM_SKIP_ALL_FILTERED, FDM_SKIP_NO_CELL, FDM_SKIP_
 RASTER_METHOD = {"max": 0, "min": 1, "mean": 2, "minmax": 3}        # fastdem::RasterMethod
 FDM_ERR_INVALID, FDM_ERR_HIP, FDM_ERR_NO_LAYER, FDM_ERR_NO_DEVICE = -1, -2, -3, -4
 NORMALIZE = {"min_max": 0, "percentile_1_99": 1, "fixed_range": 2}   # PngExportConfig::Normalize
+PCD_ASCII, PCD_BINARY = 0, 1                                         # fdm_pcd_header.format
 COLORMAP = {"grayscale": 0, "viridis": 1, "jet": 2}                  # PngExportConfig::Colormap
 
 _P = C.c_void_p
@@ -264,6 +278,19 @@ PROTOTYPES = {
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),
     "fdm_engine_build_dem": (C.c_int, [C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(FdmDemConfig), C.c_int,
                                        C.POINTER(_P), C.POINTER(FdmDemStats)]),
+    "fdm_pcd_parse_header": (C.c_int, [_P, C.c_uint64, C.POINTER(FdmPcdHeader)]),
+    "fdm_pcd_write_header": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, _D, C.c_int, _P, C.c_uint64,
+                                       C.POINTER(C.c_uint64)]),
+    "fdm_pcd_decode": (C.c_int, [C.POINTER(FdmPcdHeader), _P, C.c_uint64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int,
+                                 C.c_int]),
+    "fdm_pcd_encode": (C.c_int, [C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                 C.c_uint64, C.POINTER(C.c_uint64)]),
+    "fdm_pcd_build_dem": (C.c_int, [C.POINTER(FdmPcdHeader), _P, C.c_uint64, C.c_int, C.POINTER(FdmDemConfig), C.c_int,
+                                    C.POINTER(_P), C.POINTER(FdmDemStats)]),
+    "fdm_engine_to_pcd": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "fdm_pcd_debug_profile": (C.c_int, [C.c_int]),
+    "fdm_pcd_debug_last_kernel_ms": (C.c_int, [_F]),
     "fdm_default_image_config": (None, [C.POINTER(FdmImageConfig)]),
     "fdm_engine_render_layer": (C.c_int, [_P, C.c_char_p, C.POINTER(FdmImageConfig), _P, C.c_uint64,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F]),

@@ -51,6 +51,26 @@ struct Color {
   constexpr Color(uint8_t r_, uint8_t g_, uint8_t b_) : r(r_), g(g_), b(b_) {}
 };
 
+// core/types.hpp:19-22 — Eigen::Vector4f there; the same 16 bytes here
+struct alignas(16) Point4 {
+  float v[4];
+  constexpr Point4() : v{0.0f, 0.0f, 0.0f, 0.0f} {}
+  constexpr Point4(float x, float y, float z, float w) : v{x, y, z, w} {}
+  float& x() { return v[0]; }
+  float& y() { return v[1]; }
+  float& z() { return v[2]; }
+  float& w() { return v[3]; }
+  float x() const { return v[0]; }
+  float y() const { return v[1]; }
+  float z() const { return v[2]; }
+  float w() const { return v[3]; }
+  float& operator[](int i) { return v[size_t(i)]; }
+  float operator[](int i) const { return v[size_t(i)]; }
+  float* data() { return v; }
+  const float* data() const { return v; }
+};
+using Normal4 = Point4;  // a normal's fourth component is 0; the SoA cloud keeps x, y, z
+
 class PointCloud {
  public:
   // xyz view of one point (reads and writes go to the SoA channels)
@@ -63,6 +83,23 @@ class PointCloud {
     operator Eigen::Vector3f() const { return Eigen::Vector3f(x_, y_, z_); }
   };
 
+  // one point's normal in the SoA channels, and the channel as a sequence (normals()[i], normals().back())
+  struct NormalRef {
+    float &x_, &y_, &z_;
+    float x() const { return x_; }
+    float y() const { return y_; }
+    float z() const { return z_; }
+    float w() const { return 0.0f; }
+    NormalRef& operator=(const Normal4& n) { x_ = n.x(); y_ = n.y(); z_ = n.z(); return *this; }
+    operator Normal4() const { return Normal4(x_, y_, z_, 0.0f); }
+  };
+  struct NormalsView {
+    PointCloud* cloud;
+    size_t size() const { return cloud->nx_.size(); }
+    NormalRef operator[](size_t i) const { return NormalRef{cloud->nx_[i], cloud->ny_[i], cloud->nz_[i]}; }
+    NormalRef back() const { return (*this)[size() - 1]; }
+  };
+
   PointCloud() = default;
   explicit PointCloud(size_t n) { resize(n); }
 
@@ -73,6 +110,7 @@ class PointCloud {
     x_.resize(n); y_.resize(n); z_.resize(n);
     if (use_intensity_) intensity_.resize(n);
     if (use_color_) rgb_.resize(n);
+    if (use_normal_) { nx_.resize(n); ny_.resize(n); nz_.resize(n); }
     if (use_cov_) cov_.resize(n * 9);
   }
   void clear() { resize(0); }
@@ -81,6 +119,7 @@ class PointCloud {
     x_.push_back(x); y_.push_back(y); z_.push_back(z);
     if (use_intensity_) intensity_.push_back(0.0f);
     if (use_color_) rgb_.push_back(0u);
+    if (use_normal_) { nx_.push_back(0.0f); ny_.push_back(0.0f); nz_.push_back(0.0f); }
     if (use_cov_) cov_.resize(cov_.size() + 9, 0.0f);
   }
   void add(float x, float y, float z, Intensity i) {
@@ -119,6 +158,13 @@ class PointCloud {
   Color color(size_t i) const { return Color(uint8_t(rgb_[i] >> 16), uint8_t(rgb_[i] >> 8), uint8_t(rgb_[i])); }
   void setColor(size_t i, const Color& c) { rgb_[i] = pack(c); }
 
+  // normal channel (nanopcl/core/point_cloud.hpp): what loadPCD fills from normal_x / normal_y / normal_z
+  bool hasNormal() const { return use_normal_; }
+  void useNormal() { use_normal_ = true; nx_.resize(size(), 0.0f); ny_.resize(size(), 0.0f); nz_.resize(size(), 0.0f); }
+  Normal4 normal(size_t i) const { return Normal4(nx_[i], ny_[i], nz_[i], 0.0f); }
+  NormalRef normal(size_t i) { return NormalRef{nx_[i], ny_[i], nz_[i]}; }
+  NormalsView normals() { return NormalsView{this}; }
+
   const std::string& frameId() const { return frame_id_; }
   void setFrameId(const std::string& id) { frame_id_ = id; }
   uint64_t timestamp() const { return timestamp_ns_; }
@@ -130,15 +176,23 @@ class PointCloud {
   const float* zData() const { return z_.data(); }
   const float* intensityData() const { return use_intensity_ ? intensity_.data() : nullptr; }
   const uint32_t* rgbData() const { return use_color_ ? rgb_.data() : nullptr; }
+  const float* normalData(int axis) const { return !use_normal_ ? nullptr : (axis == 0 ? nx_ : (axis == 1 ? ny_ : nz_)).data(); }
+  // ... and for the calls that fill a cloud in place (loadPCD)
+  float* xData() { return x_.data(); }
+  float* yData() { return y_.data(); }
+  float* zData() { return z_.data(); }
+  float* intensityData() { return use_intensity_ ? intensity_.data() : nullptr; }
+  uint32_t* rgbData() { return use_color_ ? rgb_.data() : nullptr; }
+  float* normalData(int axis) { return !use_normal_ ? nullptr : (axis == 0 ? nx_ : (axis == 1 ? ny_ : nz_)).data(); }
 
  private:
   static uint32_t pack(const Color& c) { return (uint32_t(c.r) << 16) | (uint32_t(c.g) << 8) | uint32_t(c.b); }
-  HostVector<float> x_, y_, z_, intensity_;
+  HostVector<float> x_, y_, z_, intensity_, nx_, ny_, nz_;
   HostVector<uint32_t> rgb_;  // 0x00RRGGBB
   std::vector<float> cov_;
   std::string frame_id_;
   uint64_t timestamp_ns_ = 0;
-  bool use_intensity_ = false, use_color_ = false, use_cov_ = false;
+  bool use_intensity_ = false, use_color_ = false, use_cov_ = false, use_normal_ = false;
 };
 
 }  // namespace nanopcl

@@ -20,25 +20,7 @@
 
 namespace nanopcl {
 
-// core/types.hpp:19-22 — Eigen::Vector4f there; the same 16 bytes here
-struct alignas(16) Point4 {
-  float v[4];
-  constexpr Point4() : v{0.0f, 0.0f, 0.0f, 0.0f} {}
-  constexpr Point4(float x, float y, float z, float w) : v{x, y, z, w} {}
-  float& x() { return v[0]; }
-  float& y() { return v[1]; }
-  float& z() { return v[2]; }
-  float& w() { return v[3]; }
-  float x() const { return v[0]; }
-  float y() const { return v[1]; }
-  float z() const { return v[2]; }
-  float w() const { return v[3]; }
-  float& operator[](int i) { return v[size_t(i)]; }
-  float operator[](int i) const { return v[size_t(i)]; }
-  float* data() { return v; }
-  const float* data() const { return v; }
-};
-using Normal4 = Point4;
+// (Point4 and Normal4, core/types.hpp:19-22, live in nanopcl/core.hpp: the SoA cloud hands out normals as Normal4)
 static_assert(sizeof(Point4) == 16 && alignof(Point4) == 16, "the engine reads 16-byte records");
 
 struct Time {

@@ -1061,7 +1061,7 @@ void fdm_engine_destroy(fdm_engine* e) {
   if (e->d_image) (void)hipFree(e->d_image);
   if (e->d_render) (void)hipFree(e->d_render);
   for (void* p : {(void*)e->pc_keys[0], (void*)e->pc_keys[1], (void*)e->pc_idx[0], (void*)e->pc_idx[1], (void*)e->pc_hist,
-                  (void*)e->pc_stat, (void*)e->pc_in, (void*)e->pc_out})
+                  (void*)e->pc_stat, (void*)e->pc_in, (void*)e->pc_out, (void*)e->pcd_rec})
     if (p) (void)hipFree(p);
   for (auto& ev : e->pc_ev)
     if (ev) (void)hipEventDestroy(ev);

@@ -41,6 +41,7 @@
 #include "fdm_raster.hpp"
 #include "fdm_knn.hpp"
 #include "fdm_dem.hpp"
+#include "fdm_pcd.hpp"
 #include "fdm_ingest.hpp"
 #include "fdm_post.hpp"
 
@@ -395,6 +396,8 @@ struct fdm_engine {
   size_t pc_in_cap = 0;
   float* pc_out = nullptr;           // toPointCloud's five channels, pc_out_cap points each
   size_t pc_out_cap = 0;
+  uint32_t* pcd_rec = nullptr;       // fdm_engine_to_pcd's packed records, pcd_rec_cap words
+  size_t pcd_rec_cap = 0;
   float pc_ms[3] = {0.f, 0.f, 0.f};  // ids / grouping / walk of the last fromPointCloud (profile on)
   hipEvent_t pc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ... and the events they are taken with (created on first use)
 };

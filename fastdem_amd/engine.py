@@ -597,6 +597,16 @@ class Engine:
                                                        C.byref(hc)))
         return [p.value for p in ptrs], n.value, bool(hi.value), bool(hc.value)
 
+    def to_pcd(self):
+        """The binary data section of nanopcl::io::savePCD(toPointCloud(map)), packed on the device: (bytes, n_points,
+        has_intensity, has_color).  fastdem_amd.pcd.write_header gives the header that goes in front."""
+        cap = self.rows * self.cols * 20
+        buf = np.empty(max(cap, 1), dtype=np.uint8)
+        nb, n, hi, hc = C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_int32(0)
+        rc = _ck(self._lib.fdm_engine_to_pcd(self._h, _ptr(buf), cap, C.byref(nb), C.byref(n), C.byref(hi), C.byref(hc)))
+        assert rc == 0, rc
+        return buf[:nb.value].tobytes(), n.value, bool(hi.value), bool(hc.value)
+
     # -- egress (SURVEY.md §8 f3) --
     def pack_cloud(self, elevation_layer="elevation", sub=None, names_cap=4096):
         """toPointCloud2Impl on the device: (fields, point_step, data[n_points, n_fields] float32).

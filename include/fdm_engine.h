@@ -589,6 +589,79 @@ int fdm_engine_build_dem(uint64_t n, const void* x, const void* y, const void* z
                          const void* rgb, int on_device, const fdm_dem_config* cfg, int device,
                          fdm_engine** out_engine, fdm_dem_stats* stats);
 
+/* PCD files: nanopcl::io::loadPCD / savePCD (nanopcl/io/pcd_io.hpp:243-378, :415-550) and the two calls of the pcd2dem
+ * tool (fastdem/tools/pcd2dem.cpp).  The header and ASCII records are host work; binary records are decoded and packed
+ * on the device, so a file's bytes cross PCIe once and the cloud never exists on the host as arrays. */
+#define FDM_PCD_ASCII 0
+#define FDM_PCD_BINARY 1
+#define FDM_PCD_MAX_FIELDS 64
+typedef struct fdm_pcd_field {  /* detail::PCDFieldInfo (:72-78) */
+  char name[64];                /* lower-cased, NUL-terminated (a longer name is cut: it matches no channel) */
+  char type;                    /* the TYPE token's first character as written: F, U, I or anything else */
+  uint8_t reserved[3];
+  uint32_t size, count, offset; /* offset: the running sum of size * count, uint32 arithmetic */
+} fdm_pcd_field;
+typedef struct fdm_pcd_header {  /* detail::PCDHeader (:80-96) + where the data starts + loadPCD's field choice (:260-281) */
+  fdm_pcd_field fields[FDM_PCD_MAX_FIELDS];
+  int32_t n_fields;
+  uint32_t width, height;       /* the cloud has width * height points (uint32 arithmetic); POINTS is ignored */
+  uint32_t point_size;          /* bytes per binary record */
+  double viewpoint[7];          /* tx ty tz qw qx qy qz; 0 0 0 1 0 0 0 unless VIEWPOINT has at least seven numbers */
+  int32_t format;               /* FDM_PCD_ASCII (also: no DATA line, DATA without or with an unknown word) or FDM_PCD_BINARY */
+  int32_t idx_x, idx_y, idx_z;  /* field indices, -1 = absent */
+  int32_t idx_intensity;        /* the first of intensity, i, reflectivity */
+  int32_t idx_rgb;              /* rgb, else rgba */
+  int32_t idx_nx, idx_ny, idx_nz; /* normal_x / _y / _z, each falling back to nx / ny / nz; a channel only when all three exist */
+  uint64_t data_offset;         /* the byte behind the DATA line's '\n' (n_bytes without one) */
+} fdm_pcd_header;
+/* parseHeader (:114-207) over the first n_bytes of a file; no byte behind them is read, no device is touched.  Lines
+ * that are empty or start with '#' are skipped, tokens split on white space ('\r' included), keys and field names
+ * compared lower-cased; SIZE / TYPE / COUNT lists shorter than FIELDS default to 4 / F / 1.  FDM_ERR_INVALID where the
+ * reference throws or is undefined: no FIELDS, binary_compressed, WIDTH / HEIGHT without a number, a SIZE / COUNT /
+ * WIDTH / HEIGHT / VIEWPOINT token std::stoul / std::stod rejects; and for more than 64 fields. */
+int fdm_pcd_parse_header(const void* bytes, uint64_t n_bytes, fdm_pcd_header* header);
+/* savePCD's header text (:454-488, :491 / :516) for a cloud of n points with these channels; viewpoint NULL = identity,
+ * its numbers are printed with %g.  *n_bytes is the text's length (no NUL is written); FDM_SKIP_BUFFER_TOO_SMALL when
+ * it exceeds cap (nothing is written).  No device is touched. */
+int fdm_pcd_write_header(uint64_t n, int has_intensity, int has_rgb, int has_normal, const double* viewpoint, int format,
+                         char* buf, uint64_t cap, uint64_t* n_bytes);
+/* loadPCD's data section (:296-375): the records at `body` into caller-owned arrays of width * height entries, output
+ * index == record index; any array may be NULL, and a channel the file lacks leaves its array untouched.  No point is
+ * dropped: NaN and infinite values are loaded as they are.  rgb is the 4 bytes at the colour field, as 0x00RRGGBB.
+ * Binary: each value goes through readFieldAsFloat (:209-230) — F4 (bits copied), F8 (rounded to nearest even), U1,
+ * U4, I4; every other type / size pair reads as 0.0f — in the k_pcd_decode kernel; a pageable host body is copied to
+ * the device once, a pinned one (fdm_host_alloc) is read in place when it starts on a 16-byte boundary (copied otherwise), a
+ * device body may start at any byte.  ASCII: one
+ * line per point, the value of a field is the token at the field's index (COUNT is not accounted for, as in the
+ * reference), parsed on the host and uploaded when the outputs are device arrays.
+ * FDM_ERR_INVALID: no x, y or z field; a body shorter than width * height * point_size or with too few lines or
+ * tokens; a token std::stof / std::stoul rejects; and, for binary files, what the reference leaves undefined or this
+ * library does not take: a point_size of 0, a chosen field (the colour field: its 4 bytes) reaching beyond the
+ * record, a point_size above 1024.  Synchronous. */
+int fdm_pcd_decode(const fdm_pcd_header* header, const void* body, uint64_t body_bytes, int body_on_device, float* x,
+                   float* y, float* z, float* intensity, uint32_t* rgb, float* nx, float* ny, float* nz, int out_on_device,
+                   int device);
+/* savePCD's data section (:490-545) for n points into the host buffer `out`: fields x y z, then intensity, rgb
+ * (r << 16 | g << 8 | b: the low 24 bits), normal_x normal_y normal_z, each present iff its array is given (the normals:
+ * all three or none).  The arrays are host (on_device 0) or device arrays.  Binary records (12 to 32 bytes) are packed
+ * by the k_pcd_pack kernel; ASCII lines are written on the host with std::fixed at `precision` (the reference's
+ * default: 8), the colour as a decimal integer.  *n_bytes is the section's size; FDM_SKIP_BUFFER_TOO_SMALL when it
+ * exceeds cap (nothing is written). */
+int fdm_pcd_encode(uint64_t n, const float* x, const float* y, const float* z, const float* intensity, const uint32_t* rgb,
+                   const float* nx, const float* ny, const float* nz, int on_device, int format, int precision, int device,
+                   void* out, uint64_t cap, uint64_t* n_bytes);
+/* buildDEM(loadPCD(file), cfg) (pcd2dem.cpp:38-44): the records are decoded into library-owned device arrays and take
+ * the device path of fdm_engine_build_dem, with its statuses — FDM_SKIP_EMPTY_CLOUD for a file of 0 points, a file with
+ * a coordinate that is not finite is refused by the outlier removal — and those of fdm_pcd_decode. */
+int fdm_pcd_build_dem(const fdm_pcd_header* header, const void* body, uint64_t body_bytes, int body_on_device,
+                      const fdm_dem_config* cfg, int device, fdm_engine** out_engine, fdm_dem_stats* stats);
+/* The binary data section of savePCD(toPointCloud(map)) (pcd2dem.cpp:51-54) into the host buffer `out`:
+ * fdm_engine_to_point_cloud_device, the pack kernel, one download.  Records are x y z [intensity] [rgb] as
+ * *has_intensity / *has_color say; *n_bytes = *n_points * the record size; FDM_SKIP_BUFFER_TOO_SMALL when that exceeds
+ * cap (nothing is written; rows * cols * 20 bytes always suffice). */
+int fdm_engine_to_pcd(fdm_engine* e, void* out, uint64_t cap, uint64_t* n_bytes, uint64_t* n_points, int32_t* has_intensity,
+                      int32_t* has_color);
+
 /* Pinned host memory for input clouds (the arrays fdm_engine_integrate* read in place, see
  * fdm_engine_integrate_async).  Blocks come from a process-wide pool of hipHostMalloc'ed memory in
  * power-of-two size classes — a cloud allocated per sensor message costs a free-list pop, not a

@@ -31,6 +31,13 @@ int fdm_engine_debug_timeline(fdm_engine* e, uint64_t* ticks, uint64_t cap_block
  * pipeline they mean to check. */
 int fdm_engine_debug_batch_launches(fdm_engine* e, uint64_t out[2]);
 
+/* fdm_pcd_debug_profile(1): the calling thread's PCD kernels are timed with device events from now on (off by
+ * default; scripts/pcd_bench.py).  fdm_pcd_debug_last_kernel_ms: ms2[0] the k_pcd_decode launch of the last
+ * fdm_pcd_decode / fdm_pcd_build_dem of a binary file, ms2[1] the k_pcd_pack launch of the last binary fdm_pcd_encode /
+ * fdm_engine_to_pcd; copies are not included; zeros while the switch is off. */
+int fdm_pcd_debug_profile(int on);
+int fdm_pcd_debug_last_kernel_ms(float ms2[2]);
+
 #ifdef __cplusplus
 }
 #endif
