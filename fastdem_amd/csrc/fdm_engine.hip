@@ -46,6 +46,25 @@ int sync_all(fdm_engine* e) {
   poll_dense_paid(e);
   return FDM_OK;
 }
+int grow_device_bytes(fdm_engine* e, void** ptr, size_t* cap, size_t need, size_t want, size_t row_bytes) {
+  if (need <= *cap) return FDM_OK;
+  if (int rc = sync_all(e)) return rc;
+  void* const old = *ptr;
+  *ptr = nullptr;
+  *cap = 0;
+  if (old) HIPCK(hipFree(old));
+  HIPCK(hipMalloc(ptr, want * row_bytes));
+  *cap = want;
+  return FDM_OK;
+}
+int pick_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(FDM_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(FDM_ERR_INVALID, "bad device ordinal");
+  HIPCK(hipSetDevice(device));
+  return FDM_OK;
+}
 // DevState::fault after the stream has drained: a batch launch whose in-kernel wait for the scans ahead ran out of
 // polls (fdm_multi.hpp).  Sticky on the device until it has been reported ONCE — the maps of that
 // batch are undefined, reset() and go on.  Only looked at when such a launch was enqueued since the last look.
@@ -833,11 +852,7 @@ static int create_impl(const fdm_geometry* g, const fdm_config* cfg, const fdm_t
   if (!g || !cfg || !out) return fail(FDM_ERR_INVALID, "null argument");
   if (!(g->resolution > 0.0) || !(g->length_x > 0.0) || !(g->length_y > 0.0))
     return fail(FDM_ERR_INVALID, "length and resolution must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FDM_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(FDM_ERR_INVALID, "bad device ordinal");
-  HIPCK(hipSetDevice(device));
+  if (int rc = pick_device(device)) return rc;
 
   fdm_engine* e = new fdm_engine();
   e->device = device;

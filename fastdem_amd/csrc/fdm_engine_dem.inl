@@ -1,83 +1,22 @@
 // fdm_engine_dem.inl — host side of buildDEM (pcd_convert.cpp:275-323) and of its two filter stages: statistical outlier
 // removal (fdm_knn.hpp; nanoPCL outlier_removal_impl.hpp:83-142) and floating-point removal (fdm_dem.hpp).
-// Part of fdm_engine_post.hip, behind fdm_engine_raster.inl, whose helpers it uses.  Offline calls: synchronous, scratch
+// Part of fdm_engine_post.hip, behind fdm_engine_cloud.inl (DevBuf, Events, the cloud staging, map_over_cloud) and
+// fdm_engine_raster.inl (whole_map, the rasterization entry), whose helpers it uses.  Offline calls: synchronous, scratch
 // is allocated per call and freed on return; the stages before a map exists run on the null stream.
 
 namespace {
-struct DevBuf {  // a device allocation that lives as long as its scope
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    HIPCK(hipMalloc(&p, bytes ? bytes : 4));
-    return FDM_OK;
-  }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-struct Events {
-  hipEvent_t ev[12] = {};
-  ~Events() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
-  int init(int count) {
-    for (int k = 0; k < count; ++k) HIPCK(hipEventCreate(&ev[k]));
-    return FDM_OK;
-  }
-  float ms(int a, int b) const {
-    float t = 0.f;
-    return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.f;
-  }
-};
-
-// the two sides of a radix sort of n (key, index) pairs and its histograms (fdm_rsort.hpp)
+// the two sides of a radix sort of n (key, index) pairs and its histograms (fdm_rsort.hpp), in one allocation
 struct SortBufs {
   DevBuf mem;
-  uint32_t* keys[2] = {nullptr, nullptr};
-  uint32_t* idx[2] = {nullptr, nullptr};
-  uint32_t* hist = nullptr;
+  RsPairs<uint32_t> pairs{};
   int alloc(unsigned n) {
-    const size_t cap = (size_t(n) + 3) & ~size_t(3);
-    const size_t tiles = (size_t(n) + rs_tile(n) - 1) / rs_tile(n);
-    if (int rc = mem.alloc((4 * cap + 256 * tiles + 256) * sizeof(uint32_t))) return rc;
+    const size_t cap = cloud_stride(n);
+    if (int rc = mem.alloc((4 * cap + rs_hist_words(n)) * sizeof(uint32_t))) return rc;
     uint32_t* const b = mem.as<uint32_t>();
-    keys[0] = b; keys[1] = b + cap; idx[0] = b + 2 * cap; idx[1] = b + 3 * cap; hist = b + 4 * cap;
+    pairs = {{b, b + cap}, {b + 2 * cap, b + 3 * cap}, b + 4 * cap};
     return FDM_OK;
   }
 };
-// stable sort of (keys[0], idx[0] or the position) by the low `bits` bits; returns the side the result is on
-template <unsigned TILE>
-int dem_sort_t(hipStream_t s, const SortBufs& B, unsigned n, unsigned bits, bool has_idx) {
-  const unsigned tiles = (n + TILE - 1u) / TILE;
-  uint32_t* const total = B.hist + size_t(256) * tiles;
-  int src = 0;
-  for (unsigned shift = 0; shift < bits; shift += 8u, src ^= 1) {
-    hipLaunchKernelGGL((k_rs_hist<uint32_t, TILE>), dim3(tiles), dim3(256), 0, s, n, B.keys[src], shift, tiles, B.hist);
-    hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, tiles, B.hist, total);
-    if (shift || has_idx)
-      hipLaunchKernelGGL((k_rs_scatter<uint32_t, true, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, s, n, B.keys[src],
-                         B.idx[src], B.keys[src ^ 1], B.idx[src ^ 1], shift, tiles, B.hist, total);
-    else
-      hipLaunchKernelGGL((k_rs_scatter<uint32_t, false, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, s, n,
-                         B.keys[src], static_cast<const uint32_t*>(nullptr), B.keys[src ^ 1], B.idx[src ^ 1], shift,
-                         tiles, B.hist, total);
-  }
-  return src;
-}
-int dem_sort(hipStream_t s, const SortBufs& B, unsigned n, unsigned bits, bool has_idx) {
-  return rs_tile(n) == kRsTileSmall ? dem_sort_t<kRsTileSmall>(s, B, n, bits, has_idx)
-                                    : dem_sort_t<kRsTile>(s, B, n, bits, has_idx);
-}
-unsigned bits_of(uint64_t max_value) {  // bits a key of 0 .. max_value needs, at least one
-  unsigned bits = 1;
-  while (bits < 32u && (max_value >> bits) != 0u) ++bits;
-  return bits;
-}
-float unord_h(uint32_t u) {
-  const uint32_t b = u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu);
-  float f;
-  std::memcpy(&f, &b, sizeof(f));
-  return f;
-}
 
 thread_local fdm_sor_stats g_sor_stats = {};
 
@@ -145,7 +84,8 @@ int sor_device(hipStream_t s, unsigned n, const float* dx, const float* dy, cons
   HIPCK(hipStreamSynchronize(s));
   if (hs.nonfinite)
     return fail(FDM_ERR_INVALID, "the cloud has a coordinate that is not finite (undefined in the reference's k-d tree)");
-  const KnnGrid G = sor_grid(unord_h(hs.min_x), unord_h(hs.min_y), unord_h(hs.max_x), unord_h(hs.max_y), n, unsigned(k));
+  const KnnGrid G = sor_grid(unord_host(hs.min_x), unord_host(hs.min_y), unord_host(hs.max_x), unord_host(hs.max_y), n,
+                             unsigned(k));
   const unsigned ncol = unsigned(G.gx) * unsigned(G.gy);
   g_sor_stats.grid_x = G.gx;
   g_sor_stats.grid_y = G.gy;
@@ -156,10 +96,10 @@ int sor_device(hipStream_t s, unsigned n, const float* dx, const float* dy, cons
   if (int rc = b_pts.alloc(size_t(n) * sizeof(float4))) return rc;
   if (int rc = b_start.alloc((size_t(ncol) + 1) * sizeof(uint32_t))) return rc;
   if (int rc = b_queue.alloc(size_t(n) * sizeof(uint32_t))) return rc;
-  hipLaunchKernelGGL(k_knn_keys, dim3(blocks), dim3(256), 0, s, n, dx, dy, G, S.keys[0]);
-  const int side = dem_sort(s, S, n, bits_of(ncol - 1u), false);
-  hipLaunchKernelGGL(k_knn_gather, dim3(blocks), dim3(256), 0, s, n, S.idx[side], dx, dy, dz, b_pts.as<float4>());
-  hipLaunchKernelGGL(k_knn_starts, dim3((ncol + 1u + 255u) / 256u), dim3(256), 0, s, n, S.keys[side], ncol,
+  hipLaunchKernelGGL(k_knn_keys, dim3(blocks), dim3(256), 0, s, n, dx, dy, G, S.pairs.keys[0]);
+  const int side = rs_enqueue(s, S.pairs, n, rs_key_bits(ncol - 1u));
+  hipLaunchKernelGGL(k_knn_gather, dim3(blocks), dim3(256), 0, s, n, S.pairs.idx[side], dx, dy, dz, b_pts.as<float4>());
+  hipLaunchKernelGGL(k_knn_starts, dim3((ncol + 1u + 255u) / 256u), dim3(256), 0, s, n, S.pairs.keys[side], ncol,
                      b_start.as<uint32_t>());
   HIPCK(hipGetLastError());
   HIPCK(hipEventRecord(E.ev[1], s));
@@ -251,12 +191,13 @@ int height_filter_device(fdm_engine* e, unsigned n, const float* dx, const float
   if (hs.bad)
     return fail(FDM_ERR_INVALID, "a cell's z range over the bin size does not fit an int32 (undefined in the reference)");
   // by bin, then (stable) by cell: the pairs end up ordered by (cell, bin, index)
-  HIPCK(hipMemcpyAsync(S.keys[0], bins, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-  const int side1 = dem_sort(s, S, n, bits_of(hs.max_bin), false);
-  if (side1 != 0) HIPCK(hipMemcpyAsync(S.idx[0], S.idx[side1], size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(k_dem_gather_u32, dim3(blocks), dim3(256), 0, s, n, S.idx[0], cell, S.keys[0]);
-  const int side2 = dem_sort(s, S, n, bits_of(ncell), true);
-  hipLaunchKernelGGL(k_hf_peak, dim3(blocks), dim3(256), 0, s, n, S.keys[side2], S.idx[side2], ncell, bins, cmin, bin,
+  const RsPairs<uint32_t>& B = S.pairs;
+  HIPCK(hipMemcpyAsync(B.keys[0], bins, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  const int side1 = rs_enqueue(s, B, n, rs_key_bits(hs.max_bin));
+  if (side1 != 0) HIPCK(hipMemcpyAsync(B.idx[0], B.idx[side1], size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(k_dem_gather_u32, dim3(blocks), dim3(256), 0, s, n, B.idx[0], cell, B.keys[0]);
+  const int side2 = rs_enqueue(s, B, n, rs_key_bits(ncell), 0, kRsIdxGiven);
+  hipLaunchKernelGGL(k_hf_peak, dim3(blocks), dim3(256), 0, s, n, B.keys[side2], B.idx[side2], ncell, bins, cmin, bin,
                      height_threshold, cmax);
   hipLaunchKernelGGL(k_hf_keep, dim3(blocks), dim3(256), 0, s, n, cell, dz, ncell, cmax, d_keep, st);
   HIPCK(hipGetLastError());
@@ -278,15 +219,6 @@ int compact_device(hipStream_t s, unsigned n, const uint8_t* d_keep, const float
   hipLaunchKernelGGL(k_dem_compact, dim3(blocks), dim3(256), 0, s, n, d_keep, b_counts.as<uint32_t>(), C);
   HIPCK(hipGetLastError());
   HIPCK(hipStreamSynchronize(s));
-  return FDM_OK;
-}
-
-int pick_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FDM_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(FDM_ERR_INVALID, "bad device ordinal");
-  HIPCK(hipSetDevice(device));
   return FDM_OK;
 }
 }  // namespace
@@ -317,8 +249,7 @@ int fdm_statistical_outlier_removal(uint64_t n, const float* x, const float* y, 
   *threshold = 0.0f;
   *n_kept = 0;
   g_sor_stats = fdm_sor_stats{};
-  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
-  if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null coordinate array");
+  if (int rc = check_cloud(n, x, y, z)) return rc;
   const uint64_t k_eff = sor_effective_k(n, k);
   if (k_eff > uint64_t(kKnnMaxK)) return fail(FDM_ERR_INVALID, "statistical outlier removal takes at most 64 neighbours");
   if (n == 0) return FDM_OK;
@@ -334,17 +265,11 @@ int fdm_statistical_outlier_removal(uint64_t n, const float* x, const float* y, 
     }
     return FDM_OK;
   }
-  DevBuf b_in, b_mean, b_keep;
-  const float* d[3] = {x, y, z};
-  if (!on_device) {
-    const size_t cap = (size_t(n) + 3) & ~size_t(3);
-    if (int rc = b_in.alloc(cap * 3 * sizeof(float))) return rc;
-    const float* src[3] = {x, y, z};
-    for (int q = 0; q < 3; ++q) {
-      HIPCK(hipMemcpy(b_in.as<float>() + cap * size_t(q), src[q], size_t(n) * sizeof(float), hipMemcpyHostToDevice));
-      d[q] = b_in.as<float>() + cap * size_t(q);
-    }
-  }
+  CloudBlock b_in;
+  DevBuf b_mean, b_keep;
+  const void* const src[3] = {x, y, z};
+  const float* d[3];
+  if (int rc = stage_cloud(nullptr, n, 3, src, on_device != 0, b_in, d)) return rc;
   float* d_mean = mean_dist;
   uint8_t* d_keep = keep;
   if (!on_device || !mean_dist) {
@@ -370,25 +295,19 @@ int fdm_engine_remove_floating_points(fdm_engine* e, uint64_t n, const float* x,
   if (!e || !keep || !n_kept) return fail(FDM_ERR_INVALID, "null argument");
   *n_kept = 0;
   if (!whole_map(e)) return fail(FDM_ERR_INVALID, "removeFloatingPoints is not defined for tiled engines");
-  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
-  if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null coordinate array");
+  if (int rc = check_cloud(n, x, y, z)) return rc;
   const float bin = bin_size > 0.0f ? bin_size : float(e->G.res);  // pcd_convert.cpp:308-309
   if (!(bin > 0.0f) || !std::isfinite(bin)) return fail(FDM_ERR_INVALID, "the bin size must be positive");
   if (n == 0) return FDM_OK;
   HIPCK(hipSetDevice(e->device));
-  DevBuf b_in, b_keep;
-  const float* d[3] = {x, y, z};
+  CloudBlock b_in;
+  DevBuf b_keep;
+  const void* const src[3] = {x, y, z};
+  const float* d[3];
+  if (int rc = stage_cloud(e->stream, n, 3, src, on_device != 0, b_in, d)) return rc;
   uint8_t* d_keep = keep;
   if (!on_device) {
-    const size_t cap = (size_t(n) + 3) & ~size_t(3);
-    if (int rc = b_in.alloc(cap * 3 * sizeof(float))) return rc;
     if (int rc = b_keep.alloc(size_t(n))) return rc;
-    const float* src[3] = {x, y, z};
-    for (int q = 0; q < 3; ++q) {
-      HIPCK(hipMemcpyAsync(b_in.as<float>() + cap * size_t(q), src[q], size_t(n) * sizeof(float), hipMemcpyHostToDevice,
-                           e->stream));
-      d[q] = b_in.as<float>() + cap * size_t(q);
-    }
     d_keep = b_keep.as<uint8_t>();
   }
   if (int rc = height_filter_device(e, unsigned(n), d[0], d[1], d[2], height_threshold, bin, d_keep, n_kept)) return rc;
@@ -413,10 +332,8 @@ int fdm_engine_build_dem(uint64_t n, const void* x, const void* y, const void* z
   fdm_default_dem_config(&c);
   if (cfg) c = *cfg;
   if (n == 0) return FDM_SKIP_EMPTY_CLOUD;  // :276 `return {}`: no map
-  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
-  if (c.method < 0 || c.method > 3) return fail(FDM_ERR_INVALID, "method must be 0 (Max), 1 (Min), 2 (Mean) or 3 (MinMax)");
-  if (!x || !y || !z) return fail(FDM_ERR_INVALID, "null coordinate array");
-  if (!(c.resolution > 0.0f) || !std::isfinite(c.resolution)) return fail(FDM_ERR_INVALID, "resolution must be positive");
+  if (int rc = check_cloud(n, x, y, z, c.method)) return rc;
+  if (int rc = check_resolution(c.resolution)) return rc;
   const float bin = c.bin_size > 0.0f ? c.bin_size : c.resolution;  // :308-309
   if (!std::isfinite(bin)) return fail(FDM_ERR_INVALID, "the bin size must be finite");
   const uint64_t k_eff = sor_effective_k(n, c.sor_k);
@@ -427,22 +344,13 @@ int fdm_engine_build_dem(uint64_t n, const void* x, const void* y, const void* z
   Events E;
   if (int rc = E.init(8)) return rc;
   // 0. the cloud on the device
-  const void* src[5] = {x, y, z, intensity, rgb};
-  const float* ch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  DevBuf b_stage;
-  if (on_device) {
-    for (int q = 0; q < 5; ++q) ch[q] = static_cast<const float*>(src[q]);
-  } else {
-    const size_t cap = (size_t(n) + 3) & ~size_t(3);
-    if (int rc = b_stage.alloc(cap * 5 * sizeof(float))) return rc;
-    for (int q = 0; q < 5; ++q) {
-      if (!src[q]) continue;
-      HIPCK(hipMemcpy(b_stage.as<float>() + cap * size_t(q), src[q], size_t(n) * sizeof(float), hipMemcpyHostToDevice));
-      ch[q] = b_stage.as<float>() + cap * size_t(q);
-    }
-  }
+  const void* const src[5] = {x, y, z, intensity, rgb};
+  const float* ch[5];
+  CloudBlock b_stage;
+  if (int rc = stage_cloud(nullptr, n, 5, src, on_device != 0, b_stage, ch)) return rc;
   // 1. statistical outlier removal (:279-282)
-  DevBuf b_mean, b_keep, b_a;
+  DevBuf b_mean, b_keep;
+  CloudBlock b_a;
   if (int rc = b_mean.alloc(size_t(n) * sizeof(float))) return rc;
   if (int rc = b_keep.alloc(size_t(n))) return rc;
   if (int rc = sor_device(nullptr, np, ch[0], ch[1], ch[2], int(k_eff), c.sor_std_mul, b_mean.as<float>(),
@@ -452,51 +360,32 @@ int fdm_engine_build_dem(uint64_t n, const void* x, const void* y, const void* z
   for (int q = 0; q < 4; ++q) S.stage_ms[q] = g_sor_stats.ms[q];
   if (S.n_after_sor == 0) return FDM_SKIP_ALL_FILTERED;
   const unsigned n1 = unsigned(S.n_after_sor);
-  const size_t cap1 = (size_t(n1) + 3) & ~size_t(3);
-  if (int rc = b_a.alloc(cap1 * 5 * sizeof(float))) return rc;
+  if (int rc = b_a.alloc(n1, 5)) return rc;
   const float* a[5];
   float* a_out[5];
   for (int q = 0; q < 5; ++q) {
-    a_out[q] = b_a.as<float>() + cap1 * size_t(q);
+    a_out[q] = b_a.ch(q);
     a[q] = ch[q] ? a_out[q] : nullptr;
   }
   if (int rc = compact_device(nullptr, np, b_keep.as<uint8_t>(), ch, a_out)) return rc;
-  // 2. the map over the survivors' bounding box (:285-305), as fdm_engine_create_from_point_cloud sizes it
-  DevBuf b_rstat;
-  if (int rc = b_rstat.alloc(sizeof(RasterStat))) return rc;
-  hipLaunchKernelGGL(k_ras_stat_init, dim3(1), dim3(64), 0, nullptr, b_rstat.as<RasterStat>());
-  hipLaunchKernelGGL(k_ras_bounds, dim3(std::min((n1 + 255u) / 256u, 2048u)), dim3(256), 0, nullptr, n1, a[0], a[1],
-                     b_rstat.as<RasterStat>());
-  HIPCK(hipGetLastError());
-  RasterStat hs{};
-  HIPCK(hipMemcpy(&hs, b_rstat.as<RasterStat>(), sizeof(hs), hipMemcpyDeviceToHost));
-  const float min_x = unord_h(hs.min_x), min_y = unord_h(hs.min_y), max_x = unord_h(hs.max_x), max_y = unord_h(hs.max_y);
-  const float width = max_x - min_x + c.resolution, height = max_y - min_y + c.resolution;
-  if (!std::isfinite(width) || !std::isfinite(height) || !(width > 0.0f) || !(height > 0.0f))
-    return fail(FDM_ERR_INVALID, "the cloud's x / y extent is not a positive finite number");
-  fdm_geometry g{};
-  g.length_x = double(width);
-  g.length_y = double(height);
-  g.resolution = double(c.resolution);
-  g.position_x = double(min_x + max_x) / 2.0;
-  g.position_y = double(min_y + max_y) / 2.0;
+  // 2. the map over the survivors' bounding box (:285-305)
   fdm_engine* e = nullptr;
-  if (int rc = fdm_engine_create_map(&g, nullptr, device, &e)) return rc;
+  if (int rc = map_over_cloud(n1, a[0], a[1], c.resolution, device, &e)) return rc;
   auto drop = [&](int rc) { fdm_engine_destroy(e); return rc; };
   // 3. floating-point removal (:308-311)
-  DevBuf b_keep2, b_b;
+  DevBuf b_keep2;
+  CloudBlock b_b;
   if (int rc = b_keep2.alloc(size_t(n1))) return drop(rc);
   (void)hipEventRecord(E.ev[0], e->stream);
   if (int rc = height_filter_device(e, n1, a[0], a[1], a[2], c.height_threshold, bin, b_keep2.as<uint8_t>(),
                                     &S.n_after_height))
     return drop(rc);
   const unsigned n2 = unsigned(S.n_after_height);
-  const size_t cap2 = (size_t(n2) + 3) & ~size_t(3);
-  if (int rc = b_b.alloc(cap2 * 5 * sizeof(float))) return drop(rc);
+  if (int rc = b_b.alloc(n2, 5)) return drop(rc);
   const float* b[5];
   float* b_out[5];
   for (int q = 0; q < 5; ++q) {
-    b_out[q] = b_b.as<float>() + cap2 * size_t(q);
+    b_out[q] = b_b.ch(q);
     b[q] = a[q] ? b_out[q] : nullptr;
   }
   if (n2)

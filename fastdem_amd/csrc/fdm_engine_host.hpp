@@ -182,8 +182,7 @@ struct RayBank {
   uint32_t* vsel = nullptr;          // voxel_any output staging
   uint32_t* ray_blk = nullptr;       // rays queued per block of k_ray_compact (large scans: block-local queue regions)
   size_t vcap = 0;                   // points the voxel / queue buffers hold
-  void* sort_tmp = nullptr;          // the radix sort's histograms (fdm_rsort.hpp)
-  size_t sort_tmp_bytes = 0;
+  uint32_t* sort_tmp = nullptr;      // the radix sort's histograms (fdm_rsort.hpp: rs_hist_words(vcap))
   void* is_buf = nullptr;            // fdm_introsort.hpp's level buffers, rank tables, segment lists (is_layout)
   size_t is_cap = 0;                 // pairs is_buf is laid out for
   hipStream_t stream = nullptr;      // where the bank's early parts run (ensure_ray_streams)
@@ -192,7 +191,7 @@ struct RayBank {
   bool res_pending = false;          // ev_res has been recorded
   void release() {                   // (fdm_engine_destroy: nothing is in flight)
     for (void* p : {(void*)rc_cnt, (void*)rc_min, (void*)ray_bins, (void*)vkeys[0], (void*)vkeys[1], (void*)vidx[0],
-                    (void*)vidx[1], (void*)vsel, (void*)ray_blk, sort_tmp, is_buf})
+                    (void*)vidx[1], (void*)vsel, (void*)ray_blk, (void*)sort_tmp, is_buf})
       if (p) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
     for (hipEvent_t ev : {ev_pre, ev_res})
@@ -361,7 +360,7 @@ struct fdm_engine {
   RegionEntry* d_region = nullptr;   // region_cap entries
   size_t region_cap = 0;
   float* d_post_pool = nullptr;      // per-thread lists of the big-neighbourhood stencil kernels
-  size_t post_pool_bytes = 0;
+  size_t post_pool_cap = 0;          // in floats
   FeatEntry* d_feat_tab = nullptr;   // kMaxRegion entries: the region as k_features_tiled reads it
   std::vector<RegionEntry> h_region; // what d_region holds (upload_region skips an identical table)
   std::vector<FeatEntry> h_feat_tab; // what d_feat_tab holds
@@ -407,6 +406,15 @@ namespace fdmh {
 int join_streams(fdm_engine* e);  // (a null engine: FDM_OK — every C entry point starts with it, ahead of its null checks)
 void poll_dense_paid(fdm_engine* e);
 int sync_all(fdm_engine* e);
+int pick_device(int device);  // the ordinal checked against the devices there are, then made current
+// An engine-owned buffer that grows on demand: nothing if need <= *cap; else everything drains (sync_all), the old buffer
+// is freed and forgotten (*ptr null, *cap 0: a failed allocation leaves an empty buffer, never a stale one), and `want`
+// rows of `per` elements are allocated; *cap counts rows.  The contents are not kept.
+int grow_device_bytes(fdm_engine* e, void** ptr, size_t* cap, size_t need, size_t want, size_t row_bytes);
+template <typename T>
+int grow_device(fdm_engine* e, T** ptr, size_t* cap, size_t need, size_t want, size_t per = 1) {
+  return grow_device_bytes(e, reinterpret_cast<void**>(ptr), cap, need, want, per * sizeof(T));
+}
 Layer* find_layer(fdm_engine* e, const char* name);
 float* lptr(fdm_engine* e, const Layer& l);
 int lstride(fdm_engine* e, const Layer& l);

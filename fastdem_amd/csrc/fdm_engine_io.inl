@@ -1,5 +1,6 @@
 // fdm_engine_io.inl — host side of PointCloud2 ingest (fdm_ingest.hpp) and map egress (fdm_egress.hpp).
-// Part of fdm_engine_post.hip (one of the library's five translation units, fdm_engine_host.hpp).
+// Part of fdm_engine_post.hip (one of the library's five translation units, fdm_engine_host.hpp), behind
+// fdm_engine_cloud.inl (ensure_pack_counts, the channel stride).
 
 namespace {
 // fdm_cloud2_layout -> IngestLayout; L.aligned covers the record layout only (the caller adds the blob's address)
@@ -18,6 +19,10 @@ int check_cloud2_layout(const fdm_cloud2_layout* lay, IngestLayout& L) {
   L.aligned = (step & 3u) == 0 && al4(L.off_x) && al4(L.off_y) && al4(L.off_z) && al4(L.off_rgb) &&
               (L.intensity_type < 7 || al4(L.off_intensity));
   return FDM_OK;
+}
+// the raw bytes of a host message on the device
+int ensure_blob(fdm_engine* e, size_t bytes) {
+  return grow_device(e, &e->d_blob, &e->blob_cap, bytes, bytes + bytes / 4 + 4096);
 }
 }  // namespace
 
@@ -42,29 +47,14 @@ int fdm_engine_ingest_cloud2(fdm_engine* e, const void* data, int on_device, uin
   const size_t bytes = size_t(n_points) * step;
   const uint8_t* blob = static_cast<const uint8_t*>(data);
   if (!on_device) {
-    if (bytes > e->blob_cap) {
-      if (int rc_sync = sync_all(e)) return rc_sync;
-      if (e->d_blob) HIPCK(hipFree(e->d_blob));
-      e->blob_cap = bytes + bytes / 4 + 4096;
-      HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_blob), e->blob_cap));
-    }
+    if (int rc_blob = ensure_blob(e, bytes)) return rc_blob;
     HIPCK(hipMemcpyAsync(e->d_blob, data, bytes, hipMemcpyHostToDevice, e->stream));
     blob = e->d_blob;
   }
-  if (n_points > e->in_cap) {
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->d_in) HIPCK(hipFree(e->d_in));
-    e->in_cap = ((n_points + n_points / 4 + 1024) + 3) & ~size_t(3);  // channels stay 16-byte aligned
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_in), e->in_cap * 5 * sizeof(float)));
-  }
+  if (int rc_in = grow_device(e, &e->d_in, &e->in_cap, size_t(n_points), cloud_cap(size_t(n_points)), 5)) return rc_in;
   L.aligned = L.aligned && (reinterpret_cast<uintptr_t>(blob) & 3u) == 0;
   const unsigned blocks = unsigned((n_points + 255) / 256);
-  if (size_t(blocks) + 1 > e->pack_counts_cap) {
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->pack_counts) HIPCK(hipFree(e->pack_counts));
-    e->pack_counts_cap = size_t(blocks) + 1 + 1024;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->pack_counts), e->pack_counts_cap * sizeof(uint32_t)));
-  }
+  if (int rc_cnt = ensure_pack_counts(e, blocks)) return rc_cnt;
   const bool hi = lay->off_intensity >= 0, hc = lay->off_rgb >= 0;
   hipLaunchKernelGGL(k_ingest_count, dim3(blocks), dim3(256), 0, e->stream, blob, L, n_points, e->pack_counts);
   hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, e->stream, e->pack_counts, blocks);
@@ -123,12 +113,7 @@ int fdm_engine_integrate_cloud2(fdm_engine* e, const void* data, int on_device, 
     if (alias) {
       blob = static_cast<const uint8_t*>(alias);
     } else {
-      if (bytes > e->blob_cap) {
-        if (int rc_sync = sync_all(e)) return rc_sync;
-        if (e->d_blob) HIPCK(hipFree(e->d_blob));
-        e->blob_cap = bytes + bytes / 4 + 4096;
-        HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_blob), e->blob_cap));
-      }
+      if (int rc_blob = ensure_blob(e, bytes)) return rc_blob;
       HIPCK(hipMemcpyAsync(e->d_blob, data, bytes, hipMemcpyHostToDevice, e->stream));
       blob = e->d_blob;
     }
@@ -137,12 +122,7 @@ int fdm_engine_integrate_cloud2(fdm_engine* e, const void* data, int on_device, 
   StageSlot slot;
   if ((rc = next_stage_slot(e, n_points, &slot))) return rc;
   const unsigned blocks = unsigned((n_points + 255) / 256);
-  if (size_t(blocks) + 1 > e->pack_counts_cap) {
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->pack_counts) HIPCK(hipFree(e->pack_counts));
-    e->pack_counts_cap = size_t(blocks) + 1 + 1024;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->pack_counts), e->pack_counts_cap * sizeof(uint32_t)));
-  }
+  if (int rc_cnt = ensure_pack_counts(e, blocks)) return rc_cnt;
   const bool hi = lay->off_intensity >= 0, hc = lay->off_rgb >= 0;
   hipLaunchKernelGGL(k_ingest_soa, dim3(blocks), dim3(256), 0, e->stream, blob, L, n_points, e->pack_counts, slot.x(),
                      slot.y(), slot.z(), hi ? slot.intensity() : nullptr, hc ? slot.rgb() : nullptr);
@@ -211,12 +191,7 @@ int plan_pack(fdm_engine* e, const char* elevation_layer, int32_t r0, int32_t c0
 int pack_count(fdm_engine* e, const PackPlan& pl, uint64_t* n_points) {
   *n_points = 0;
   if (pl.total == 0) return FDM_OK;
-  if (size_t(pl.blocks) + 1 > e->pack_counts_cap) {
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->pack_counts) HIPCK(hipFree(e->pack_counts));
-    e->pack_counts_cap = size_t(pl.blocks) + 1 + 1024;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->pack_counts), e->pack_counts_cap * sizeof(uint32_t)));
-  }
+  if (int rc_cnt = ensure_pack_counts(e, pl.blocks)) return rc_cnt;
   hipLaunchKernelGGL(k_pack_count, dim3(pl.blocks), dim3(256), 0, e->stream, pl.Q, e->G, e->d_state, pl.L,
                      e->pack_counts);
   hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, e->stream, e->pack_counts, pl.blocks);
@@ -230,11 +205,7 @@ int pack_count(fdm_engine* e, const PackPlan& pl, uint64_t* n_points) {
 
 int pack_write(fdm_engine* e, const PackPlan& pl, uint64_t n_points) {
   const size_t need = size_t(n_points) * pl.fields.size();
-  if (need > e->pack_cap) {
-    if (e->d_pack) HIPCK(hipFree(e->d_pack));
-    e->pack_cap = need + need / 8 + 1024;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_pack), e->pack_cap * sizeof(float)));
-  }
+  if (int rc_pack = grow_device(e, &e->d_pack, &e->pack_cap, need, need + need / 8 + 1024)) return rc_pack;
   if (n_points == 0) return FDM_OK;
   // the kernel's whole LDS (it has no static part): up to 69 648 B of the CU's 160 KB, above 64 KB from 64 fields on
   const unsigned lds = pack_write_lds_bytes(unsigned(pl.fields.size()));

@@ -1,7 +1,8 @@
 // fdm_engine_pcd.inl — host side of the PCD file codec (nanopcl/io/pcd_io.hpp: loadPCD :243-378, savePCD :415-550) and of
-// the pcd2dem tool's two calls (fastdem/tools/pcd2dem.cpp).  Part of fdm_engine_post.hip, behind fdm_engine_dem.inl, whose
-// DevBuf and pick_device it uses.  The header and ASCII records are host work (fdm_pcd_host.hpp); binary records are
-// decoded and packed on the device (fdm_pcd.hpp).  Offline calls: synchronous, scratch is allocated per call.
+// the pcd2dem tool's two calls (fastdem/tools/pcd2dem.cpp).  Part of fdm_engine_post.hip, behind fdm_engine_cloud.inl
+// (DevBuf, Events, the cloud staging) and fdm_engine_dem.inl (buildDEM), which it uses.  The header and ASCII records
+// are host work (fdm_pcd_host.hpp); binary records are decoded and packed on the device (fdm_pcd.hpp).  Offline calls:
+// synchronous, scratch is allocated per call.
 
 #include "fdm_pcd_host.hpp"
 
@@ -132,7 +133,8 @@ int pcd_decode_impl(const fdm_pcd_header* h, const void* body, uint64_t body_byt
   const uint64_t need = uint64_t(n) * h->point_size;
   if (body_bytes < need) return fail(FDM_ERR_INVALID, "Unexpected end of binary data");
   if (int rc = pick_device(device)) return rc;
-  DevBuf b_body, b_out;
+  DevBuf b_body;
+  CloudBlock b_out;
   const uint8_t* d_body = static_cast<const uint8_t*>(body);
   if (!body_on_device) {
     const void* alias = pinned_alias(body);
@@ -144,10 +146,9 @@ int pcd_decode_impl(const fdm_pcd_header* h, const void* body, uint64_t body_byt
       d_body = b_body.as<uint8_t>();
     }
   }
-  const size_t cap = (size_t(n) + 3) & ~size_t(3);
   if (!out_on_device)
-    if (int rc = b_out.alloc(cap * 8 * sizeof(float))) return rc;
-  for (int k = 0; k < 8; ++k) D.out[k] = !want[k] ? nullptr : (out_on_device ? want[k] : b_out.as<float>() + cap * size_t(k));
+    if (int rc = b_out.alloc(n, 8)) return rc;
+  for (int k = 0; k < 8; ++k) D.out[k] = !want[k] ? nullptr : (out_on_device ? want[k] : b_out.ch(k));
   if (int rc = pcd_decode_launch(d_body, D, fields_aligned, n)) return rc;
   if (!out_on_device)
     for (int k = 0; k < 8; ++k)
@@ -221,8 +222,7 @@ int fdm_pcd_encode(uint64_t n, const float* x, const float* y, const float* z, c
   if (!n_bytes) return fail(FDM_ERR_INVALID, "null argument");
   *n_bytes = 0;
   if (format != FDM_PCD_ASCII && format != FDM_PCD_BINARY) return fail(FDM_ERR_INVALID, "format must be 0 (ascii) or 1 (binary)");
-  if (n >= kRasMaxPoints) return fail(FDM_ERR_INVALID, "point count exceeds 2^31-1");
-  if (n && (!x || !y || !z)) return fail(FDM_ERR_INVALID, "null coordinate array");
+  if (int rc = check_cloud(n, x, y, z)) return rc;
   const bool has_normal = nx && ny && nz;
   if (!has_normal && (nx || ny || nz)) return fail(FDM_ERR_INVALID, "the normal channel takes all three arrays or none");
   const void* ch[8] = {x, y, z, intensity, rgb, has_normal ? nx : nullptr, has_normal ? ny : nullptr, has_normal ? nz : nullptr};
@@ -233,19 +233,10 @@ int fdm_pcd_encode(uint64_t n, const float* x, const float* y, const float* z, c
     *n_bytes = n * uint64_t(n_words) * 4;
     if (!out || *n_bytes > cap) return FDM_SKIP_BUFFER_TOO_SMALL;
     if (int rc = pick_device(device)) return rc;
-    DevBuf b_in;
+    CloudBlock b_in;
     PcdPack P{};
     P.n_words = n_words;
-    for (int k = 0; k < 8; ++k) P.ch[k] = ch[k];
-    if (!on_device) {
-      const size_t capn = (size_t(n) + 3) & ~size_t(3);
-      if (int rc = b_in.alloc(capn * 8 * sizeof(float))) return rc;
-      for (int k = 0; k < 8; ++k) {
-        if (!ch[k]) continue;
-        HIPCK(hipMemcpy(b_in.as<float>() + capn * size_t(k), ch[k], size_t(n) * 4, hipMemcpyHostToDevice));
-        P.ch[k] = b_in.as<float>() + capn * size_t(k);
-      }
-    }
+    if (int rc = stage_cloud(nullptr, n, 8, ch, on_device != 0, b_in, P.ch)) return rc;
     DevBuf b_rec;
     if (int rc = b_rec.alloc(size_t(*n_bytes))) return rc;
     return pcd_pack_download(nullptr, n, P, b_rec.as<uint32_t>(), out);
@@ -281,14 +272,13 @@ int fdm_pcd_build_dem(const fdm_pcd_header* header, const void* body, uint64_t b
   const uint32_t n = header->width * header->height;
   if (n == 0) return fdm_engine_build_dem(0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, cfg, device, out_engine, stats);
   if (int rc = pick_device(device)) return rc;
-  DevBuf b_cloud;
-  const size_t cap = (size_t(n) + 3) & ~size_t(3);
+  CloudBlock b_cloud;
   int slot[5], n_ch = 0;  // x, y, z and those of intensity, rgb the file has (buildDEM has no use for the normals)
   for (int k = 0; k < 5; ++k) slot[k] = k < 3 || idx[k] >= 0 ? n_ch++ : -1;
-  if (int rc = b_cloud.alloc(cap * size_t(n_ch) * sizeof(float))) return rc;
+  if (int rc = b_cloud.alloc(n, n_ch)) return rc;
   void* out[8] = {};
   for (int k = 0; k < 5; ++k)
-    if (slot[k] >= 0) out[k] = b_cloud.as<float>() + cap * size_t(slot[k]);
+    if (slot[k] >= 0) out[k] = b_cloud.ch(slot[k]);
   if (int rc = pcd_decode_impl(header, body, body_bytes, body_on_device, out, 1, device)) return rc;
   return fdm_engine_build_dem(n, out[0], out[1], out[2], idx[3] >= 0 ? out[3] : nullptr, idx[4] >= 0 ? out[4] : nullptr, 1,
                               cfg, device, out_engine, stats);
@@ -314,13 +304,8 @@ int fdm_engine_to_pcd(fdm_engine* e, void* out, uint64_t cap, uint64_t* n_bytes,
   if (*n_points == 0) return FDM_OK;
   if (!out || *n_bytes > cap) return FDM_SKIP_BUFFER_TOO_SMALL;
   const size_t words = size_t(*n_points) * size_t(P.n_words);
-  if (words > e->pcd_rec_cap) {  // the engine's own record buffer: no allocation per call
-    if (e->pcd_rec) HIPCK(hipFree(e->pcd_rec));
-    e->pcd_rec = nullptr;
-    e->pcd_rec_cap = 0;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->pcd_rec), (words + words / 4 + 1024) * sizeof(uint32_t)));
-    e->pcd_rec_cap = words + words / 4 + 1024;
-  }
+  // the engine's own record buffer: no allocation per call
+  if (int rc = grow_device(e, &e->pcd_rec, &e->pcd_rec_cap, words, words + words / 4 + 1024)) return rc;
   return pcd_pack_download(e->stream, *n_points, P, e->pcd_rec, out);
 }
 

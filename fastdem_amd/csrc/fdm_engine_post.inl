@@ -18,13 +18,10 @@ int check_halo(const fdm_engine* e, int need) {
 }
 // neighbourhood offsets, dr-major / dc-minor; box = region(Size(k,k)), disc = region(radius)
 int upload_region(fdm_engine* e, const std::vector<RegionEntry>& reg) {
-  if (reg.size() > e->region_cap) {  // (any disc the reference accepts: 0.3 m on a 0.02 m map is 707 cells)
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->d_region) HIPCK(hipFree(e->d_region));
-    e->d_region = nullptr;
-    e->region_cap = std::max<size_t>(size_t(kMaxRegion), reg.size() + reg.size() / 4);
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_region), e->region_cap * sizeof(RegionEntry)));
-  }
+  // (any disc the reference accepts: 0.3 m on a 0.02 m map is 707 cells)
+  if (int rc_grow = grow_device(e, &e->d_region, &e->region_cap, reg.size(),
+                                std::max<size_t>(size_t(kMaxRegion), reg.size() + reg.size() / 4)))
+    return rc_grow;
   // the table of the last call stays on the device: a stage called again with the same parameters (the usual case: once
   // per published map) uploads nothing and waits for nothing
   if (e->h_region.size() == reg.size() && !reg.empty() &&
@@ -59,14 +56,8 @@ int ensure_pool(fdm_engine* e, size_t per_thread, unsigned threads, unsigned* bl
     return fail(FDM_ERR_INVALID, "neighbourhood too large for this map: " + std::to_string(entries) + " entries per cell x " +
                                      std::to_string(e->ncell) + " cells would keep the device busy for minutes");
   const size_t want_threads = std::min<size_t>(((e->ncell + threads - 1) / threads) * threads, 16384);
-  const size_t bytes = want_threads * per_thread * sizeof(float);
-  if (bytes > e->post_pool_bytes) {
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->d_post_pool) HIPCK(hipFree(e->d_post_pool));
-    e->d_post_pool = nullptr;
-    e->post_pool_bytes = bytes;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_post_pool), bytes));
-  }
+  const size_t floats = want_threads * per_thread;
+  if (int rc_grow = grow_device(e, &e->d_post_pool, &e->post_pool_cap, floats, floats)) return rc_grow;
   *blocks_out = unsigned(want_threads / threads);
   return FDM_OK;
 }

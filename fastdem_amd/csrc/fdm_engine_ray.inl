@@ -59,53 +59,29 @@ int ensure_voxel_buffers(fdm_engine* e, RayBank& b, size_t n) {
   }
   HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vsel), b.vcap * sizeof(uint32_t)));
   HIPCK(hipMalloc(reinterpret_cast<void**>(&b.ray_blk), (b.vcap / 512u + 2u) * sizeof(uint32_t)));  // (blocks of >= 512 points)
-  // the radix sort's histogram: 256 bins x tiles, + the 256 totals (fdm_rsort.hpp)
-  const size_t tiles = std::max((b.vcap + kRsTile - 1) / kRsTile, (size_t(kRsSmallMax) + kRsTileSmall - 1) / kRsTileSmall);
-  b.sort_tmp_bytes = (256u * tiles + 256u) * sizeof(uint32_t);
-  HIPCK(hipMalloc(&b.sort_tmp, b.sort_tmp_bytes));
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.sort_tmp), rs_hist_words(b.vcap) * sizeof(uint32_t)));
   return FDM_OK;
 }
 
 // Stable sort of the n pairs in (vkeys[src], vidx[src]) by the low `bits` bits of the key; the result lands in
 // (vkeys[1], vidx[1]).  `src` must be voxel_sort_source(bits): the buffers alternate once per pass.
-int voxel_sort_passes(unsigned bits) { return int((bits + 7u) / 8u); }
-int voxel_sort_source(unsigned bits) { return (voxel_sort_passes(bits) & 1) ? 0 : 1; }
-template <typename KEY, unsigned TILE>
-int enqueue_radix_sort_t(const RayLane& lane, unsigned n, unsigned bits) {
-  RayBank& b = lane.b;
-  const unsigned tiles = (n + TILE - 1u) / TILE;
-  uint32_t* const hist = static_cast<uint32_t*>(b.sort_tmp);
-  uint32_t* const total = hist + size_t(256) * tiles;
-  int src = voxel_sort_source(bits);
-  for (int pass = 0; pass < voxel_sort_passes(bits); ++pass, src ^= 1) {
-    const KEY* kin = reinterpret_cast<const KEY*>(b.vkeys[src]);
-    KEY* kout = reinterpret_cast<KEY*>(b.vkeys[src ^ 1]);
-    const unsigned shift = unsigned(pass) * 8u;
-    // (the first pass's histogram is k_voxel_keys' and its indices are the positions)
-    if (pass > 0)
-      hipLaunchKernelGGL((k_rs_hist<KEY, TILE>), dim3(tiles), dim3(256), 0, lane.s, n, kin, shift, tiles, hist);
-    hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, lane.s, tiles, hist, total);
-    if (pass > 0)
-      hipLaunchKernelGGL((k_rs_scatter<KEY, true, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, lane.s, n, kin,
-                         b.vidx[src], kout, b.vidx[src ^ 1], shift, tiles, hist, total);
-    else
-      hipLaunchKernelGGL((k_rs_scatter<KEY, false, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, lane.s, n, kin,
-                         static_cast<const uint32_t*>(nullptr), kout, b.vidx[src ^ 1], shift, tiles, hist, total);
-  }
-  HIPCK(hipGetLastError());
-  return FDM_OK;
-}
+int voxel_sort_source(unsigned bits) { return (rs_passes(bits) & 1) ? 0 : 1; }
 template <typename KEY>
 int enqueue_radix_sort(const RayLane& lane, unsigned n, unsigned bits) {
-  return rs_tile(n) == kRsTileSmall ? enqueue_radix_sort_t<KEY, kRsTileSmall>(lane, n, bits)
-                                    : enqueue_radix_sort_t<KEY, kRsTile>(lane, n, bits);
+  const RayBank& b = lane.b;
+  const RsPairs<KEY> pairs{{reinterpret_cast<KEY*>(b.vkeys[0]), reinterpret_cast<KEY*>(b.vkeys[1])},
+                           {b.vidx[0], b.vidx[1]}, b.sort_tmp};
+  // (the first pass's histogram is k_voxel_keys' and its indices are the positions)
+  (void)rs_enqueue<KEY>(lane.s, pairs, n, bits, voxel_sort_source(bits), kRsHistGiven);
+  HIPCK(hipGetLastError());
+  return FDM_OK;
 }
 // the keys of the scan's points into vkeys[src] (+ the sort's first histogram)
 template <typename KEY>
 void launch_voxel_keys(fdm_engine* e, const RayLane& lane, unsigned n, float inv, int flag_slot, const VoxelCompact& C,
                        const float* dx, const float* dy, const float* dz, int src) {
   const unsigned tile = rs_tile(n), tiles = (n + tile - 1u) / tile;
-  uint32_t* const hist = static_cast<uint32_t*>(lane.b.sort_tmp);
+  uint32_t* const hist = lane.b.sort_tmp;
   KEY* const keys = reinterpret_cast<KEY*>(lane.b.vkeys[src]);
   if (tile == kRsTileSmall)
     hipLaunchKernelGGL((k_voxel_keys<KEY, kRsTileSmall>), dim3(tiles), dim3(256), 0, lane.s, n, inv, flag_slot, C,

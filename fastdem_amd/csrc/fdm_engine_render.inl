@@ -14,14 +14,7 @@ int check_render(fdm_engine* e, const char* layer, const fdm_image_config* cfg, 
 // e->d_render->range (every mode but FIXED_RANGE).
 int enqueue_render(fdm_engine* e, const Layer* l, const fdm_image_config* cfg, bool* range_on_device) {
   if (e->ncell == 0 || e->ncell > (size_t(1) << 31)) return fail(FDM_ERR_INVALID, "map too large to render");
-  if (e->ncell > e->image_cap) {
-    if (int rc_sync = sync_all(e)) return rc_sync;
-    if (e->d_image) HIPCK(hipFree(e->d_image));
-    e->d_image = nullptr;
-    e->image_cap = 0;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_image), e->ncell * sizeof(uint32_t)));
-    e->image_cap = e->ncell;
-  }
+  if (int rc_grow = grow_device(e, &e->d_image, &e->image_cap, e->ncell, e->ncell)) return rc_grow;
   if (!e->d_render) HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_render), sizeof(RenderState)));
   const float* src = lptr(e, *l);
   const int stride = lstride(e, *l);

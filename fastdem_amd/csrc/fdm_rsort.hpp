@@ -1,5 +1,7 @@
-// fdm_rsort.hpp — stable LSD radix sort of (key, point index) pairs for the voxel filter of the raycasting stage
-// (fdm_raycast.hpp: scans too large for the sort-free path, 63-bit keys of clouds without a range bound).  gfx950 only.
+// fdm_rsort.hpp — stable LSD radix sort of (key, point index) pairs: the kernels, and at the end of the file the one host
+// driver that enqueues them (rs_enqueue).  Users: the voxel filter of the raycasting stage (fdm_engine_ray.inl: scans too
+// large for the sort-free path, 63-bit keys of clouds without a range bound), fromPointCloud's grouping by cell
+// (fdm_engine_raster.inl), buildDEM's two filters (fdm_engine_dem.inl).  gfx950 only.
 //
 // Reference being served: lib/nanoPCL/include/nanopcl/filters/impl/voxel_grid_impl.hpp:56-63 (sort of the
 // (key, index) array) — the engine needs the STABLE order (ties in point order, see fdm_raycast.hpp).
@@ -18,6 +20,8 @@
 // 0.777 ms for the stage: ten ballots and a 4 x 1024-entry counter table per round cost what the fourth pass costs.)
 #pragma once
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 #include <hip/hip_runtime.h>
@@ -160,6 +164,57 @@ __global__ __launch_bounds__(256) void k_rs_scatter(unsigned n, const KEY* __res
       idx_out[first + rank] = i_[r];
     }
   }
+}
+
+// ---- host side: the driver every sort of the library goes through; the callers own the buffers ----
+template <typename KEY>
+struct RsPairs {
+  KEY* keys[2];       // the two sides the passes alternate between
+  uint32_t* idx[2];
+  uint32_t* hist;     // rs_hist_words(capacity) words
+};
+// words of histogram a sort of up to `capacity` pairs needs — 256 bins x tiles + the 256 totals — whichever tile size
+// rs_tile picks for the actual n
+inline size_t rs_hist_words(size_t capacity) {
+  const size_t tiles = std::max((capacity + kRsTile - 1) / kRsTile,
+                                (std::min<size_t>(capacity, kRsSmallMax) + kRsTileSmall - 1) / kRsTileSmall);
+  return 256u * tiles + 256u;
+}
+inline unsigned rs_key_bits(uint64_t max_value) {  // bits a key of 0 .. max_value needs, at least one, at most 32
+  unsigned bits = 1;
+  while (bits < 32u && (max_value >> bits) != 0u) ++bits;
+  return bits;
+}
+inline int rs_passes(unsigned bits) { return int((bits + 7u) / 8u); }
+
+// what the caller has done for the first pass already
+constexpr unsigned kRsIdxGiven = 1u;   // idx[src] holds the pairs' indices (else: a pair's index is its position)
+constexpr unsigned kRsHistGiven = 2u;  // hist holds the first pass's histogram (k_voxel_keys leaves it)
+
+template <typename KEY, unsigned TILE>
+int rs_enqueue_t(hipStream_t s, const RsPairs<KEY>& B, unsigned n, unsigned bits, int src, unsigned first) {
+  const unsigned tiles = (n + TILE - 1u) / TILE;
+  uint32_t* const total = B.hist + size_t(256) * tiles;
+  for (unsigned shift = 0; shift < bits; shift += 8u, src ^= 1, first = 0u) {
+    if (!(first & kRsHistGiven))
+      hipLaunchKernelGGL((k_rs_hist<KEY, TILE>), dim3(tiles), dim3(256), 0, s, n, B.keys[src], shift, tiles, B.hist);
+    hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, tiles, B.hist, total);
+    if (shift || (first & kRsIdxGiven))
+      hipLaunchKernelGGL((k_rs_scatter<KEY, true, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, s, n, B.keys[src],
+                         B.idx[src], B.keys[src ^ 1], B.idx[src ^ 1], shift, tiles, B.hist, total);
+    else
+      hipLaunchKernelGGL((k_rs_scatter<KEY, false, int(TILE / 256u)>), dim3(tiles), dim3(256), 0, s, n, B.keys[src],
+                         static_cast<const uint32_t*>(nullptr), B.keys[src ^ 1], B.idx[src ^ 1], shift, tiles, B.hist,
+                         total);
+  }
+  return src;
+}
+// Stable sort of the n pairs on side `src` by the low `bits` bits of the key, rs_passes(bits) passes on stream s; returns
+// the side the result is on (src for an even number of passes).  `first`: kRsIdxGiven | kRsHistGiven.  Enqueue-only.
+template <typename KEY>
+int rs_enqueue(hipStream_t s, const RsPairs<KEY>& B, unsigned n, unsigned bits, int src = 0, unsigned first = 0u) {
+  return rs_tile(n) == kRsTileSmall ? rs_enqueue_t<KEY, kRsTileSmall>(s, B, n, bits, src, first)
+                                    : rs_enqueue_t<KEY, kRsTile>(s, B, n, bits, src, first);
 }
 
 }  // namespace fdm

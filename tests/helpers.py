@@ -91,3 +91,9 @@ def run_both(eng, ref, s, Tbs, Twb, check_ids=True):
         ie, ir = eng.last_cell_ids(n), ref.last_cell_ids(n)
         assert np.array_equal(ie, ir), f"cell ids differ at {(ie != ir).sum()} of {n} points"
     return rc_e, st_e
+
+
+def lay_of(fastdem_amd, lay):
+    """A tests/cloud2.py Layout as the engine's fdm_cloud2_layout."""
+    return fastdem_amd.Engine.cloud2_layout(lay.point_step, lay.off_x, lay.off_y, lay.off_z, lay.off_intensity,
+                                            lay.intensity_type, lay.off_rgb)

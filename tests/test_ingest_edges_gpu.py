@@ -9,17 +9,12 @@ import numpy as np
 import pytest
 
 import io_cases as K
-from helpers import assert_layers_equal, pair
+from helpers import assert_layers_equal, lay_of, pair
 from io_restate import restate_from_cloud2, restate_pack
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 CHANNELS = ("x", "y", "z", "intensity", "rgb")
-
-
-def lay_of(gpu, lay):
-    return gpu.Engine.cloud2_layout(lay.point_step, lay.off_x, lay.off_y, lay.off_z, lay.off_intensity,
-                                    lay.intensity_type, lay.off_rgb)
 
 
 def same_channels(got, want, what):

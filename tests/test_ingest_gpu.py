@@ -5,15 +5,10 @@ import numpy as np
 import pytest
 
 from cloud2 import make_blob
-from helpers import assert_layers_equal, pair, same_geometry
+from helpers import assert_layers_equal, lay_of, pair, same_geometry
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-
-
-def lay_of(gpu, lay):
-    return gpu.Engine.cloud2_layout(lay.point_step, lay.off_x, lay.off_y, lay.off_z, lay.off_intensity,
-                                    lay.intensity_type, lay.off_rgb)
 
 
 def same_decode(gpu, R, blob, n, lay):

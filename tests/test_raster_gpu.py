@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import raster_restate as RR
-from helpers import assert_layers_bit_identical
+from helpers import assert_layers_bit_identical, lay_of
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -79,6 +79,40 @@ def test_point_count_edges(gpu, R, n):
         assert st["n_cells_written"] == int((ref.layer("n_points") > 0).sum())
         check(eng, ref)
         eng.close()
+
+
+N_LARGE_TILE = 600_001    # one past fdm_rsort.hpp's kRsSmallMax: tiles of 4 096 pairs, the histogram sized past the small tile's
+
+
+def large_tile_cloud():
+    """600 001 points of which 5 000, at random places of the input, have a z; the others' is NaN.  The device skips
+    none of them before the sort (a skipped point gets the key ncell, behind every cell), so all 600 001 pairs go through
+    the large-tile passes, and the walk has to find every cell's run in input order."""
+    c = uniform_cloud(N_LARGE_TILE, 17)
+    live = np.zeros(N_LARGE_TILE, dtype=bool)
+    live[np.random.default_rng(18).choice(N_LARGE_TILE, 5000, replace=False)] = True
+    c["z"][~live] = np.nan
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _large_tile_case():
+    import fdm_ref_py as R
+    c = large_tile_cloud()
+    ref = RefMap(R)
+    ref.raster(c, "mean")
+    return c, ref
+
+
+def test_large_tile_sort(gpu, R):
+    """The 4 096-pair tile of the radix sort as fromPointCloud reaches it; `mean`: the variance shows a walk out of order."""
+    c, ref = _large_tile_case()
+    eng = gpu.Engine.create_map(W, H, RES)
+    rc, st = raster(eng, c, "mean")
+    assert rc == 0 and st["n_points_used"] == int(ref.layer("n_points").sum()) == 5000
+    assert st["n_cells_written"] == int((ref.layer("n_points") > 0).sum()) > 1000
+    check(eng, ref)
+    eng.close()
 
 
 RUNS = (1, 2, 63, 64, 65, 256, 257, 4000)
@@ -374,3 +408,57 @@ def test_to_point_cloud_into_arrays_that_are_too_small(gpu):
                                                    C.byref(n), None, None)
     assert rc == gpu.capi.FDM_SKIP_BUFFER_TOO_SMALL and n.value == eng.to_point_cloud()["x"].size > 4
     assert (x == 7.0).all()
+
+
+def _same_bits(a, b, what):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            _same_bits(a[k], b[k], f"{what} {k}")
+    elif isinstance(a, (tuple, list)):
+        assert len(a) == len(b), what
+        for k, (u, v) in enumerate(zip(a, b)):
+            _same_bits(u, v, f"{what} [{k}]")
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape, what
+        assert a.tobytes() == b.tobytes(), what
+    else:
+        assert a == b, what
+
+
+def test_buffers_grow_from_a_small_call_to_a_larger_one(gpu):
+    """The engine's on-demand buffers (message bytes, decoded channels, block counters, staged cloud, sort pairs and
+    histograms, toPointCloud's channels, packed records of either kind) are sized by the first call with some slack.  One
+    engine runs every call that owns one with a small input and then with one past that slack: 5, then 300 000 message
+    points; 100, then 5 000 cloud points on a 64 x 64 map, which leave at most 100, then more than 2 000 valid cells
+    for the three map-sized calls.  Each result equals the same call's on an engine that ran nothing before it (the larger
+    cloud covers every cell of the smaller one, and a rasterized cell is overwritten whole: the maps are the same)."""
+    import io_cases as K
+    side = 6.4                                                            # 64 x 64 cells
+
+    def cloud(n, seed):
+        rng = np.random.default_rng(seed)
+        return {"x": rng.uniform(-side / 2, side / 2, n).astype(F32), "y": rng.uniform(-side / 2, side / 2, n).astype(F32),
+                "z": rng.normal(1.0, 0.5, n).astype(F32), "intensity": rng.uniform(0, 1, n).astype(F32),
+                "rgb": rng.integers(0, 1 << 24, n).astype(np.uint32)}
+
+    small, large = cloud(100, 71), cloud(5000, 72)
+    large["x"][:100], large["y"][:100] = small["x"], small["y"]
+    steps = ((small, "ingest_5", 5), (large, "ingest_300000", 300_000))
+    valid = []
+    eng = gpu.Engine.create_map(side, side, RES)
+    for c, blob_name, n_msg in steps:
+        fresh = gpu.Engine.create_map(side, side, RES)
+        blob, lay = K.SCRATCH_BLOBS[blob_name]()
+        _same_bits(eng.ingest_cloud2(blob, n_msg, lay_of(gpu, lay)), fresh.ingest_cloud2(blob, n_msg, lay_of(gpu, lay)),
+                   blob_name)
+        got, want = raster(eng, c, "mean"), raster(fresh, c, "mean")
+        assert got == want and got[0] == 0, (got, want)
+        assert eng.layers() == fresh.layers()
+        assert_layers_bit_identical(eng, fresh)
+        for call in ("to_point_cloud", "pack_cloud", "to_pcd"):
+            _same_bits(getattr(eng, call)(), getattr(fresh, call)(), f"{call} after {c['x'].size} points")
+        valid.append(eng.to_point_cloud()["x"].size)
+        fresh.close()
+    eng.close()
+    assert valid[0] <= 100 and valid[1] > 2000, valid
