@@ -126,6 +126,14 @@ class FdmDemStats(C.Structure):  # fdm_dem_stats (include/fdm_engine.h)
                 ("raster", FdmRasterStats)]
 
 
+class FdmCloudView(C.Structure):  # fdm_cloud_view (include/fdm_engine.h)
+    _fields_ = [(k, C.c_void_p) for k in ("x", "y", "z", "intensity", "rgb", "nx", "ny", "nz", "cov9")]
+
+
+class FdmCloudOut(C.Structure):  # fdm_cloud_out (include/fdm_engine.h)
+    _fields_ = [(k, C.c_void_p) for k in ("x", "y", "z", "intensity", "rgb", "nx", "ny", "nz", "cov9", "idx")]
+
+
 class FdmPcdField(C.Structure):  # fdm_pcd_field (include/fdm_engine.h)
     _fields_ = [("name", C.c_char * 64), ("type", C.c_char), ("reserved", C.c_uint8 * 3), ("size", C.c_uint32),
                 ("count", C.c_uint32), ("offset", C.c_uint32)]
@@ -160,6 +168,7 @@ FDM_OK, FDM_SKIP_EMPTY_CLOUD, FDM_SKIP_ALL_FILTERED, FDM_SKIP_NO_CELL, FDM_SKIP_
 RASTER_METHOD = {"max": 0, "min": 1, "mean": 2, "minmax": 3}        # fastdem::RasterMethod
 FDM_ERR_INVALID, FDM_ERR_HIP, FDM_ERR_NO_LAYER, FDM_ERR_NO_DEVICE = -1, -2, -3, -4
 NORMALIZE = {"min_max": 0, "percentile_1_99": 1, "fixed_range": 2}   # PngExportConfig::Normalize
+VOXEL_MODE = {"centroid": 0, "nearest": 1, "any": 2, "center": 3}   # nanopcl::filters::VoxelMode
 PCD_ASCII, PCD_BINARY = 0, 1                                         # fdm_pcd_header.format
 COLORMAP = {"grayscale": 0, "viridis": 1, "jet": 2}                  # PngExportConfig::Colormap
 
@@ -275,6 +284,12 @@ PROTOTYPES = {
     "fdm_sor_last_stats": (C.c_int, [C.POINTER(FdmSorStats)]),
     "fdm_engine_remove_floating_points": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P,
                                                     C.POINTER(C.c_uint64)]),
+    "fdm_cloud_voxel_grid": (C.c_int, [C.c_uint64, C.POINTER(FdmCloudView), C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(FdmCloudOut), C.POINTER(C.c_uint64)]),
+    "fdm_cloud_grid_max_z": (C.c_int, [C.c_uint64, C.POINTER(FdmCloudView), C.c_int, C.c_float, C.c_int, C.c_int,
+                                       C.POINTER(FdmCloudOut), C.POINTER(C.c_uint64)]),
+    "fdm_cloud_debug_profile": (C.c_int, [C.c_int]),
+    "fdm_cloud_debug_last_ms": (C.c_int, [_F]),
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),
     "fdm_engine_build_dem": (C.c_int, [C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(FdmDemConfig), C.c_int,
                                        C.POINTER(_P), C.POINTER(FdmDemStats)]),

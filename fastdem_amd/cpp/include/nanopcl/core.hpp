@@ -152,6 +152,7 @@ class PointCloud {
     return m;
   }
   float* covarianceData() { return use_cov_ ? cov_.data() : nullptr; }  // [n][9], column-major 3x3 per point
+  const float* covarianceData() const { return use_cov_ ? cov_.data() : nullptr; }
 
   bool hasColor() const { return use_color_; }
   void useColor() { use_color_ = true; rgb_.resize(size(), 0u); }

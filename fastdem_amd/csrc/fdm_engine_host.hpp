@@ -33,6 +33,7 @@
 #include "fdm_route.hpp"
 #include "fdm_raycast.hpp"
 #include "fdm_introsort.hpp"
+#include "fdm_voxel.hpp"
 #include "fdm_raywedge.hpp"
 #include "fdm_rbatch.hpp"
 #include "fdm_rsort.hpp"

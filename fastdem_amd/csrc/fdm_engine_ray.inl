@@ -41,26 +41,36 @@ int ensure_ray_cells(fdm_engine* e, RayBank& b) {
   return FDM_OK;
 }
 
-// (sync_all flushes a held-back stage, which runs in bank 0 and may grow it first: everything is idle afterwards)
-int ensure_voxel_buffers(fdm_engine* e, RayBank& b, size_t n) {
-  if (n <= b.vcap) return FDM_OK;
-  if (int rc_sync = sync_all(e)) return rc_sync;
+// A bank's voxel / queue buffers for n points with a quarter and 1 024 of slack: what it held is freed first, so nothing of
+// the bank may be in flight.  Engine-free: the cloud filters (fdm_engine_voxel.inl) fill a bank of their own with it.
+int alloc_voxel_buffers(RayBank& b, size_t n) {
   for (int k = 0; k < 2; ++k) {
     if (b.vkeys[k]) HIPCK(hipFree(b.vkeys[k]));
     if (b.vidx[k]) HIPCK(hipFree(b.vidx[k]));
+    b.vkeys[k] = nullptr;
+    b.vidx[k] = nullptr;
   }
   if (b.vsel) HIPCK(hipFree(b.vsel));
   if (b.ray_blk) HIPCK(hipFree(b.ray_blk));
   if (b.sort_tmp) HIPCK(hipFree(b.sort_tmp));
-  b.vcap = n + n / 4 + 1024;
+  b.vsel = b.ray_blk = b.sort_tmp = nullptr;
+  b.vcap = 0;
+  const size_t cap = n + n / 4 + 1024;
   for (int k = 0; k < 2; ++k) {
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vkeys[k]), b.vcap * sizeof(unsigned long long)));
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vidx[k]), b.vcap * sizeof(uint32_t)));
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vkeys[k]), cap * sizeof(unsigned long long)));
+    HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vidx[k]), cap * sizeof(uint32_t)));
   }
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vsel), b.vcap * sizeof(uint32_t)));
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.ray_blk), (b.vcap / 512u + 2u) * sizeof(uint32_t)));  // (blocks of >= 512 points)
-  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.sort_tmp), rs_hist_words(b.vcap) * sizeof(uint32_t)));
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.vsel), cap * sizeof(uint32_t)));
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.ray_blk), (cap / 512u + 2u) * sizeof(uint32_t)));  // (blocks of >= 512 points)
+  HIPCK(hipMalloc(reinterpret_cast<void**>(&b.sort_tmp), rs_hist_words(cap) * sizeof(uint32_t)));
+  b.vcap = cap;
   return FDM_OK;
+}
+// (sync_all flushes a held-back stage, which runs in bank 0 and may grow it first: everything is idle afterwards)
+int ensure_voxel_buffers(fdm_engine* e, RayBank& b, size_t n) {
+  if (n <= b.vcap) return FDM_OK;
+  if (int rc_sync = sync_all(e)) return rc_sync;
+  return alloc_voxel_buffers(b, n);
 }
 
 // Stable sort of the n pairs in (vkeys[src], vidx[src]) by the low `bits` bits of the key; the result lands in
@@ -126,16 +136,20 @@ size_t is_layout(uintptr_t base, size_t cap, IsBufs<KEY>* B) {
   B->cap_tiles = unsigned(ct);
   return off;
 }
-int ensure_introsort_buffers(fdm_engine* e, RayBank& b, size_t n) {
-  if (n <= b.is_cap) return FDM_OK;
-  if (int rc_sync = sync_all(e)) return rc_sync;
+int alloc_introsort_buffers(RayBank& b, size_t n) {  // (engine-free, as alloc_voxel_buffers)
   if (b.is_buf) HIPCK(hipFree(b.is_buf));
   b.is_buf = nullptr;
+  b.is_cap = 0;
   const size_t cap = n + n / 4u + 1024u;
   IsBufs<unsigned long long> B{};  // (the 64-bit layout is the larger one)
   HIPCK(hipMalloc(&b.is_buf, is_layout(uintptr_t(0), cap, &B)));
   b.is_cap = cap;
   return FDM_OK;
+}
+int ensure_introsort_buffers(fdm_engine* e, RayBank& b, size_t n) {
+  if (n <= b.is_cap) return FDM_OK;
+  if (int rc_sync = sync_all(e)) return rc_sync;
+  return alloc_introsort_buffers(b, n);
 }
 // (key, position) of the n pairs in vkeys[0] (k_voxel_keys' output) -> vkeys[1] / vidx[1] in std::sort's order, the
 // dropped points behind the valid ones

@@ -117,7 +117,8 @@ struct VoxelKeyTraits<uint32_t> {
 // One block per sort tile (TILE = fdm_rsort.hpp's rs_tile(n) points): besides the keys it leaves the
 // FIRST pass's digit histogram of its tile (hist[bin][tile], as k_rs_hist would: one launch and one pass over the keys
 // less), and the point indices are not written at all — the first scatter pass takes "position" for them.
-template <typename KEY, unsigned TILE>
+// FLAT (gridMaxZ, fdm_voxel.hpp): the key of (x, y, 0) — z still decides whether the point is valid (grid_max_z_impl.hpp:43-46).
+template <typename KEY, unsigned TILE, bool FLAT = false>
 __global__ __launch_bounds__(256) void k_voxel_keys(unsigned n, float inv_voxel, int flag_slot,
                                                     const VoxelCompact C, DevState* __restrict__ st,
                                                     const float* __restrict__ x,
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(256) void k_voxel_keys(unsigned n, float inv_voxel,
       const float a = x[i], b = y[i], c = z[i];
       const bool valid = isfinite(a) && isfinite(b) && isfinite(c);
       KEY k = VoxelKeyTraits<KEY>::invalid;
-      if (valid) k = C.bits > 0 ? voxel_pack_compact<KEY>(a, b, c, inv_voxel, C) : KEY(voxel_pack(a, b, c, inv_voxel));
+      const float kz = FLAT ? 0.0f : c;
+      if (valid) k = C.bits > 0 ? voxel_pack_compact<KEY>(a, b, kz, inv_voxel, C) : KEY(voxel_pack(a, b, kz, inv_voxel));
       keys[i] = k;
       sel[i] = 0u;  // k_voxel_mark sets the representatives
       atomicAdd(&h[unsigned(k) & 255u], 1u);

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (FdmCloud2Layout, FdmConfig, FdmDemConfig, FdmDemStats, FdmGeometry, FdmRasterStats, FdmScanStats,
+from .capi import (FdmCloud2Layout, FdmCloudOut, FdmCloudView, FdmConfig, FdmDemConfig, FdmDemStats, FdmGeometry, FdmRasterStats, FdmScanStats,
                    FdmSorStats, FdmTile)
 
 
@@ -840,3 +840,75 @@ def build_dem(x, y, z, intensity=None, rgb=None, config=None, device=0, return_s
              "sor_threshold": np.float32(st.sor_threshold), "stage_ms": tuple(float(v) for v in st.stage_ms),
              "n_points_used": int(st.raster.n_points_used), "n_cells_written": int(st.raster.n_cells_written)}
     return eng, stats
+
+
+def _downsample(x, y, z, size, mode, intensity, rgb, normals, cov, order, device, return_index):
+    """fdm_cloud_voxel_grid (mode 0 .. 3) / fdm_cloud_grid_max_z (mode None) on numpy arrays or torch device tensors."""
+    lib = capi.load()
+    torch_in = _is_torch(x)
+    if normals is not None and not isinstance(normals, (tuple, list)):
+        normals = tuple(normals[:, k] for k in range(3))       # an (n, 3) array
+    if torch_in:
+        import torch
+        torch.cuda.current_stream(x.device).synchronize()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()  # where the tensors live
+        n = x.numel()
+        given = {"x": x, "y": y, "z": z, "intensity": intensity, "rgb": rgb, "cov9": cov}
+        for k, v in zip(("nx", "ny", "nz"), normals or (None,) * 3):
+            given[k] = v
+        given = {k: (None if v is None else v.contiguous()) for k, v in given.items()}
+        outs = {k: torch.empty((n, 9) if k == "cov9" else n, dtype=v.dtype, device=x.device)
+                for k, v in given.items() if v is not None}
+        outs["idx"] = torch.empty(n, dtype=torch.int32, device=x.device)
+        ptr = _dptr
+    else:
+        x, y, z = _f32(x).reshape(-1), _f32(y).reshape(-1), _f32(z).reshape(-1)
+        n = x.size
+        given = {"x": x, "y": y, "z": z, "intensity": _f32(intensity), "rgb": _u32(rgb),
+                 "cov9": None if cov is None else _f32(cov).reshape(n, 9)}
+        for k, v in zip(("nx", "ny", "nz"), normals or (None,) * 3):
+            given[k] = _f32(v)
+        outs = {k: np.empty((n, 9) if k == "cov9" else n, dtype=v.dtype) for k, v in given.items() if v is not None}
+        outs["idx"] = np.empty(n, dtype=np.uint32)
+        ptr = _ptr
+    view = FdmCloudView(**{k: ptr(v) for k, v in given.items()})
+    out = FdmCloudOut(**{k: ptr(v) for k, v in outs.items()})
+    n_out = C.c_uint64(0)
+    size = float(np.float32(size))
+    if mode is None:
+        _ck(lib.fdm_cloud_grid_max_z(n, C.byref(view), int(torch_in), size, int(order), int(device), C.byref(out),
+                                     C.byref(n_out)))
+    else:
+        m = capi.VOXEL_MODE[mode.lower()] if isinstance(mode, str) else int(mode)
+        _ck(lib.fdm_cloud_voxel_grid(n, C.byref(view), int(torch_in), size, m, int(order), int(device), C.byref(out),
+                                     C.byref(n_out)))
+    k = int(n_out.value)
+    res = {name: v[:k] for name, v in outs.items()}
+    if "nx" in res:
+        res["normals"] = (res.pop("nx"), res.pop("ny"), res.pop("nz"))
+    if "cov9" in res:
+        res["cov"] = res.pop("cov9")
+    idx = res.pop("idx")
+    if return_index:
+        res["idx"] = (idx.long() & 0xFFFFFFFF) if torch_in else idx
+    return res
+
+
+def voxel_grid(x, y, z, voxel_size, mode="centroid", intensity=None, rgb=None, normals=None, cov=None, order=0,
+               device=0, return_index=False):
+    """nanopcl::filters::voxelGrid(cloud, voxel_size, mode) on the device: mode "centroid", "nearest", "any" or "center".
+    numpy arrays in, numpy arrays out; torch device tensors in, device tensors out (they can feed integrate_device or
+    from_point_cloud as they are).  normals: three arrays (nx, ny, nz) or one of shape (n, 3); cov: (n, 9).  Returns a
+    dict with "x", "y", "z" and the channels given ("intensity", "rgb", "normals" as a tuple of three, "cov");
+    return_index adds "idx", the input index each output point was copied from (centroid, center: the voxel's
+    representative).  order: 0 = ties in input order, 1 = the order std::sort leaves (engine option "voxel_any_order").
+    device: the ordinal numpy input runs on; torch tensors run on the device they live on."""
+    return _downsample(x, y, z, voxel_size, mode, intensity, rgb, normals, cov, order, device, return_index)
+
+
+def grid_max_z(x, y, z, grid_size, intensity=None, rgb=None, normals=None, cov=None, order=0, device=0,
+               return_index=False):
+    """nanopcl::filters::gridMaxZ(cloud, grid_size) on the device: per (x, y) cell the point with the largest z, every
+    channel that point's.  Arguments and result as voxel_grid."""
+    return _downsample(x, y, z, grid_size, None, intensity, rgb, normals, cov, order, device, return_index)
+

@@ -562,6 +562,51 @@ int fdm_sor_last_stats(fdm_sor_stats* out);
 int fdm_engine_remove_floating_points(fdm_engine* e, uint64_t n, const float* x, const float* y, const float* z,
                                       int on_device, float height_threshold, float bin_size, uint8_t* keep,
                                       uint64_t* n_kept);
+/* ---- cloud downsampling: nanopcl::filters::voxelGrid and gridMaxZ (filters/downsample.hpp; voxel_grid_impl.hpp:30-236,
+ * grid_max_z_impl.hpp:31-75, core/voxel.hpp:28-102) ----
+ * Engine-free and synchronous, on `device`.  The input is SoA: host arrays (on_device 0) or device arrays; x, y, z are
+ * required, the other channels nullable, the normal's three arrays all or none.
+ * KEYS AND ORDER.  inv = 1.0f / size; a point with a non-finite x, y or z is dropped; the others get the key
+ * voxel::pack(x, y, z, inv): floor(v * inv) converted to int32 as x86 converts it (INT_MIN outside the int range),
+ * clamped to [-2^20, 2^20 - 1], packed [z:21][y:21][x:21].  gridMaxZ packs (x, y, 0.0f) but still drops a point whose z
+ * is not finite.  The (key, index) pairs are sorted by key and every run of equal keys gives one output point, in
+ * ascending key order.  order 0: equal keys keep the input order (a stable sort); order 1: the order libstdc++'s
+ * std::sort leaves them in, i.e. the reference's own (engine option "voxel_any_order").  `rep` is a run's first entry.
+ * CENTROID (mode 0): x, y, z and intensity are fp32 sums from 0 over the run, in its order, each DIVIDED by
+ * float(count); colour: float sums of r, g, b, each divided by the count and truncated to uint8; normal: component sums
+ * s, norm = sqrt((sx*sx + sy*sy) + sz*sz) correctly rounded, s / norm if norm > 1e-6f, else (0, 0, 1); covariance: the
+ * rep's.  CENTER (mode 3): the same, but the position is ((i + 0.5f) * size) per axis from the unpacked key.
+ * NEAREST (mode 1): the point with the first strictly smallest d2 below FLT_MAX (the rep if none), d2 = (dx*dx + dz*dz)
+ * + (dy*dy + 0) to that centre — the order of Eigen's 4-float packet reduction (ASSUMED: DESIGN.md §7); every channel is
+ * that point's.  ANY (mode 2): entry start + (count * 7 + start * 13) % count of the sorted valid entries, `start` the
+ * run's first — what fdm_engine_voxel_any picks.  gridMaxZ: the run's first strictly greatest z; every channel is
+ * that point's.
+ * OUTPUT.  Arrays of capacity n (the output is never larger than the input), host arrays for a host input and device
+ * arrays otherwise; any may be NULL, and one whose input channel is absent is left untouched.  idx[r] = input index of
+ * the point output r was copied from (CENTROID, CENTER: the run's rep), for the channels this ABI does not carry.
+ * *n_out is a host word.  n == 0: FDM_OK, *n_out = 0.  FDM_ERR_INVALID: a size outside [0.001, 100] or NaN
+ * ("voxel_size must be in [0.001, 100]" / "grid_size must be in [0.001, 100]"), an unknown mode or order,
+ * n > 2^32 - 4097 (the sorts count tiles of 4 096 pairs in 32 bits), input normals given in part, a null x, y or z.
+ * The thread's current device is put back before the call returns. */
+typedef struct fdm_cloud_view {
+  const float *x, *y, *z, *intensity;
+  const uint32_t* rgb;          /* 0x00RRGGBB */
+  const float *nx, *ny, *nz;    /* all three or none */
+  const float* cov9;            /* 9 floats per point */
+} fdm_cloud_view;
+typedef struct fdm_cloud_out {
+  float *x, *y, *z, *intensity;
+  uint32_t* rgb;
+  float *nx, *ny, *nz;
+  float* cov9;
+  uint32_t* idx;
+} fdm_cloud_out;
+/* mode: 0 CENTROID, 1 NEAREST, 2 ANY, 3 CENTER (VoxelMode's order) */
+int fdm_cloud_voxel_grid(uint64_t n, const fdm_cloud_view* in, int on_device, float voxel_size, int mode, int order,
+                         int device, const fdm_cloud_out* out, uint64_t* n_out);
+int fdm_cloud_grid_max_z(uint64_t n, const fdm_cloud_view* in, int on_device, float grid_size, int order, int device,
+                         const fdm_cloud_out* out, uint64_t* n_out);
+
 typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
   float resolution;
   int32_t method;              /* RasterMethod: 0 Max, 1 Min, 2 Mean, 3 MinMax */
