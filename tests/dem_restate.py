@@ -8,6 +8,11 @@ data, not product.
   restate_floating        removeFloatingPoints                          pcd_convert.cpp:228-269
   restate_build_dem       buildDEM                                      pcd_convert.cpp:275-323
 
+For tests/test_sor_edges_gpu.py (clouds built against the engine's column search, tests/sor_cases.py):
+  knn_mean_distances_of   the brute-force means of a sample of queries (a cloud too large for every pair)
+  knn_mean_within_rings   what a column search that stops after ring s would return: the wrong answer of a probe
+  knn_columns, sor_grid   the search grid's columns and its size rule, restated
+
 The k-NN is brute force (every pair), in fp32 with the reference's operation order ((dx*dx) + (dy*dy)) + (dz*dz); the two
 global sums are SEQUENTIAL fp64 sums (np.cumsum: np.sum is pairwise and rounds differently).  A point's cell comes from
 the oracle's grid, rasterization from tests/raster_restate.py, inpainting from the oracle as tests/test_post_gpu.py uses it.
@@ -27,6 +32,22 @@ def effective_k(n, k):
     return n - 1 if k < 0 else min(int(k), n - 1)    # a negative int converts to a huge size_t
 
 
+def _knn_rows(x, y, z, k, rows):
+    """The mean distances of the queries `rows` (indices into the cloud) against every point of the cloud."""
+    dx = x[rows, None] - x[None, :]
+    dy = y[rows, None] - y[None, :]
+    dz = z[rows, None] - z[None, :]
+    d2 = ((dx * dx) + (dy * dy)) + (dz * dz)                         # float32 throughout: one rounding per operation
+    assert d2.dtype == F32
+    d2[np.arange(rows.size), rows] = np.inf                          # only the query's own index is left out
+    best = np.sort(np.partition(d2, k - 1, axis=1)[:, :k], axis=1)
+    root = np.sqrt(best)                                             # correctly rounded in fp32
+    acc = np.zeros(rows.size, dtype=F32)
+    for j in range(k):                                               # sum += sqrt(dist_sq), nearest first
+        acc = (acc + root[:, j]).astype(F32)
+    return acc / F32(k)
+
+
 def knn_mean_distances(x, y, z, k, chunk=512):
     """float32[n]: (sum of sqrt of the k smallest squared distances to the OTHER points, ascending, fp32) / float(k)."""
     x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
@@ -34,19 +55,62 @@ def knn_mean_distances(x, y, z, k, chunk=512):
     out = np.empty(n, dtype=F32)
     for a in range(0, n, chunk):
         b = min(n, a + chunk)
-        dx = x[a:b, None] - x[None, :]
-        dy = y[a:b, None] - y[None, :]
-        dz = z[a:b, None] - z[None, :]
-        d2 = ((dx * dx) + (dy * dy)) + (dz * dz)                     # float32 throughout: one rounding per operation
-        assert d2.dtype == F32
-        d2[np.arange(b - a), np.arange(a, b)] = np.inf               # only the query's own index is left out
-        best = np.sort(np.partition(d2, k - 1, axis=1)[:, :k], axis=1)
-        root = np.sqrt(best)                                         # correctly rounded in fp32
-        acc = np.zeros(b - a, dtype=F32)
-        for j in range(k):                                           # sum += sqrt(dist_sq), nearest first
-            acc = (acc + root[:, j]).astype(F32)
-        out[a:b] = acc / F32(k)
+        out[a:b] = _knn_rows(x, y, z, k, np.arange(a, b))
     return out
+
+
+def knn_mean_distances_of(x, y, z, k, queries, cells=1 << 23):
+    """float32[len(queries)]: knn_mean_distances' values at the point indices `queries`, by the same arithmetic, in
+    chunks of about `cells` distances (a sample of a cloud too large for every pair)."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    queries = np.asarray(queries, dtype=np.int64)
+    chunk = max(1, cells // max(1, x.size))
+    out = np.empty(queries.size, dtype=F32)
+    for a in range(0, queries.size, chunk):
+        out[a:a + chunk] = _knn_rows(x, y, z, k, queries[a:a + chunk])
+    return out
+
+
+def knn_columns(p, mn, h, g):
+    """The search grid's column of coordinates p along one axis, as fdm_knn.hpp's knn_col(knn_u(p, mn, 1 / h), g) has
+    it: a subtraction and a multiplication rounded to fp32 each, truncation, the clamp to [0, g - 1]."""
+    inv_h = F32(1.0) / F32(h)
+    u = ((np.asarray(p, dtype=F32) - F32(mn)).astype(F32) * inv_h).astype(F32)
+    return np.clip(u.astype(np.int64), 0, int(g) - 1)
+
+
+def knn_mean_within_rings(x, y, z, k, q, s, h, min_x, min_y, gx, gy):
+    """The mean distance point q would get from a search that looks no further than ring s: brute force over the points
+    whose column lies within Chebyshev distance s of q's column (inf where these are fewer than k).  What a column
+    search that stops after ring s returns — the wrong answer a probe is built to tell from the right one."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    cx, cy = knn_columns(x, min_x, h, gx), knn_columns(y, min_y, h, gy)
+    near = np.flatnonzero(np.maximum(np.abs(cx - cx[q]), np.abs(cy - cy[q])) <= s)
+    if near.size - 1 < k:
+        return F32(np.inf)
+    return _knn_rows(x[near], y[near], z[near], k, np.flatnonzero(near == q))[0]
+
+
+def sor_grid(min_x, min_y, max_x, max_y, n, k, grid_max=2048):
+    """(h, gx, gy) of the search grid: the arithmetic of fdm_engine_dem.inl's sor_grid, for test clouds that are built
+    to reach one of its branches.  h in fp64 first (area rule, length rule, the column cap), then fp32."""
+    ex, ey = float(F32(max_x)) - float(F32(min_x)), float(F32(max_y)) - float(F32(min_y))
+    per = max(4.0, 0.5 * k)
+    h = float(np.sqrt(per * ex * ey / n))
+    if not h > 0.0:
+        h = per * max(ex, ey) / n
+    h = max(h, max(ex, ey) / (grid_max - 1))
+    hf = F32(h)
+    with np.errstate(divide="ignore", over="ignore"):
+        inv = F32(1.0) / hf
+    if not (hf > 0 and np.isfinite(hf) and np.isfinite(inv) and inv > 0):
+        hf, inv = F32(1.0), F32(1.0)
+
+    def cols(mx, mn):
+        u = F32(F32(F32(mx) - F32(mn)) * inv)
+        c = np.floor(float(u)) if np.isfinite(u) and u > 0 else 0.0
+        return int(min(c, grid_max - 1)) + 1
+    return hf, cols(max_x, min_x), cols(max_y, min_y)
 
 
 def sor_threshold(mean, std_mul):
