@@ -113,6 +113,11 @@ class FdmSorStats(C.Structure):  # fdm_sor_stats (include/fdm_engine.h)
                 ("voxel", C.c_float), ("ms", C.c_float * 4)]
 
 
+class FdmNormalStats(C.Structure):  # fdm_normal_stats (include/fdm_engine.h)
+    _fields_ = [("n_queries", C.c_uint64), ("n_fallback", C.c_uint64), ("n_invalid", C.c_uint64),
+                ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("voxel", C.c_float), ("ms", C.c_float * 4)]
+
+
 class FdmDemConfig(C.Structure):
     """fdm_dem_config == fastdem::DEMConfig (io/pcd_convert.hpp:28-42)."""
 
@@ -288,6 +293,9 @@ PROTOTYPES = {
                                        C.POINTER(FdmCloudOut), C.POINTER(C.c_uint64)]),
     "fdm_cloud_grid_max_z": (C.c_int, [C.c_uint64, C.POINTER(FdmCloudView), C.c_int, C.c_float, C.c_int, C.c_int,
                                        C.POINTER(FdmCloudOut), C.POINTER(C.c_uint64)]),
+    "fdm_cloud_estimate_normals": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P,
+                                             C.POINTER(C.c_uint64)]),
+    "fdm_normals_last_stats": (C.c_int, [C.POINTER(FdmNormalStats)]),
     "fdm_cloud_debug_profile": (C.c_int, [C.c_int]),
     "fdm_cloud_debug_last_ms": (C.c_int, [_F]),
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),

@@ -197,3 +197,5 @@ class PointCloud {
 };
 
 }  // namespace nanopcl
+
+#include "nanopcl/geometry/normal_estimation.hpp"  // estimateNormals, estimateCovariances, estimateNormalsCovariances

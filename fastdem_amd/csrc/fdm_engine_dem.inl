@@ -53,6 +53,51 @@ KnnGrid sor_grid(float min_x, float min_y, float max_x, float max_y, uint64_t n,
   return G;
 }
 
+// The k-NN search grid of n device points (fdm_knn.hpp): the column size picked for k, the points in column order and the
+// table of column starts, with the counters and the queue the search kernels fill.  Outlier removal and normal estimation
+// (fdm_engine_normals.inl) search the same grid.
+struct KnnIndex {
+  DevBuf b_stat, b_pts, b_start, b_queue;
+  SortBufs S;
+  KnnGrid G{};
+  KnnStat* st() const { return b_stat.as<KnnStat>(); }
+  const float4* pts() const { return b_pts.as<float4>(); }
+  const uint32_t* start() const { return b_start.as<uint32_t>(); }
+  uint32_t* queue() const { return b_queue.as<uint32_t>(); }
+};
+// bounds (and the refusal of a coordinate that is not finite), keys, sort, gather, starts.  Synchronises s once, for the
+// bounding box.
+int knn_grid_build(hipStream_t s, unsigned n, const float* dx, const float* dy, const float* dz, unsigned k, KnnIndex& I) {
+  if (int rc = I.b_stat.alloc(sizeof(KnnStat))) return rc;
+  KnnStat* const st = I.st();
+  const unsigned blocks = (n + 255u) / 256u;
+  hipLaunchKernelGGL(k_knn_init, dim3(1), dim3(64), 0, s, st);
+  hipLaunchKernelGGL(k_knn_bounds, dim3(std::min(blocks, 2048u)), dim3(256), 0, s, n, dx, dy, dz, st);
+  HIPCK(hipGetLastError());
+  KnnStat hs{};
+  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIPCK(hipStreamSynchronize(s));
+  if (hs.nonfinite)
+    return fail(FDM_ERR_INVALID, "the cloud has a coordinate that is not finite (undefined in the reference's k-d tree)");
+  I.G = sor_grid(unord_host(hs.min_x), unord_host(hs.min_y), unord_host(hs.max_x), unord_host(hs.max_y), n, k);
+  const KnnGrid& G = I.G;
+  const unsigned ncol = unsigned(G.gx) * unsigned(G.gy);
+  SortBufs& S = I.S;
+  if (int rc = S.alloc(n)) return rc;
+  if (int rc = I.b_pts.alloc(size_t(n) * sizeof(float4))) return rc;
+  if (int rc = I.b_start.alloc((size_t(ncol) + 1) * sizeof(uint32_t))) return rc;
+  if (int rc = I.b_queue.alloc(size_t(n) * sizeof(uint32_t))) return rc;
+  hipLaunchKernelGGL(k_knn_keys, dim3(blocks), dim3(256), 0, s, n, dx, dy, G, S.pairs.keys[0]);
+  const int side = rs_enqueue(s, S.pairs, n, rs_key_bits(ncol - 1u));
+  hipLaunchKernelGGL(k_knn_gather, dim3(blocks), dim3(256), 0, s, n, S.pairs.idx[side], dx, dy, dz, I.b_pts.as<float4>());
+  hipLaunchKernelGGL(k_knn_starts, dim3((ncol + 1u + 255u) / 256u), dim3(256), 0, s, n, S.pairs.keys[side], ncol,
+                     I.b_start.as<uint32_t>());
+  HIPCK(hipGetLastError());
+  return FDM_OK;
+}
+// the top-k bucket (KB of the search kernels) that holds k
+int knn_bucket(int k) { return k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64)); }
+
 template <int KB>
 void sor_search(hipStream_t s, unsigned n, int k, const float4* pts, const uint32_t* start, const KnnGrid& G,
                 float* mean, uint32_t* queue, KnnStat* st) {
@@ -71,39 +116,19 @@ int sor_device(hipStream_t s, unsigned n, const float* dx, const float* dy, cons
   g_sor_stats.n_queries = n;
   Events E;
   if (int rc = E.init(6)) return rc;
-  DevBuf b_stat;
-  if (int rc = b_stat.alloc(sizeof(KnnStat))) return rc;
-  KnnStat* const st = b_stat.as<KnnStat>();
   const unsigned blocks = (n + 255u) / 256u;
   HIPCK(hipEventRecord(E.ev[0], s));
-  hipLaunchKernelGGL(k_knn_init, dim3(1), dim3(64), 0, s, st);
-  hipLaunchKernelGGL(k_knn_bounds, dim3(std::min(blocks, 2048u)), dim3(256), 0, s, n, dx, dy, dz, st);
-  HIPCK(hipGetLastError());
+  KnnIndex I;
+  if (int rc = knn_grid_build(s, n, dx, dy, dz, unsigned(k), I)) return rc;
+  KnnStat* const st = I.st();
   KnnStat hs{};
-  HIPCK(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
-  HIPCK(hipStreamSynchronize(s));
-  if (hs.nonfinite)
-    return fail(FDM_ERR_INVALID, "the cloud has a coordinate that is not finite (undefined in the reference's k-d tree)");
-  const KnnGrid G = sor_grid(unord_host(hs.min_x), unord_host(hs.min_y), unord_host(hs.max_x), unord_host(hs.max_y), n,
-                             unsigned(k));
-  const unsigned ncol = unsigned(G.gx) * unsigned(G.gy);
+  const KnnGrid& G = I.G;
   g_sor_stats.grid_x = G.gx;
   g_sor_stats.grid_y = G.gy;
   g_sor_stats.voxel = G.h;
-  SortBufs S;
-  DevBuf b_pts, b_start, b_queue;
-  if (int rc = S.alloc(n)) return rc;
-  if (int rc = b_pts.alloc(size_t(n) * sizeof(float4))) return rc;
-  if (int rc = b_start.alloc((size_t(ncol) + 1) * sizeof(uint32_t))) return rc;
-  if (int rc = b_queue.alloc(size_t(n) * sizeof(uint32_t))) return rc;
-  hipLaunchKernelGGL(k_knn_keys, dim3(blocks), dim3(256), 0, s, n, dx, dy, G, S.pairs.keys[0]);
-  const int side = rs_enqueue(s, S.pairs, n, rs_key_bits(ncol - 1u));
-  hipLaunchKernelGGL(k_knn_gather, dim3(blocks), dim3(256), 0, s, n, S.pairs.idx[side], dx, dy, dz, b_pts.as<float4>());
-  hipLaunchKernelGGL(k_knn_starts, dim3((ncol + 1u + 255u) / 256u), dim3(256), 0, s, n, S.pairs.keys[side], ncol,
-                     b_start.as<uint32_t>());
-  HIPCK(hipGetLastError());
+  const DevBuf &b_pts = I.b_pts, &b_start = I.b_start, &b_queue = I.b_queue;
   HIPCK(hipEventRecord(E.ev[1], s));
-  const int bucket = k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
+  const int bucket = knn_bucket(k);
   switch (bucket) {
     case 4: sor_search<4>(s, n, k, b_pts.as<float4>(), b_start.as<uint32_t>(), G, d_mean, b_queue.as<uint32_t>(), st); break;
     case 16: sor_search<16>(s, n, k, b_pts.as<float4>(), b_start.as<uint32_t>(), G, d_mean, b_queue.as<uint32_t>(), st); break;

@@ -45,6 +45,7 @@
 #include "fdm_pcd.hpp"
 #include "fdm_ingest.hpp"
 #include "fdm_post.hpp"
+#include "fdm_normals.hpp"
 
 using namespace fdm;
 
@@ -408,6 +409,14 @@ int join_streams(fdm_engine* e);  // (a null engine: FDM_OK — every C entry po
 void poll_dense_paid(fdm_engine* e);
 int sync_all(fdm_engine* e);
 int pick_device(int device);  // the ordinal checked against the devices there are, then made current
+struct ScopedDevice {  // the thread's current device, put back when an engine-free cloud call returns
+  int prev = -1;
+  ScopedDevice() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+  ~ScopedDevice() { if (prev >= 0) (void)hipSetDevice(prev); }
+  ScopedDevice(const ScopedDevice&) = delete;
+  ScopedDevice& operator=(const ScopedDevice&) = delete;
+};
+bool cloud_profile_on();  // fdm_cloud_debug_profile's switch for the calling thread (fdm_engine_voxel.inl)
 // An engine-owned buffer that grows on demand: nothing if need <= *cap; else everything drains (sync_all), the old buffer
 // is freed and forgotten (*ptr null, *cap 0: a failed allocation leaves an empty buffer, never a stale one), and `want`
 // rows of `per` elements are allocated; *cap counts rows.  The contents are not kept.

@@ -13,11 +13,6 @@ struct ScopedDev {
   void* p = nullptr;
   ~ScopedDev() { if (p) (void)hipFree(p); }
 };
-struct ScopedDevice {  // the thread's current device, put back when the call returns
-  int prev = -1;
-  ScopedDevice() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~ScopedDevice() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 // fdm_cloud_debug_profile: the calling thread's calls are timed with four device events (none are created otherwise)
 struct StageClock {
   hipEvent_t ev[4] = {};
@@ -237,6 +232,10 @@ int cloud_downsample(uint64_t n, const fdm_cloud_view* in, int on_device, float 
   return FDM_OK;
 }
 }  // namespace
+
+namespace fdmh {
+bool cloud_profile_on() { return g_downsample_profile; }
+}  // namespace fdmh
 
 extern "C" {
 

@@ -22,6 +22,7 @@
 //                 squared distance are below 2^-22 relative).  A lane that is not done after kKnnShells rings — an
 //                 isolated outlier, the very thing SOR looks for — appends itself to a queue.
 //   k_knn_brute   one block per queued query over the whole cloud: per-lane top-k, merged in LDS
+// fdm_normals.hpp searches the same grid with the same walk (knn_walk) and keeps who the neighbours are as well.
 // Every loop bound is known on the host before launch: kKnnShells rings, runs of at most n points, at most n queue
 // entries, k rounds of the merge.
 #pragma once
@@ -40,7 +41,7 @@ struct KnnStat {
   uint32_t nonfinite;                   // some x, y or z is NaN or infinite
   uint32_t n_queue;                     // queries left to k_knn_brute
   uint32_t n_kept;                      // k_sor_keep
-  uint32_t pad;
+  uint32_t n_invalid;                   // points that got the invalid value (fdm_normals.hpp)
 };
 struct KnnGrid {
   float min_x, min_y, inv_h, h;
@@ -51,7 +52,7 @@ inline __global__ void k_knn_init(KnnStat* __restrict__ st) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     st->min_x = st->min_y = 0xFFFFFFFFu;
     st->max_x = st->max_y = 0u;
-    st->nonfinite = st->n_queue = st->n_kept = st->pad = 0u;
+    st->nonfinite = st->n_queue = st->n_kept = st->n_invalid = 0u;
   }
 }
 
@@ -139,6 +140,7 @@ struct KnnTop {
     for (int j = 0; j < KB; ++j) v[j] = j < KB - k ? -1.0f : __builtin_inff();
   }
   __device__ __forceinline__ float kth() const { return v[KB - 1]; }
+  __device__ __forceinline__ void offer(float d, float /*w*/) { push(d); }  // what knn_walk calls: who is not kept
   __device__ __forceinline__ void push(float d) {
     if (d < v[KB - 1]) {
       v[KB - 1] = d;
@@ -163,14 +165,12 @@ struct KnnTop {
   }
 };
 
-template <int KB>
-__global__ __launch_bounds__(256) void k_knn_search(unsigned n, int k, const float4* __restrict__ pts,
-                                                    const uint32_t* __restrict__ start, const KnnGrid G,
-                                                    float* __restrict__ mean, uint32_t* __restrict__ queue,
-                                                    KnnStat* __restrict__ st) {
-  const unsigned p = blockIdx.x * 256u + threadIdx.x;
-  if (p >= n) return;
-  const float4 q = pts[p];
+// The query at sorted position p walks rings of columns outward and offers every point it meets — itself too when SELF —
+// to `top` (offer(d2, w), kth()).  True once `top` holds the k nearest of the whole cloud: the whole grid was seen, or the
+// k-th squared distance is below the square of the ring's bound (the file comment); false after kKnnShells rings.
+template <bool SELF, class Top>
+__device__ __forceinline__ bool knn_walk(unsigned p, const float4& q, const float4* __restrict__ pts,
+                                         const uint32_t* __restrict__ start, const KnnGrid& G, Top& top) {
   const float ux = knn_u(q.x, G.min_x, G.inv_h), uy = knn_u(q.y, G.min_y, G.inv_h);
   const int cx = knn_col(ux, G.gx), cy = knn_col(uy, G.gy);
   float margin;
@@ -179,8 +179,6 @@ __global__ __launch_bounds__(256) void k_knn_search(unsigned n, int k, const flo
     margin = fminf(fminf(fx, 1.0f - fx), fminf(fy, 1.0f - fy));
     margin = margin > 0.0f ? margin : 0.0f;
   }
-  KnnTop<KB> top;
-  top.init(k);
   bool done = false;
 #pragma unroll 1
   for (int s = 0; s <= kKnnShells && !done; ++s) {
@@ -201,7 +199,10 @@ __global__ __launch_bounds__(256) void k_knn_search(unsigned n, int k, const flo
         const unsigned t0 = start[row + unsigned(xa)], t1 = start[row + unsigned(xb) + 1u];
 #pragma unroll 1
         for (unsigned t = t0; t < t1; ++t)
-          if (t != p) top.push(knn_dist2(q, pts[t]));
+          if (SELF || t != p) {
+            const float4 c = pts[t];
+            top.offer(knn_dist2(q, c), c.w);
+          }
       }
     }
     if (x0 == 0 && y0 == 0 && x1 == G.gx - 1 && y1 == G.gy - 1) { done = true; break; }  // the whole cloud was seen
@@ -211,7 +212,20 @@ __global__ __launch_bounds__(256) void k_knn_search(unsigned n, int k, const flo
       done = top.kth() < lb2;
     }
   }
-  if (done) mean[__float_as_uint(q.w)] = top.mean(k);
+  return done;
+}
+
+template <int KB>
+__global__ __launch_bounds__(256) void k_knn_search(unsigned n, int k, const float4* __restrict__ pts,
+                                                    const uint32_t* __restrict__ start, const KnnGrid G,
+                                                    float* __restrict__ mean, uint32_t* __restrict__ queue,
+                                                    KnnStat* __restrict__ st) {
+  const unsigned p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n) return;
+  const float4 q = pts[p];
+  KnnTop<KB> top;
+  top.init(k);
+  if (knn_walk<false>(p, q, pts, start, G, top)) mean[__float_as_uint(q.w)] = top.mean(k);
   else queue[atomicAdd(&st->n_queue, 1u)] = p;
 }
 

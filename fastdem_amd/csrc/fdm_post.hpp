@@ -1014,6 +1014,91 @@ __device__ __forceinline__ void eig3_direct(const float* cov, float* val, float*
   val[1] = ev[1] * scale + shift;
   val[2] = ev[2] * scale + shift;
 }
+// ... with all three eigenvectors: V column-major, column j the eigenvector of val[j] (normal estimation,
+// fdm_normals.hpp).  Up to the roots this is eig3_direct operation for operation; that one is kept as it is so that no
+// stencil result can move.  Columns k and l as there; column 1 = (column 2 x column 0), normalised.
+__device__ __forceinline__ void eig3_direct_all(const float* cov, float* val, float* V) {
+  const float shift = (cov[0] + cov[4] + cov[8]) / 3.0f;
+  float sm[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) sm[c * 3 + r] = r >= c ? cov[c * 3 + r] : cov[r * 3 + c];
+  sm[0] -= shift; sm[4] -= shift; sm[8] -= shift;
+  float scale = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) scale = fmaxf(scale, fabsf(sm[k]));
+  if (scale > 0.0f) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sm[k] /= scale;
+  }
+  const float s_inv3 = 1.0f / 3.0f, s_sqrt3 = sqrtf(3.0f);
+  const float c0 = sm[0] * sm[4] * sm[8] + 2.0f * sm[1] * sm[2] * sm[5] - sm[0] * sm[5] * sm[5] -
+                   sm[4] * sm[2] * sm[2] - sm[8] * sm[1] * sm[1];
+  const float c1 = sm[0] * sm[4] - sm[1] * sm[1] + sm[0] * sm[8] - sm[2] * sm[2] + sm[4] * sm[8] - sm[5] * sm[5];
+  const float c2 = sm[0] + sm[4] + sm[8];
+  const float c2_over_3 = c2 * s_inv3;
+  float a_over_3 = (c2 * c2_over_3 - c1) * s_inv3;
+  a_over_3 = fmaxf(a_over_3, 0.0f);
+  const float half_b = 0.5f * (c0 + c2_over_3 * (2.0f * c2_over_3 * c2_over_3 - c1));
+  float q = a_over_3 * a_over_3 * a_over_3 - half_b * half_b;
+  q = fmaxf(q, 0.0f);
+  const float rho = sqrtf(a_over_3);
+  const float theta = static_cast<float>(atan2(static_cast<double>(sqrtf(q)), static_cast<double>(half_b))) * s_inv3;
+  double sin_d, cos_d;
+  sincos(static_cast<double>(theta), &sin_d, &cos_d);
+  const float cos_theta = static_cast<float>(cos_d);
+  const float sin_theta = static_cast<float>(sin_d);
+  float ev[3];
+  ev[0] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
+  ev[1] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
+  ev[2] = c2_over_3 + 2.0f * rho * cos_theta;
+  const float eps = 1.1920929e-07f;
+  if ((ev[2] - ev[0]) <= eps) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0f : 0.0f;  // eivecs.setIdentity()
+  } else {
+    float d0 = ev[2] - ev[1];
+    const float d1 = ev[1] - ev[0];
+    int k = 0, l = 2;
+    if (d0 > d1) { k = 2; l = 0; d0 = d1; }
+    float tmp[9], vk[3], vl[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) tmp[i] = sm[i];
+    const float evk = k == 0 ? ev[0] : ev[2], evl = l == 0 ? ev[0] : ev[2];
+    tmp[0] -= evk; tmp[4] -= evk; tmp[8] -= evk;
+    eig3_kernel(tmp, vk, vl);
+    if (d0 <= 2.0f * eps * d1) {
+      const float dot = vk[0] * vl[0] + (vk[1] * vl[1] + vk[2] * vl[2]);
+      vl[0] -= dot * vl[0]; vl[1] -= dot * vl[1]; vl[2] -= dot * vl[2];
+      const float n = sqrtf(eig3_sqnorm(vl));
+      vl[0] /= n; vl[1] /= n; vl[2] /= n;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) tmp[i] = sm[i];
+      tmp[0] -= evl; tmp[4] -= evl; tmp[8] -= evl;
+      float dummy[3];
+      eig3_kernel(tmp, vl, dummy);
+    }
+    float a0[3], a2[3], c[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      a0[r] = k == 0 ? vk[r] : vl[r];
+      a2[r] = k == 0 ? vl[r] : vk[r];
+    }
+    eig3_cross(a2, a0, c);
+    const float n = sqrtf(eig3_sqnorm(c));
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      V[r] = a0[r];
+      V[3 + r] = c[r] / n;
+      V[6 + r] = a2[r];
+    }
+  }
+  val[0] = ev[0] * scale + shift;
+  val[1] = ev[1] * scale + shift;
+  val[2] = ev[2] * scale + shift;
+}
 
 // ---- feature extraction (feature_extraction.cpp:59-116) ----
 struct FeatureParams {

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi
 from .capi import (FdmCloud2Layout, FdmCloudOut, FdmCloudView, FdmConfig, FdmDemConfig, FdmDemStats, FdmGeometry, FdmRasterStats, FdmScanStats,
-                   FdmSorStats, FdmTile)
+                   FdmNormalStats, FdmSorStats, FdmTile)
 
 
 class EngineError(RuntimeError):
@@ -912,3 +912,50 @@ def grid_max_z(x, y, z, grid_size, intensity=None, rgb=None, normals=None, cov=N
     channel that point's.  Arguments and result as voxel_grid."""
     return _downsample(x, y, z, grid_size, None, intensity, rgb, normals, cov, order, device, return_index)
 
+
+def normals_last_stats():
+    """What this thread's last estimate_normals did: n_queries, n_fallback (queries the brute-force queue took),
+    n_invalid, grid_x, grid_y, voxel, ms (grid build, search, fallback queue, write; zeros unless
+    fdm_cloud_debug_profile is on)."""
+    st = FdmNormalStats()
+    _ck(capi.load().fdm_normals_last_stats(C.byref(st)))
+    return {"n_queries": int(st.n_queries), "n_fallback": int(st.n_fallback), "n_invalid": int(st.n_invalid),
+            "grid_x": int(st.grid_x), "grid_y": int(st.grid_y), "voxel": float(st.voxel),
+            "ms": tuple(float(v) for v in st.ms)}
+
+
+def estimate_normals(x, y, z, k=20, viewpoint=(0.0, 0.0, 0.0), covariances=False, device=0, return_stats=False):
+    """nanopcl::geometry::estimateNormals(cloud, k, viewpoint) on the device, or estimateNormalsCovariances with
+    covariances=True: per point the PCA of its k nearest points (itself included), the normal turned towards the
+    viewpoint, the covariance regularised for GICP to eigenvalues (1e-3, 1, 1).  numpy arrays in, numpy arrays out; torch
+    device tensors in, device tensors out.  Returns normals[n, 3], or (normals, cov[n, 3, 3]) with covariances; points
+    with fewer than 3 neighbours or a degenerate neighbourhood get a zero normal and the identity.  return_stats appends
+    normals_last_stats().  device: the ordinal numpy input runs on; torch tensors run on the device they live on."""
+    lib = capi.load()
+    vp = (C.c_float * 3)(*[float(np.float32(v)) for v in viewpoint])
+    n_invalid = C.c_uint64(0)
+    if _is_torch(x):
+        import torch
+        torch.cuda.current_stream(x.device).synchronize()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        x, y, z = (v.contiguous() for v in (x, y, z))
+        n = x.numel()
+        soa = torch.empty((3, n), dtype=torch.float32, device=x.device)
+        cov9 = torch.empty((n, 9), dtype=torch.float32, device=x.device) if covariances else None
+        _ck(lib.fdm_cloud_estimate_normals(n, _dptr(x), _dptr(y), _dptr(z), 1, int(k), vp, int(device), _dptr(soa[0]),
+                                           _dptr(soa[1]), _dptr(soa[2]), _dptr(cov9), C.byref(n_invalid)))
+        normals = soa.t().contiguous()
+        cov = cov9.view(n, 3, 3).transpose(1, 2).contiguous() if covariances else None   # column-major -> [row][column]
+    else:
+        x, y, z = _f32(x).reshape(-1), _f32(y).reshape(-1), _f32(z).reshape(-1)
+        n = x.size
+        soa = np.empty((3, n), dtype=np.float32)
+        cov9 = np.empty((n, 9), dtype=np.float32) if covariances else None
+        _ck(lib.fdm_cloud_estimate_normals(n, _ptr(x), _ptr(y), _ptr(z), 0, int(k), vp, int(device), _ptr(soa[0]),
+                                           _ptr(soa[1]), _ptr(soa[2]), _ptr(cov9), C.byref(n_invalid)))
+        normals = np.ascontiguousarray(soa.T)
+        cov = np.ascontiguousarray(cov9.reshape(n, 3, 3).transpose(0, 2, 1)) if covariances else None
+    out = (normals, cov) if covariances else (normals,)
+    if return_stats:
+        out = out + (normals_last_stats(),)
+    return out[0] if len(out) == 1 else out

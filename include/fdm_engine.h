@@ -607,6 +607,44 @@ int fdm_cloud_voxel_grid(uint64_t n, const fdm_cloud_view* in, int on_device, fl
 int fdm_cloud_grid_max_z(uint64_t n, const fdm_cloud_view* in, int on_device, float grid_size, int order, int device,
                          const fdm_cloud_out* out, uint64_t* n_out);
 
+/* ---- normals and GICP covariances of a cloud: nanopcl::geometry::estimateNormals, estimateCovariances and
+ * estimateNormalsCovariances in their k-NN form (geometry/normal_estimation.hpp:43-63, 107-124, 159-179;
+ * impl/normal_estimation_impl.hpp:33-68, impl/pca.hpp:34-107, impl/setters.hpp:20-105) ----
+ * Engine-free and synchronous, on `device`; host arrays in and out (on_device 0) or device arrays.  Give nx, ny, nz (all
+ * three or none), cov9 (9 floats per point, column-major), or both: both is the reference's single pass and equals the
+ * two separate calls bit for bit.
+ * NEIGHBOURS.  effective_k = min(size_t(k), n): a negative k means every point.  A point's neighbours are the
+ * effective_k points of the whole cloud, ITSELF INCLUDED at distance 0, that are smallest by (d2, input index), d2 =
+ * ((dx*dx) + (dy*dy)) + (dz*dz) in fp32 without contraction, d = query - point; they are taken in that order.  The
+ * search is EXACT; nanoflann's pruning bound is rounded and can miss a neighbour within rounding of the k-th (ASSUMED
+ * equal otherwise: DESIGN.md §7).  Where distances tie, nanoflann's order follows its tree traversal and cannot be
+ * restated: the tie-break by input index is THIS PROJECT'S DEFINITION.
+ * PCA.  Fewer than 3 neighbours (k in 0 .. 2, n < 3): invalid.  Otherwise offset = the first neighbour; sequential fp32
+ * sums over the neighbours in order of d = p - offset and of d_a * d_b; inv_n = 1.0f / float(m); cov(a, b) = (sum_sq(a,
+ * b) - (sum_a * sum_b) * inv_n) * inv_n (that reading of pca.hpp:55 ASSUMED: DESIGN.md §6); trace < FLT_EPSILON: invalid;
+ * else Eigen's computeDirect, eigenvalues ascending, eigenvectors V.
+ * OUTPUT.  normal = column 0 of V, negated when n . (viewpoint - p) < 0 (a dot of exactly 0 does not flip; viewpoint
+ * NULL = the origin); an invalid normal is (0, 0, 0).  covariance = V diag(1e-3f, 1, 1) VT, V's columns scaled first
+ * (ASSUMED, as the a0 b0 + (a1 b1 + a2 b2) order of every three-term dot: DESIGN.md §6); an invalid covariance is the
+ * identity.  *n_invalid (nullable, a host word) = the points that got the invalid value.
+ * n == 0: FDM_OK, nothing is touched.  FDM_ERR_INVALID: a coordinate that is NaN or infinite (looked for only where a
+ * search runs, effective_k >= 3); effective_k > 64; normals given in part; neither normals nor cov9; n >= 2^31.  The
+ * thread's current device is put back before the call returns. */
+int fdm_cloud_estimate_normals(uint64_t n, const float* x, const float* y, const float* z, int on_device, int k,
+                               const float viewpoint[3], int device, float* nx, float* ny, float* nz, float* cov9,
+                               uint64_t* n_invalid);
+typedef struct fdm_normal_stats {  /* the calling thread's last fdm_cloud_estimate_normals */
+  uint64_t n_queries, n_fallback;  /* points searched; ... of which the grid search left to the brute-force queue */
+  uint64_t n_invalid;              /* points that got the invalid value */
+  int32_t grid_x, grid_y;          /* columns of the search grid */
+  float voxel;                     /* their edge, metres */
+  /* device ms while fdm_cloud_debug_profile (fdm_engine_debug.h) is on, zeros otherwise: grid build; search; fallback
+   * queue; write.  The PCA is fused into the search and queue kernels, so `write` is what is left behind them: the
+   * counters' read-back and a host cloud's download */
+  float ms[4];
+} fdm_normal_stats;
+int fdm_normals_last_stats(fdm_normal_stats* out);
+
 typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
   float resolution;
   int32_t method;              /* RasterMethod: 0 Max, 1 Min, 2 Mean, 3 MinMax */

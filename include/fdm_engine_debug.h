@@ -41,7 +41,7 @@ int fdm_pcd_debug_last_kernel_ms(float ms2[2]);
 /* fdm_cloud_debug_profile(1): the calling thread's fdm_cloud_voxel_grid / fdm_cloud_grid_max_z calls are timed with
  * device events from now on (off by default: no event is created; scripts/voxel_bench.py).  fdm_cloud_debug_last_ms:
  * device ms of the last such call — keys and sort, run heads and staging, per-run reduction; zeros while the switch is
- * off. */
+ * off.  The same switch times fdm_cloud_estimate_normals' stages (fdm_normal_stats.ms, fdm_engine.h). */
 int fdm_cloud_debug_profile(int on);
 int fdm_cloud_debug_last_ms(float ms3[3]);
 
