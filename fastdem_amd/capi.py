@@ -118,6 +118,37 @@ class FdmNormalStats(C.Structure):  # fdm_normal_stats (include/fdm_engine.h)
                 ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("voxel", C.c_float), ("ms", C.c_float * 4)]
 
 
+class FdmAlignSettings(C.Structure):
+    """fdm_align_settings == nanopcl::registration::AlignSettings (registration/align.hpp:32-59)."""
+
+    _fields_ = [("max_correspondence_dist", C.c_float), ("max_iterations", C.c_int32), ("translation_eps", C.c_double),
+                ("rotation_eps", C.c_double), ("relative_error_eps", C.c_double), ("min_correspondences", C.c_uint64),
+                ("robust_kernel", C.c_int32), ("reserved", C.c_int32), ("robust_kernel_width", C.c_double),
+                ("covariance_epsilon", C.c_double)]
+
+
+class FdmRegisterClouds(C.Structure):  # fdm_register_clouds (include/fdm_engine.h)
+    _fields_ = [("n_source", C.c_uint64), ("sx", C.c_void_p), ("sy", C.c_void_p), ("sz", C.c_void_p),
+                ("s_cov9", C.c_void_p), ("n_target", C.c_uint64), ("tx", C.c_void_p), ("ty", C.c_void_p),
+                ("tz", C.c_void_p), ("tnx", C.c_void_p), ("tny", C.c_void_p), ("tnz", C.c_void_p),
+                ("t_cov9", C.c_void_p), ("on_device", C.c_int32)]
+
+
+class FdmRegistrationResult(C.Structure):  # fdm_registration_result
+    _fields_ = [("transform", C.c_double * 16), ("fitness", C.c_double), ("rmse", C.c_double),
+                ("iterations", C.c_uint64), ("converged", C.c_int32), ("has_covariance", C.c_int32),
+                ("covariance", C.c_double * 36)]
+
+
+class FdmRegisterStats(C.Structure):  # fdm_register_stats
+    _fields_ = [("n_source", C.c_uint64), ("n_target", C.c_uint64), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
+                ("voxel", C.c_float), ("ring_limit", C.c_int32), ("linearizations", C.c_int32), ("ms", C.c_float * 3)]
+
+
+REGISTER_METHOD = {"icp": 0, "plane": 1, "gicp": 2}
+ROBUST_KERNEL = {"none": 0, "huber": 1, "tukey": 2, "cauchy": 3}
+
+
 class FdmDemConfig(C.Structure):
     """fdm_dem_config == fastdem::DEMConfig (io/pcd_convert.hpp:28-42)."""
 
@@ -296,6 +327,12 @@ PROTOTYPES = {
     "fdm_cloud_estimate_normals": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P,
                                              C.POINTER(C.c_uint64)]),
     "fdm_normals_last_stats": (C.c_int, [C.POINTER(FdmNormalStats)]),
+    "fdm_default_align_settings": (None, [C.POINTER(FdmAlignSettings)]),
+    "fdm_cloud_register": (C.c_int, [C.c_int, C.POINTER(FdmRegisterClouds), _P, C.POINTER(FdmAlignSettings), C.c_int,
+                                     C.POINTER(FdmRegistrationResult)]),
+    "fdm_cloud_register_linearize": (C.c_int, [C.c_int, C.POINTER(FdmRegisterClouds), _P, C.POINTER(FdmAlignSettings),
+                                               C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), _P]),
+    "fdm_register_last_stats": (C.c_int, [C.POINTER(FdmRegisterStats)]),
     "fdm_cloud_debug_profile": (C.c_int, [C.c_int]),
     "fdm_cloud_debug_last_ms": (C.c_int, [_F]),
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),

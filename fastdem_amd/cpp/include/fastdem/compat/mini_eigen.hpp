@@ -9,6 +9,7 @@
 #include <array>
 #include <cmath>
 #include <cstddef>
+#include <utility>
 
 namespace Eigen {
 
@@ -151,6 +152,47 @@ class Isometry3d {
 
  private:
   std::array<double, 16> m_;
+};
+
+// Fixed-size dense matrix, column-major: what nanopcl/registration.hpp needs of Matrix<double, 6, 6> (the pose
+// covariance) and Matrix<double, 6, 1> (a twist).
+template <typename T, int R, int C>
+struct Matrix {
+  std::array<T, size_t(R * C)> m{};
+  T& operator()(int r, int c) { return m[size_t(c * R + r)]; }
+  T operator()(int r, int c) const { return m[size_t(c * R + r)]; }
+  T& operator()(int i) { static_assert(C == 1, ""); return m[size_t(i)]; }
+  T operator()(int i) const { static_assert(C == 1, ""); return m[size_t(i)]; }
+  T* data() { return m.data(); }
+  const T* data() const { return m.data(); }
+  static Matrix Zero() { return Matrix(); }
+  static Matrix Identity() { static_assert(R == C, ""); Matrix a; for (int i = 0; i < R; ++i) a(i, i) = T(1); return a; }
+  Matrix<T, C, R> transpose() const { Matrix<T, C, R> t; for (int r = 0; r < R; ++r) for (int c = 0; c < C; ++c) t(c, r) = (*this)(r, c); return t; }
+  Matrix operator-(const Matrix& o) const { Matrix d; for (size_t i = 0; i < m.size(); ++i) d.m[i] = m[i] - o.m[i]; return d; }
+  template <int K>
+  Matrix<T, R, K> operator*(const Matrix<T, C, K>& o) const {
+    Matrix<T, R, K> p;
+    for (int r = 0; r < R; ++r) for (int k = 0; k < K; ++k) { T s = 0; for (int c = 0; c < C; ++c) s += (*this)(r, c) * o(c, k); p(r, k) = s; }
+    return p;
+  }
+  T norm() const { T s = 0; for (T v : m) s += v * v; return std::sqrt(s); }
+  Matrix inverse() const {  // Gauss-Jordan with partial pivoting
+    static_assert(R == C, "");
+    Matrix a = *this, inv = Identity();
+    for (int k = 0; k < R; ++k) {
+      int piv = k;
+      for (int r = k + 1; r < R; ++r) if (std::fabs(a(r, k)) > std::fabs(a(piv, k))) piv = r;
+      for (int c = 0; c < R; ++c) { std::swap(a(k, c), a(piv, c)); std::swap(inv(k, c), inv(piv, c)); }
+      const T d = a(k, k);
+      for (int c = 0; c < R; ++c) { a(k, c) /= d; inv(k, c) /= d; }
+      for (int r = 0; r < R; ++r) {
+        if (r == k) continue;
+        const T f = a(r, k);
+        for (int c = 0; c < R; ++c) { a(r, c) -= f * a(k, c); inv(r, c) -= f * inv(k, c); }
+      }
+    }
+    return inv;
+  }
 };
 
 }  // namespace Eigen

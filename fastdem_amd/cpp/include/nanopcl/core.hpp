@@ -199,3 +199,4 @@ class PointCloud {
 }  // namespace nanopcl
 
 #include "nanopcl/geometry/normal_estimation.hpp"  // estimateNormals, estimateCovariances, estimateNormalsCovariances
+#include "nanopcl/registration.hpp"                // alignICP, alignPlaneICP, alignGICP

@@ -46,6 +46,8 @@
 #include "fdm_ingest.hpp"
 #include "fdm_post.hpp"
 #include "fdm_normals.hpp"
+#include "fdm_register.hpp"
+#include "fdm_register_host.hpp"
 
 using namespace fdm;
 

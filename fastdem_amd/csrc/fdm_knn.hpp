@@ -167,10 +167,15 @@ struct KnnTop {
 
 // The query at sorted position p walks rings of columns outward and offers every point it meets — itself too when SELF —
 // to `top` (offer(d2, w), kth()).  True once `top` holds the k nearest of the whole cloud: the whole grid was seen, or the
-// k-th squared distance is below the square of the ring's bound (the file comment); false after kKnnShells rings.
-template <bool SELF, class Top>
+// k-th squared distance is below the square of the ring's bound (the file comment); false after `rings` rings.
+// RADIUS (fdm_register.hpp: the query is no member of the grid and may lie outside its box — knn_col clamps and the margin
+// falls to 0, which only makes the bound more conservative): the walk also ends, true, once that bound's square exceeds
+// max_d2 — no unvisited point can then be within the radius — and the host picks `rings` so that one of the exits is
+// always taken.  The defaults are the walk of the k-NN kernels, unchanged.
+template <bool SELF, class Top, bool RADIUS = false>
 __device__ __forceinline__ bool knn_walk(unsigned p, const float4& q, const float4* __restrict__ pts,
-                                         const uint32_t* __restrict__ start, const KnnGrid& G, Top& top) {
+                                         const uint32_t* __restrict__ start, const KnnGrid& G, Top& top,
+                                         int rings = kKnnShells, float max_d2 = 0.0f) {
   const float ux = knn_u(q.x, G.min_x, G.inv_h), uy = knn_u(q.y, G.min_y, G.inv_h);
   const int cx = knn_col(ux, G.gx), cy = knn_col(uy, G.gy);
   float margin;
@@ -181,7 +186,7 @@ __device__ __forceinline__ bool knn_walk(unsigned p, const float4& q, const floa
   }
   bool done = false;
 #pragma unroll 1
-  for (int s = 0; s <= kKnnShells && !done; ++s) {
+  for (int s = 0; s <= rings && !done; ++s) {
     const int y0 = cy - s < 0 ? 0 : cy - s, y1 = cy + s > G.gy - 1 ? G.gy - 1 : cy + s;
     const int x0 = cx - s < 0 ? 0 : cx - s, x1 = cx + s > G.gx - 1 ? G.gx - 1 : cx + s;
 #pragma unroll 1
@@ -209,7 +214,7 @@ __device__ __forceinline__ bool knn_walk(unsigned p, const float4& q, const floa
     const float lb = __fmul_rn(__fmul_rn(float(s) + margin - 0.00390625f, G.h), 0.9999f);
     if (lb > 0.0f) {
       const float lb2 = __fmul_rn(__fmul_rn(lb, lb), 0.9999f);
-      done = top.kth() < lb2;
+      done = top.kth() < lb2 || (RADIUS && max_d2 < lb2);
     }
   }
   return done;

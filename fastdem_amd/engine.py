@@ -959,3 +959,157 @@ def estimate_normals(x, y, z, k=20, viewpoint=(0.0, 0.0, 0.0), covariances=False
     if return_stats:
         out = out + (normals_last_stats(),)
     return out[0] if len(out) == 1 else out
+
+
+class RegistrationResult:
+    """nanopcl::registration::RegistrationResult: transform (4 x 4, source -> target), fitness, rmse, iterations,
+    converged and covariance (6 x 6 in [v; omega] order, or None)."""
+
+    __slots__ = ("transform", "fitness", "rmse", "iterations", "converged", "covariance")
+
+    def __init__(self, transform, fitness, rmse, iterations, converged, covariance):
+        self.transform, self.fitness, self.rmse = transform, fitness, rmse
+        self.iterations, self.converged, self.covariance = iterations, converged, covariance
+
+    def success(self, min_fitness=0.5):
+        return self.converged and self.fitness >= min_fitness
+
+    def information_matrix(self):
+        return None if self.covariance is None else np.linalg.inv(self.covariance)
+
+    def __repr__(self):
+        return (f"RegistrationResult(fitness={self.fitness:.4g}, rmse={self.rmse:.4g}, iterations={self.iterations}, "
+                f"converged={self.converged}, covariance={'yes' if self.covariance is not None else 'None'})")
+
+
+def align_settings(**settings):
+    """fdm_align_settings with AlignSettings' defaults and the given fields: max_correspondence_dist, max_iterations,
+    translation_eps, rotation_eps, relative_error_eps, min_correspondences, robust_kernel ("none", "huber", "tukey",
+    "cauchy" or its number), robust_kernel_width, covariance_epsilon."""
+    st = capi.FdmAlignSettings()
+    capi.load().fdm_default_align_settings(C.byref(st))
+    names = {f[0] for f in capi.FdmAlignSettings._fields_} - {"reserved"}
+    for key, value in settings.items():
+        if key not in names:
+            raise TypeError(f"unknown registration setting {key!r}")
+        if key == "robust_kernel" and isinstance(value, str):
+            value = capi.ROBUST_KERNEL[value.lower()]
+        setattr(st, key, value)
+    return st
+
+
+def _register_clouds(source, target, target_normals, source_cov, target_cov):
+    """(FdmRegisterClouds, device or None, the arrays it points into) for numpy arrays or torch device tensors."""
+    sx, sy, sz = source
+    tx, ty, tz = target
+    torch_in = _is_torch(sx)
+    if torch_in:
+        import torch
+        torch.cuda.current_stream(sx.device).synchronize()
+        device = sx.device.index if sx.device.index is not None else torch.cuda.current_device()
+
+        def prep(v):
+            if v is None:
+                return None
+            if not _is_torch(v) or v.dtype != torch.float32 or v.device != sx.device:
+                raise TypeError("registration takes float32 tensors that all live on the source's device "
+                                "(or NumPy arrays throughout)")
+            return v.contiguous()
+        ptr, size = _dptr, lambda v: v.numel()                                     # noqa: E731
+        cov = lambda v, n: None if v is None else prep(v).reshape(n, 3, 3).transpose(1, 2).contiguous()   # noqa: E731
+    else:
+        device = None
+
+        def prep(v):
+            if _is_torch(v):
+                raise TypeError("registration takes NumPy arrays throughout or torch device tensors throughout")
+            return None if v is None else _f32(v).reshape(-1)
+        ptr, size = _ptr, lambda v: v.size                                         # noqa: E731
+        cov = lambda v, n: None if v is None else np.ascontiguousarray(prep(v).reshape(n, 3, 3).transpose(0, 2, 1))   # noqa: E731
+    if target_normals is not None and not isinstance(target_normals, (tuple, list)):
+        target_normals = tuple(target_normals[:, k] for k in range(3))              # an (n, 3) array
+    keep = [prep(v) for v in (sx, sy, sz, tx, ty, tz)] + [prep(v) for v in (target_normals or (None,) * 3)]
+    ns, nt = size(keep[0]), size(keep[3])
+    keep += [cov(source_cov, ns), cov(target_cov, nt)]                              # [row][column] -> column-major
+    p = [ptr(v) for v in keep]
+    clouds = capi.FdmRegisterClouds(ns, p[0], p[1], p[2], p[9], nt, p[3], p[4], p[5], p[6], p[7], p[8], p[10],
+                                    int(torch_in))
+    return clouds, device, keep
+
+
+def _guess16(T):
+    return None if T is None else (C.c_double * 16)(*_colmajor16(T))
+
+
+def _register(method, source, target, initial_guess, target_normals, source_cov, target_cov, device, settings):
+    clouds, dev, keep = _register_clouds(source, target, target_normals, source_cov, target_cov)
+    st = settings.pop("settings", None) or align_settings(**settings)
+    res = capi.FdmRegistrationResult()
+    _ck(capi.load().fdm_cloud_register(capi.REGISTER_METHOD[method], C.byref(clouds), _guess16(initial_guess),
+                                       C.byref(st), int(device if dev is None else dev), C.byref(res)))
+    del keep
+    T = np.array(res.transform, dtype=np.float64).reshape(4, 4).T.copy()
+    cov = np.array(res.covariance, dtype=np.float64).reshape(6, 6) if res.has_covariance else None
+    return RegistrationResult(T, float(res.fitness), float(res.rmse), int(res.iterations), bool(res.converged), cov)
+
+
+def align_icp(sx, sy, sz, tx, ty, tz, initial_guess=None, device=0, **settings):
+    """nanopcl::registration::alignICP(source, target, initial_guess, settings) on the device: point-to-point ICP.
+    numpy arrays or torch device tensors (they run on the device they live on); initial_guess a 4 x 4 matrix (None = the
+    identity); settings: the fields of AlignSettings by name (align_settings).  Returns a RegistrationResult."""
+    return _register("icp", (sx, sy, sz), (tx, ty, tz), initial_guess, None, None, None, device, settings)
+
+
+def align_plane_icp(sx, sy, sz, tx, ty, tz, target_normals, initial_guess=None, device=0, **settings):
+    """alignPlaneICP: point-to-plane ICP against the target's normals (three arrays or one of shape (n, 3), e.g. from
+    estimate_normals).  Otherwise as align_icp."""
+    return _register("plane", (sx, sy, sz), (tx, ty, tz), initial_guess, target_normals, None, None, device, settings)
+
+
+def align_gicp(sx, sy, sz, tx, ty, tz, source_cov, target_cov, initial_guess=None, device=0, **settings):
+    """alignGICP: generalized ICP with both clouds' covariances, (n, 3, 3) indexed [row][column] as
+    estimate_normals(..., covariances=True) returns them.  Otherwise as align_icp."""
+    return _register("gicp", (sx, sy, sz), (tx, ty, tz), initial_guess, None, source_cov, target_cov, device, settings)
+
+
+def linearize(method, sx, sy, sz, tx, ty, tz, transform=None, target_normals=None, source_cov=None, target_cov=None,
+              device=0, return_correspondences=False, **settings):
+    """One linearization of `method` ("icp", "plane", "gicp") at `transform` — the reference's linearizer: a dict with H
+    (6 x 6, symmetric), H_upper (21), b (6), error and num_inliers; return_correspondences adds "corr", the target index
+    of every source point (-1 for none)."""
+    clouds, dev, keep = _register_clouds((sx, sy, sz), (tx, ty, tz), target_normals, source_cov, target_cov)
+    st = settings.pop("settings", None) or align_settings(**settings)
+    H, b = (C.c_double * 21)(), (C.c_double * 6)()
+    err, cnt = C.c_double(0.0), C.c_uint64(0)
+    ns = int(clouds.n_source)
+    corr = None
+    if return_correspondences:
+        if clouds.on_device:
+            import torch
+            corr = torch.empty(ns, dtype=torch.int32, device=keep[0].device)
+        else:
+            corr = np.empty(ns, dtype=np.int32)
+    _ck(capi.load().fdm_cloud_register_linearize(capi.REGISTER_METHOD[method], C.byref(clouds), _guess16(transform),
+                                                 C.byref(st), int(device if dev is None else dev), H, b, C.byref(err),
+                                                 C.byref(cnt), (_dptr if clouds.on_device else _ptr)(corr)))
+    del keep
+    Hu = np.array(H, dtype=np.float64)
+    full = np.zeros((6, 6))
+    full[np.triu_indices(6)] = Hu
+    full = full + np.triu(full, 1).T
+    out = {"H": full, "H_upper": Hu, "b": np.array(b, dtype=np.float64), "error": float(err.value),
+           "num_inliers": int(cnt.value)}
+    if return_correspondences:
+        out["corr"] = corr
+    return out
+
+
+def register_last_stats():
+    """What this thread's last registration call did: n_source, n_target, grid_x, grid_y, voxel (the target's search
+    grid), ring_limit, linearizations, ms (grid build, regularisation, the linearizations summed; zeros unless
+    fdm_cloud_debug_profile is on)."""
+    st = capi.FdmRegisterStats()
+    _ck(capi.load().fdm_register_last_stats(C.byref(st)))
+    return {"n_source": int(st.n_source), "n_target": int(st.n_target), "grid_x": int(st.grid_x), "grid_y": int(st.grid_y),
+            "voxel": float(st.voxel), "ring_limit": int(st.ring_limit), "linearizations": int(st.linearizations),
+            "ms": tuple(float(v) for v in st.ms)}

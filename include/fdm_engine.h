@@ -645,6 +645,100 @@ typedef struct fdm_normal_stats {  /* the calling thread's last fdm_cloud_estima
 } fdm_normal_stats;
 int fdm_normals_last_stats(fdm_normal_stats* out);
 
+/* ---- registration of two clouds: nanopcl::registration::alignICP, alignPlaneICP and alignGICP (registration/align.hpp:
+ * 71-246; iterative_solver.hpp:96-219, criteria.hpp:40-68, optimizers/lm_optimizer.hpp:98-103, linearizers/
+ * linearizer.hpp:42-146, factors/{icp,plane,gicp}_factor.hpp, factors/robust_kernels.hpp:42-74, correspondence/
+ * kdtree_correspondence.hpp:57-120, core/lie.hpp:39-148) ----
+ * Engine-free and synchronous, on `device`; host arrays (on_device 0) or device arrays.  The per-iteration work — the
+ * transform, the nearest target point within the radius, the factor and the sum of the factors — runs on the device; the
+ * 6 x 6 algebra and the loop run on the host in double.  alignVGICP (the voxel distribution map) is not provided.
+ * LOOP.  T = initial_guess (16 doubles, column-major; NULL = the identity), prev_error = DBL_MAX, lambda = 1e-3 and never
+ * adapted.  Per iteration: linearize every source point at T; fewer inliers than min_correspondences: failed (T, fitness
+ * 0, rmse +inf, iterations = iter, not converged, no covariance); delta = (H + lambda I)^-1 (-b); new_T = se3Exp(delta) T;
+ * converged: new_T with iter + 1; else T = new_T, prev_error = error.  After max_iterations: T, not converged, the last
+ * model's statistics.  max_iterations <= 0: the initial guess, fitness 0, rmse +inf, 0 iterations.  An empty source or
+ * target: the initial guess, 0, +inf, 0, not converged, before any channel is looked at.
+ * delta is [v; omega]: se3Exp takes the first three as v and the last three as omega (so3Exp is the identity below
+ * |omega| = 1e-10, else Rodrigues; t = leftJacobian(omega) v with c1 = (1 - cos) / theta, c2 = (theta - sin) / theta).
+ * CONVERGENCE is criteria.hpp as written: |delta[3..5]| < translation_eps && |delta[0..2]| < rotation_eps — THE NAMES ARE
+ * SWAPPED relative to that layout: translation_eps bounds the rotation part and rotation_eps the translation part.  Kept,
+ * not corrected.  Converged also when rel_change < relative_error_eps, rel_change = prev > 0 ? |prev - curr| / prev : 0.
+ * CORRESPONDENCE.  p = T * source[i] in double, ((r0 x + r1 y) + r2 z) + t per row without contraction (ASSUMED order:
+ * DESIGN.md §6), rounded once to float; the nearest target point by d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in fp32, d = p -
+ * target; accepted iff d2 <= max_correspondence_dist * max_correspondence_dist (a float product).  Among equal distances
+ * the LOWER TARGET INDEX wins: this project's definition (nanoflann's pick follows its tree).  The factor uses the double
+ * p.  The search is exact.
+ * FACTORS, all in double as written in the reference.  ICP has no robust kernel; plane ICP weights by |r|, GICP by the
+ * Mahalanobis distance.  GICP regularises every covariance of both clouds once: cov(0, 0) not finite -> eps I; otherwise
+ * V diag(eps, 1, 1) VT = I - (1 - eps) v0 v0T from the lower triangle cast to double, v0 the unit eigenvector of the
+ * smallest eigenvalue, computed in double.  ASSUMED: an exactly diagonal input with equal diagonal gives diag(eps, 1, 1);
+ * any other coincidence of the two smallest eigenvalues is unspecified.  The source's is rotated R C RT per iteration; W =
+ * inverse3x3(C_src + C_tgt) by Cramer's rule.
+ * RESULT.  fitness = inliers / n_source; rmse = sqrt(2 error / inliers) — unguarded on the converged path as in
+ * makeSuccessResult, so converging on no inliers (min_correspondences 0, nothing in reach) gives NaN; the sums of the factors are taken in a fixed
+ * tree (no atomics): two calls on the same input return the same bits.
+ * DEVIATION.  The reference's covariance is Eigen's pivoted LDLT solve whenever isPositive(), which also holds for a
+ * semidefinite H (plane ICP on a planar target: rank 3), with the near-zero pivots zeroed.  Here has_covariance = 1 only
+ * when an unpivoted Cholesky in double of the last UNDAMPED H finds every pivot above n_source * 2^-52 * max diag(H);
+ * covariance (row-major, [v; omega] order) is then inverse(H).  Otherwise it is absent.
+ * FDM_ERR_INVALID: a coordinate of either cloud or an entry of the initial guess that is NaN or infinite; plane ICP
+ * without all three target normal arrays; GICP without both cov9 arrays; a negative or NaN max_correspondence_dist; an
+ * unknown method or kernel; n >= 2^31 in either cloud; a null x, y or z.  The thread's current device is put back before
+ * the call returns. */
+#define FDM_REGISTER_ICP 0
+#define FDM_REGISTER_PLANE 1
+#define FDM_REGISTER_GICP 2
+typedef struct fdm_align_settings {  /* registration::AlignSettings (align.hpp:32-59), field for field */
+  float max_correspondence_dist;     /* 1.0 */
+  int32_t max_iterations;            /* 50 */
+  double translation_eps;            /* 1e-4 */
+  double rotation_eps;               /* 1e-4 */
+  double relative_error_eps;         /* 1e-6 */
+  uint64_t min_correspondences;      /* 10 */
+  int32_t robust_kernel;             /* RobustKernel: 0 NONE, 1 HUBER, 2 TUKEY, 3 CAUCHY (plane ICP and GICP) */
+  int32_t reserved;
+  double robust_kernel_width;        /* 1.0 */
+  double covariance_epsilon;         /* 1e-3 (GICP) */
+} fdm_align_settings;
+void fdm_default_align_settings(fdm_align_settings* settings);
+typedef struct fdm_register_clouds {
+  uint64_t n_source;
+  const float *sx, *sy, *sz;
+  const float* s_cov9;               /* GICP: 9 floats per point, column-major; else NULL */
+  uint64_t n_target;
+  const float *tx, *ty, *tz;
+  const float *tnx, *tny, *tnz;      /* plane ICP: all three; else NULL */
+  const float* t_cov9;               /* GICP */
+  int32_t on_device;                 /* 0: host arrays, else device arrays */
+} fdm_register_clouds;
+typedef struct fdm_registration_result {  /* registration::RegistrationResult (result.hpp:27-60) */
+  double transform[16];              /* column-major, source -> target */
+  double fitness, rmse;
+  uint64_t iterations;
+  int32_t converged, has_covariance;
+  double covariance[36];             /* valid when has_covariance */
+} fdm_registration_result;
+/* method: FDM_REGISTER_ICP, _PLANE or _GICP; settings NULL = the defaults */
+int fdm_cloud_register(int method, const fdm_register_clouds* clouds, const double* initial_guess,
+                       const fdm_align_settings* settings, int device, fdm_registration_result* out);
+/* One linearization at `transform` (NULL = the identity) — the reference's linearizer: H[21] (upper triangle, row-major),
+ * b[6], the error and the inlier count.  corr (nullable; n_source int32, a host array for host clouds and a device array
+ * otherwise) receives the target index each source point corresponds to, -1 for none.  An empty cloud gives zeros. */
+int fdm_cloud_register_linearize(int method, const fdm_register_clouds* clouds, const double* transform,
+                                 const fdm_align_settings* settings, int device, double H[21], double b[6], double* error,
+                                 uint64_t* num_inliers, int32_t* corr);
+typedef struct fdm_register_stats {  /* the calling thread's last fdm_cloud_register / fdm_cloud_register_linearize */
+  uint64_t n_source, n_target;
+  int32_t grid_x, grid_y;            /* columns of the target's search grid */
+  float voxel;                       /* their edge, metres */
+  int32_t ring_limit;                /* rings a query may visit: those that cover the radius, capped by the grid */
+  int32_t linearizations;            /* linearize launches */
+  /* device ms while fdm_cloud_debug_profile (fdm_engine_debug.h) is on, zeros otherwise (no events are created then):
+   * the grid build; the regularisation of both clouds' covariances; the linearizations (search, factor and sums), summed */
+  float ms[3];
+} fdm_register_stats;
+int fdm_register_last_stats(fdm_register_stats* out);
+
 typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
   float resolution;
   int32_t method;              /* RasterMethod: 0 Max, 1 Min, 2 Mean, 3 MinMax */
