@@ -33,13 +33,18 @@
 //                + the cell's rank in the block's compacted list: a block's winners are one contiguous run); likewise
 //                the colour of a block-local last point.  The update finds the winner's entry through the slot in the
 //                reduced key (aux.w for the colour), and the caller's arrays are dead as soon as the launch has run.
-//   update half  64 cells per block (memory order), four threads per cell.  Round trip 1: the cell's keys of
-//                all scans (four scans per thread), its estimator record, the per-scan geometry.  The block's
-//                (cell, scan) events are then compacted into an LDS list (kEvCap entries) and spread evenly over
-//                the threads: round trip 2 fetches {aux, zs, obs} of ALL events at once (a thread holds 2-3 of them
-//                whatever their distribution over the cells), the observations go back through LDS to the cell's
-//                lead thread, which walks its events in scan order: strips vacated since the previous event,
-//                estimator step in registers, one record store.  With raycast_enabled (template RAY) the walk also
+//   update half  64 cells per block (memory order), four threads per cell, laid out group-major: thread q * 64 + c looks
+//                after scans 4 q .. 4 q + 3 of cell c, so wavefront q holds one group of four scans of all 64 cells and
+//                a key load is one contiguous run of keys per scan.  Round trip 1: the cell's keys of all scans, its
+//                estimator record, the per-scan geometry.  The cell's scan mask is OR-ed through a small LDS table
+//                (its threads sit in different wavefronts).  The block's (cell, scan) events are then compacted into an
+//                LDS list (kEvCap entries) and spread evenly over the threads: round trip 2 fetches {aux, zs, obs} of
+//                ALL events at once (a thread holds 2-3 of them whatever their distribution over the cells), the
+//                observations go back through LDS to the cell's OWNER — thread c, so the owners are wavefront 0, every
+//                lane of it a cell, and wavefronts 1-3 skip the serial part — which walks its events in scan order:
+//                strips vacated since the previous event, estimator step in registers, one record store.  (Beyond 16
+//                scans: 32 cells per block, eight threads per cell, thread q * 32 + c, the owners lanes 0-31 of
+//                wavefront 0.)  With raycast_enabled (template RAY) the walk also
 //                resolves every scan's raycasting stage behind that scan's observation — the images come from the
 //                launches of fdm_rbatch.hpp between the launch that binned the batch and this one.
 //
@@ -235,10 +240,16 @@ constexpr uint32_t kMRayEmpty = 0xFFFFFFFFu;  // (= kRayEmpty, fdm_raycast.hpp)
 template <bool COL, bool RAY>
 struct MUpdLds {
   MEvent ev[kEvCap];
-  MObs ob[kEvCap];
+  union {
+    MObs ob[kEvCap];
+    // the cell masks on their way from the cell's threads to everyone who numbers or applies its events, [group][cell of
+    // the block] (tpc x cpb = 256 either way): the four scan bits of a group, in place.  Read between the barrier behind
+    // round trip 1 and the first barrier of the round loop, which is where ob's first writer waits
+    struct { uint32_t tpart[256], rpart[RAY ? 256 : 1]; } mk;
+  };
   uint32_t rgb[COL ? kEvCap : 1];
   uint32_t rcnt[RAY ? kMaxBatch * kUpdCells : 1], rmin[RAY ? kMaxBatch * kUpdCells : 1];  // [scan][cell of the block]
-  unsigned s_w[4], s_t[4];
+  unsigned s_t[4];
 };
 template <bool COL, bool RAY>
 constexpr unsigned kMLdsBytes = sizeof(MUpdLds<COL, RAY>) > sizeof(MBinLds) ? sizeof(MUpdLds<COL, RAY>) : sizeof(MBinLds);
@@ -805,9 +816,12 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
 
 // ---------------------------------------------------------------------------------------------
 // update half: kUpdCells cells of the map (memory order), every scan of the batch.  Four threads per cell — thread
-// 4 c + q looks after cell c in scans 4 q .. 4 q + 3 — so that a block holds at most 1024 events (two rounds of
+// q * cpb + c looks after cell c in scans 4 q .. 4 q + 3 — so that a block holds at most 1024 events (two rounds of
 // the exchange) and the densest corner of the map (every cell touched by every scan) is a chain as short as any
-// other; the cell's own thread (q == 0) applies the events.
+// other; the cell's own thread (q == 0) applies the events.  Group-major, so the owners are dense: with 64 cells per
+// block wavefront q IS group q and wavefront 0 applies all events, one cell per lane; with 32 cells (eight threads per
+// cell) wavefront w holds groups 2 w and 2 w + 1 and the owners are lanes 0-31 of wavefront 0.  (Cell-major — thread
+// 4 c + q — left every wavefront walking the Kalman loop with one lane in four at work.)
 template <typename POLICY, int CH, bool RAY>
 __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, DevState* __restrict__ st,
                                              const typename POLICY::Layers& L,
@@ -819,10 +833,10 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
   const unsigned lt = threadIdx.x, lane = lt & 63u, wave = lt >> 6;
   const unsigned count = U.count;
   const unsigned tpc = upd_threads_per_cell(count), cpb = 256u / tpc;   // threads per cell, cells per block (block-uniform)
-  const unsigned cq = lt & (tpc - 1u), cl = tpc == 8u ? lt >> 3 : lt >> 2;
+  const unsigned cl = lt & (cpb - 1u), cq = tpc == 8u ? lt >> 5 : lt >> 6;   // cell of the block, group of four scans
   const unsigned o = bid * cpb + cl;
   const bool valid = o < ncell;
-  const bool owner = valid && cq == 0u;  // the thread that applies the cell's events
+  const bool owner = valid && cq == 0u;  // the thread that applies the cell's events: wavefront 0, lane = cell
   MState* const ms = U.ms;
 
   // ---- round trip 1: the thread's four keys, the per-scan geometry (lane j holds scan j's) ----
@@ -903,11 +917,8 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
 #pragma unroll
   for (int j = 0; j < kScansPerThread; ++j) nib |= (kk[j] != kEmptyKey) ? (1u << j) : 0u;
   FDM_PHASE(0);  // round trip 1 (keys, geometry) back
-  unsigned tmask = nib << (unsigned(kScansPerThread) * cq);  // the cell's scans, all four threads of the cell
-  tmask |= unsigned(__shfl_xor(int(tmask), 1));
-  tmask |= unsigned(__shfl_xor(int(tmask), 2));
-  if (tpc == 8u) tmask |= unsigned(__shfl_xor(int(tmask), 4));
-  unsigned rmask = 0u;  // the cell's ray events: scans whose stage left evidence or a ray height in it
+  // the cell's scans: the threads of a cell sit in different wavefronts, their parts meet in LDS (lt == cq * cpb + cl)
+  S.mk.tpart[lt] = nib << (unsigned(kScansPerThread) * cq);
   if (RAY) {
     unsigned rb = 0u;
 #pragma unroll
@@ -921,14 +932,11 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
       S.rcnt[k * kUpdCells + cl] = rc_[j];
       S.rmin[k * kUpdCells + cl] = rh_[j];
     }
-    rmask = rb << (unsigned(kScansPerThread) * cq);
-    rmask |= unsigned(__shfl_xor(int(rmask), 1));
-    rmask |= unsigned(__shfl_xor(int(rmask), 2));
-    if (tpc == 8u) rmask |= unsigned(__shfl_xor(int(rmask), 4));
+    S.mk.rpart[lt] = rb << (unsigned(kScansPerThread) * cq);
   }
-  // which scans' moves vacated THIS cell
+  // which scans' moves vacated THIS cell (asked by the owners only)
   unsigned smask = 0u;
-  if (stripmask) {
+  if (stripmask && cq == 0u) {
     const int r = int(o % unsigned(G.s_rows)) + G.s_r0;
     const int col = int(o / unsigned(G.s_rows)) + G.s_c0;
     while (stripmask) {
@@ -941,19 +949,31 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
     if (!valid) smask = 0u;
   }
 
-  // ---- the block's (cell, scan) events, numbered cell-major / scan-minor (= thread order) ----
-  const unsigned mine = unsigned(__popc(nib));
+  __syncthreads();
+  unsigned tmask = 0u, rmask = 0u;  // the cell's scans | its ray events: scans whose stage left evidence or a ray height in it
+#pragma unroll
+  for (unsigned g = 0; g < 4u; ++g) tmask |= S.mk.tpart[g * cpb + cl];
+  if (tpc == 8u) {
+#pragma unroll
+    for (unsigned g = 4; g < 8u; ++g) tmask |= S.mk.tpart[g * cpb + cl];
+  }
+  if (RAY && cq == 0u) {
+    for (unsigned g = 0; g < tpc; ++g) rmask |= S.mk.rpart[g * cpb + cl];
+  }
+
+  // ---- the block's (cell, scan) events, numbered cell-major / scan-minor: a cell's events stay one run, in scan
+  // order.  Lane c < cpb of EVERY wavefront holds cell c's mask, so each wavefront sums the cells in front for itself ----
+  const unsigned mine = lane < cpb ? unsigned(__popc(tmask)) : 0u;
   unsigned inc = mine;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const unsigned v = __shfl_up(inc, d);
     if (int(lane) >= d) inc += v;
   }
-  if (lane == 63u) S.s_w[wave] = inc;
-  __syncthreads();
-  unsigned base = inc - mine;
-  for (unsigned w2 = 0; w2 < wave; ++w2) base += S.s_w[w2];
-  const unsigned total = uni(S.s_w[0] + S.s_w[1] + S.s_w[2] + S.s_w[3]);
+  const unsigned total = unsigned(__builtin_amdgcn_readlane(int(inc), 63));
+  unsigned base = inc - mine;                                     // the events of the cells in front of this one,
+  if (tpc == 8u) base = unsigned(__shfl(int(base), int(cl)));     // (lanes 32-63: a second group of the same 32 cells)
+  base += unsigned(__popc(tmask & lowbits(unsigned(kScansPerThread) * cq)));  // the cell's own in earlier groups
 
   typename POLICY::State stt;
   POLICY::set_nan(stt);
