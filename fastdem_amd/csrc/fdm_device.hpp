@@ -476,6 +476,32 @@ __device__ __forceinline__ void kalman_core(KalmanState& s, float z, float meas_
     s.mean = new_mean;
   }
 }
+// kalman_core for a walk that is one wavefront's serial instruction stream (fdm_multi.hpp, the owners' event loop): both
+// arms of the two first-sample cases are computed and SELECTED — no divergent branch, no register copies to merge its arms.
+// Every operation of the arm kalman_core takes has the same operands in the same order, so the values kept are the same
+// bits; the other arm's results (a division by garbage traps nothing) are dropped.  R is the measurement variance
+// ALREADY substituted (meas_var > 0 ? meas_var : max_var — the exchange does it, KalmanRecPolicy::obs_var).  `fresh`:
+// the cell was vacated in front of this observation — x and mean count as NaN, and a first sample overwrites every
+// field of the state a later step or kalman_finish reads (x, P, count, mean, m2), so nobody has to NaN them first.
+__device__ __forceinline__ void kalman_core_sel(KalmanState& s, float z, float R, float min_var, float max_var, float q,
+                                                bool fresh) {
+  const bool first_x = isnan(s.x) | fresh;  // (| not ||: a short circuit comes back as a branch)
+  const float Pq = s.P + q;
+  const float K = Pq / (Pq + R);
+  const float xn = s.x + K * (z - s.x);
+  const float Pn = clampf((1.0f - K) * Pq, min_var, max_var);
+  const float cn = s.count + 1.0f;
+  s.x = first_x ? z : xn;
+  s.P = first_x ? R : Pn;
+  s.count = first_x ? 1.0f : cn;
+  const bool first_m = isnan(s.mean) | fresh;
+  const float delta = z - s.mean;
+  const float new_mean = s.mean + (delta / s.count);
+  const float delta2 = z - new_mean;
+  const float m2n = s.m2 + delta * delta2;
+  s.mean = first_m ? z : new_mean;
+  s.m2 = first_m ? 0.0f : m2n;
+}
 __device__ __forceinline__ void kalman_finish(KalmanState& s) {
   s.var = (s.count > 1.0f) ? s.m2 / (s.count - 1.0f) : 0.0f;
   const float sigma = sqrtf((0.0f < s.var) ? s.var : 0.0f);

@@ -767,7 +767,30 @@ struct KalmanRecPolicy {  // cell records
     t.smin = (isnan(t.smin) || min_z < t.smin) ? min_z : t.smin;
     t.smax = (isnan(t.smax) || max_z > t.smax) ? max_z : t.smax;
   }
+  // the step of the batch update's serial walk (fdm_multi.hpp, mupdate_body): R is what obs_var() made of the winner's
+  // variance in the exchange, `fresh` = the cell was vacated in front of this observation.  Branch-free (kalman_core_sel).
+  // The min / max tests are one compare each, !(smin <= z) for isnan(smin) || z < smin: min_z and max_z are never NaN — a
+  // cell's minimum is a point's z below FLT_MAX or FLT_MAX itself, its maximum a z above -FLT_MAX or -FLT_MAX (make_key,
+  // make_zmax: a NaN z loses both compares) — so with smin NaN both forms take z, and otherwise !(smin <= z) IS z < smin
+  // (equal values, -0 against +0 included, keep smin either way).  Not v_min / v_max: they order -0 below +0.
+  static __device__ __forceinline__ float obs_var(const Layers& L, float var) { return (var > 0.0f) ? var : L.max_var; }
+  // (the clamp's bounds in vector registers the compiler cannot rematerialise: its selects take no scalar operand
+  // beside their mask, and it would otherwise move both constants into a register once per event)
+  struct WalkRegs { float min_var, max_var; };
+  static __device__ __forceinline__ WalkRegs walk_regs(const Layers& L) {
+    WalkRegs w{L.min_var, L.max_var};
+    asm volatile("" : "+v"(w.min_var), "+v"(w.max_var));
+    return w;
+  }
+  static __device__ __forceinline__ void walk_step(const Layers& L, const WalkRegs& w, State& t, float min_z, float R,
+                                                   float max_z, bool fresh) {
+    kalman_core_sel(t.s, min_z, R, w.min_var, w.max_var, L.q, fresh);
+    t.smin = (fresh | !(t.smin <= min_z)) ? min_z : t.smin;
+    t.smax = (fresh | !(t.smax >= max_z)) ? max_z : t.smax;
+  }
   static __device__ __forceinline__ void finish(State& t) { kalman_finish(t.s); }
+  // what finish() computed is in registers HERE (the walk's tail computes everything before its first store)
+  static __device__ __forceinline__ void settle(State& t) { asm volatile("" : "+v"(t.s.var), "+v"(t.s.upper), "+v"(t.s.lower) : : "memory"); }
   static __device__ __forceinline__ float elevation(const State& t) { return t.s.x; }  // what store() leaves in the elevation field
   static __device__ __forceinline__ void store(const Layers& L, unsigned o, const State& t) {
     float4* r = reinterpret_cast<float4*>(L.rec + size_t(o) * kKalmanRec);
@@ -865,7 +888,17 @@ struct P2RecPolicy {  // cell records
     t.smin = (isnan(t.smin) || min_z < t.smin) ? min_z : t.smin;
     t.smax = (isnan(t.smax) || max_z > t.smax) ? max_z : t.smax;
   }
+  // (the walk's hooks, see KalmanRecPolicy: the quantile estimator reads no variance and keeps its step as it is)
+  static __device__ __forceinline__ float obs_var(const Layers&, float var) { return var; }
+  struct WalkRegs {};
+  static __device__ __forceinline__ WalkRegs walk_regs(const Layers&) { return {}; }
+  static __device__ __forceinline__ void walk_step(const Layers& L, const WalkRegs&, State& t, float min_z, float var,
+                                                   float max_z, bool fresh) {
+    if (fresh) set_nan(t);
+    step(L, t, min_z, var, max_z);
+  }
   static __device__ __forceinline__ void finish(State&) {}
+  static __device__ __forceinline__ void settle(State&) {}
   static __device__ __forceinline__ float elevation(const State& t) { return t.s.elevation; }
   static __device__ __forceinline__ void store(const Layers& L, unsigned o, const State& t) {
     float4* r = reinterpret_cast<float4*>(L.rec + size_t(o) * kP2Rec);

@@ -69,7 +69,10 @@ constexpr int kLineWords = 32;           // a 128-byte line of 32-bit words
 #ifndef FDM_MB_WAVES
 #define FDM_MB_WAVES 6  // waves per SIMD k_mbatch is compiled for (<= 80 VGPRs; the LDS allows 6 blocks per CU): every block of a 16-scan VLP-16 batch resident at once
 #endif
-constexpr int kKalmanWalkFrom = 12;     // Kalman batches: the first scan whose bin blocks take the walker's chain (fdm_engine_multi.inl)
+#ifndef FDM_KALMAN_WALK_FROM
+#define FDM_KALMAN_WALK_FROM 12
+#endif
+constexpr int kKalmanWalkFrom = FDM_KALMAN_WALK_FROM;  // Kalman batches: the first scan whose bin blocks take the walker's chain (fdm_engine_multi.inl)
 constexpr int kMStates = 4;              // ring of batch states: update b-1 | bin b | crop b+1 | being re-armed
 
 // Device-resident bookkeeping of one batch.  Every word other blocks poll or add to sits on its own 128-byte
@@ -232,11 +235,12 @@ struct MBinLds {
   unsigned s_pass[4], s_in[4], s_occ[4 * kMPts];
 };
 struct MEvent { uint32_t idx; uint16_t cell, k; };  // winner's slot in obs | cell in tile | scan
-struct MObs { float min_z, var, max_z, iobs; };
+struct alignas(16) MObs { float min_z, var, max_z, iobs; };  // (one 128-bit LDS access)
 constexpr unsigned kUpdCells = 64u;   // cells per update block at most (MUpd::tpc == 4; 32 with eight threads per cell)
 __host__ __device__ constexpr unsigned upd_threads_per_cell(unsigned count) { return count > 16u ? 8u : 4u; }
 __host__ __device__ constexpr unsigned upd_cells_per_block(unsigned count) { return 256u / upd_threads_per_cell(count); }
 constexpr uint32_t kMRayEmpty = 0xFFFFFFFFu;  // (= kRayEmpty, fdm_raycast.hpp)
+constexpr int kLayTab = 64;           // layer pointers an update block keeps in LDS for its all-layer wipes (MUpdLds::lay)
 template <bool COL, bool RAY>
 struct MUpdLds {
   MEvent ev[kEvCap];
@@ -250,6 +254,9 @@ struct MUpdLds {
   uint32_t rgb[COL ? kEvCap : 1];
   uint32_t rcnt[RAY ? kMaxBatch * kUpdCells : 1], rmin[RAY ? kMaxBatch * kUpdCells : 1];  // [scan][cell of the block]
   unsigned s_t[4];
+  // all_layers[0 .. kLayTab), copied by wavefront 1 during round trip 1: the owners' wipe of vacated cells reads its
+  // pointers here and not from global memory behind the walk.  (Not with RAY: those blocks' LDS is their occupancy.)
+  float* lay[RAY ? 1 : kLayTab];
 };
 template <bool COL, bool RAY>
 constexpr unsigned kMLdsBytes = sizeof(MUpdLds<COL, RAY>) > sizeof(MBinLds) ? sizeof(MUpdLds<COL, RAY>) : sizeof(MBinLds);
@@ -847,6 +854,10 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
     kk[j] = kEmptyKey;
     if (k < count && valid) kk[j] = U.key[size_t(k) * ncell + o];
   }
+  float* lay_p = nullptr;  // (wavefront 1, no owner in it: the layer pointers join round trip 1)
+  if constexpr (!RAY) {
+    if (wave == 1u && int(lane) < min(n_layers, kLayTab)) lay_p = all_layers[lane];
+  }
   int v_sr = 0, v_sc = 0, v_shr = 0, v_shc = 0;
   unsigned v_in = 0u;
   bool v_run = false;
@@ -919,6 +930,9 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
   FDM_PHASE(0);  // round trip 1 (keys, geometry) back
   // the cell's scans: the threads of a cell sit in different wavefronts, their parts meet in LDS (lt == cq * cpb + cl)
   S.mk.tpart[lt] = nib << (unsigned(kScansPerThread) * cq);
+  if constexpr (!RAY) {
+    if (wave == 1u) S.lay[lane] = lay_p;  // (all kLayTab entries: null beyond n_layers, read but never stored through)
+  }
   if (RAY) {
     unsigned rb = 0u;
 #pragma unroll
@@ -1027,6 +1041,32 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
     }
     if (int(k) == k_last_run) ray_val = ray;
   };
+  // Without the ray stage the owners' walk is the launch's longest dependent chain — ONE wavefront issuing in order, as
+  // long as (events of the block's busiest cell) x (instructions per event) — so everything an event does not change is
+  // decided here, once.  An owner knows its cell's scans (tmask) and the scans whose move vacated it (smask): the cell is
+  // wiped in front of its event of ordinal i exactly when some vacating scan s has that event as the first one at or
+  // after s (scan s moves the map BEFORE it observes: an event of scan s itself counts) — bit 31 - i of `wrev`, tested
+  // by sign and shifted out per event; a vacating scan behind the last event wipes in the tail (wipe_tail).  The flags
+  // the old loop carried as lane masks follow: an event happened / the record and the obstacle cell are dirty <=> tmask
+  // != 0 (a wipe inside the walk is always followed by an event), some strip wiped the cell <=> wrev != 0 || wipe_tail.
+  unsigned wrev = 0u, left = 0u;   // left: the owner's events still to be applied
+  const typename POLICY::WalkRegs wregs = POLICY::walk_regs(L);
+  bool wipe_tail = false, strip_walk = false;
+  float zlo = 0.0f, zhi = 0.0f;    // min_z / max_z of the cell's last observation (the obstacle layer reads only that one)
+  if constexpr (!RAY) {
+    if (owner) {
+      left = unsigned(__popc(tmask));
+      unsigned wbefore = 0u;
+      for (unsigned sm = smask; sm; sm &= sm - 1u) {
+        const unsigned s = unsigned(__ffs(int(sm))) - 1u;       // (< count <= 32)
+        const unsigned at = tmask & ~((1u << s) - 1u);           // the cell's events of scans >= s
+        if (at) wbefore |= 1u << unsigned(__popc(tmask & ((1u << (unsigned(__ffs(int(at))) - 1u)) - 1u)));
+        else wipe_tail = true;
+      }
+      wrev = __brev(wbefore);
+      strip_walk = wbefore != 0u;
+    }
+  }
   if (RAY && owner) {  // (rays cross most cells of the map: the cell's state was fetched with round trip 1, see rec_early)
     if (tmask | rmask) {
       stt = rec_early;
@@ -1089,7 +1129,7 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
       const uint32_t zm = ax_[q].x, imx = ax_[q].y, fst = ax_[q].z;
       MObs ob;
       ob.min_z = ob_[q].x;
-      ob.var = ob_[q].y;
+      ob.var = POLICY::obs_var(L, ob_[q].y);  // (Kalman: R, substituted here by 256 threads and not in the owners' walk)
       // (a zero maximum takes the sign of the first zero-valued point, see Scratch::zs)
       ob.max_z = zm ? ((zm == 0x80000000u && (zs_[q].x & 1u)) ? -0.0f : unord(zm)) : -kFltMax;
       ob.iobs = 0.0f;
@@ -1104,27 +1144,34 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
     __syncthreads();
     // the cells' own threads apply their events of this round, in scan order
     if constexpr (!RAY) {
-      while (m && e_next < r1) {
-        const unsigned k = unsigned(__ffs(int(m))) - 1u;
-        m &= m - 1u;
-        const MObs ob = S.ob[e_next - r0];
-        const uint32_t rgb = has_col ? S.rgb[e_next - r0] : 0u;
-        ++e_next;
-        const unsigned upto = lowbits(k + 1u), from = lowbits(lastp1);  // scans lastp1 .. k
-        if (smask & upto & ~from) {  // vacated since the last event: NaN in every layer (GridMap::move)
-          POLICY::set_nan(stt);
-          sint = nanv;
-          colv = 0x7FC00000u;
-          strip_any = true;
+      // The owner's events of this round are one run of the list, known before the round: counted down, the
+      // observation of event i + 1 read from LDS before the arithmetic of event i.  No scan number in the loop (the
+      // wipes go by event ordinal, see wrev); the obstacle value and the colour are the last event's, taken behind it.
+      unsigned n = (left != 0u && e_next < r1) ? min(left, r1 - e_next) : 0u;  // (left != 0: e_next >= r0)
+      if (n) {
+        const MObs* p = &S.ob[e_next - r0];
+        e_next += n;
+        left -= n;
+        auto apply = [&](const MObs& ob) {
+          const bool fresh = int(wrev) < 0;  // vacated since the last event: NaN in every layer (GridMap::move)
+          wrev <<= 1;
+          POLICY::walk_step(L, wregs, stt, ob.min_z, ob.var, ob.max_z, fresh);
+          if (has_int) {  // isnan(sint) || iobs > sint, two-sided (iobs can be NaN: a NaN intensity as the cell's first point)
+            const float hi = (ob.iobs > sint) ? ob.iobs : sint;
+            const float hn = isnan(sint) ? ob.iobs : hi;
+            sint = fresh ? ob.iobs : hn;
+          }
+        };
+        MObs nx = *p;
+        while (--n) {
+          const MObs ob = nx;
+          nx = *++p;
+          __builtin_amdgcn_sched_barrier(0);  // (the read stays in front of the arithmetic: its latency is the loop's otherwise)
+          apply(ob);
         }
-        POLICY::step(L, stt, ob.min_z, ob.var, ob.max_z);
-        obst = (ob.max_z > ob.min_z) ? ob.max_z : nanv;
-        obst_dirty = true;
-        if (has_int && (isnan(sint) || ob.iobs > sint)) sint = ob.iobs;
-        if (has_col) colv = rgb & 0x00FFFFFFu;
-        evt = true;
-        st_dirty = true;
-        lastp1 = k + 1u;
+        apply(nx);
+        zlo = nx.min_z; zhi = nx.max_z;
+        if (has_col) colv = S.rgb[p - S.ob] & 0x00FFFFFFu;  // (a later round's last event overwrites it)
       }
     } else {
       while (m | rm) {
@@ -1166,8 +1213,51 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
     }
   }
   FDM_PHASE(2);  // events applied
-  // the scans after the cell's last event
-  if (owner) {
+  if constexpr (!RAY) {
+    // The tail behind the walk, still on the launch's longest chain: every value the owner stores is computed first —
+    // the sample variance and the bounds included — then the stores leave back to back, in the order they always had
+    // (all-layer NaN, the record's NaN, record, obstacle, intensity, colour: a lane's stores to one address stay in
+    // program order, which is all the order there is to keep), with no load from global memory and no wait between them.
+    if (owner) {
+      const bool any_evt = tmask != 0u;
+      const unsigned last1 = 32u - unsigned(__clz(int(tmask)));  // the last event's scan + 1 (no event: 0)
+      const bool strips = strip_walk || wipe_tail;
+      // map_.clear(obstacle) by every scan that observed a cell (elevation_mapping.cpp:144-146), behind the cell's last observation
+      const bool obst_clear = wipe_tail || (umask & lowbits(count) & ~lowbits(last1)) != 0u;
+      const float obst_v = (any_evt && !obst_clear && zhi > zlo) ? zhi : nanv;
+      if (wipe_tail) { sint = nanv; colv = 0x7FC00000u; }  // vacated behind the last event: the wipe is all that is stored
+      POLICY::finish(stt);  // (no event: of a NaN state, not stored)
+      POLICY::settle(stt);
+      using gfloat = __attribute__((address_space(1))) float;  // (layers are global memory: no flat store)
+      if (strips) {
+        const int n_tab = min(n_layers, kLayTab);
+        static_assert(kLayTab % 8 == 0, "the wipe reads the table in groups of eight");
+        for (int l0 = 0; l0 < n_tab; l0 += 8) {
+          float* p[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) p[q] = S.lay[l0 + q];
+#pragma unroll
+          for (int q = 0; q < 8; ++q)
+            if (l0 + q < n_tab) ((gfloat*)p[q])[o] = nanv;
+        }
+        for (int l0 = kLayTab; l0 < n_layers; l0 += 8) {  // (more layers than the table holds: their pointers from memory)
+          float* p[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) p[q] = all_layers[min(l0 + q, n_layers - 1)];
+#pragma unroll
+          for (int q = 0; q < 8; ++q)
+            if (l0 + q < n_layers) ((gfloat*)p[q])[o] = nanv;
+        }
+        POLICY::clear_cell(L, o);
+      }
+      if (any_evt && !wipe_tail) POLICY::store(L, o, stt);
+      if (any_evt || obst_clear) L.obstacle[o] = obst_v;
+      if (has_int && (any_evt || strips)) L.intensity[size_t(o) * L.istride] = sint;
+      if (has_col && (any_evt || strips)) reinterpret_cast<uint32_t*>(L.color)[o] = colv;
+    }
+  }
+  // (RAY: the tail as it was — its instantiations have no register to spare) the scans after the cell's last event
+  if (RAY && owner) {
     const unsigned all = lowbits(count), from = lowbits(lastp1);
     const unsigned tail = all & ~from;
     if (smask & tail) {

@@ -3,7 +3,9 @@
 Cycle prices per wave64 instruction from scripts/ubench/valu_issue*.hip (gfx950): plain VOP2 add / sub / mul f32,
 add / sub u32, and / or / xor, mov, lshr / ashr = 2; every other vector instruction 4 (rcp / sqrt / rsq 8);
 scalar 4 (s_nop / s_waitcnt / s_barrier / branches not counted); LDS and memory instructions are listed apart.
-usage: asm_cost.py file.s <mangled-function-prefix> [top] [--files a.hpp,b.hpp]"""
+usage: asm_cost.py file.s <mangled-function-prefix> [top] [--files a.hpp,b.hpp] [--lines A:B]
+--lines A:B prices only lines A..B of the .s file (1-based, inclusive): one loop body cut out of the listing; without
+line tables everything is booked under one key and the totals are what counts."""
 import collections
 import re
 import sys
@@ -18,7 +20,10 @@ SLOW = {'v_rcp_f32', 'v_sqrt_f32', 'v_rsq_f32', 'v_rcp_f64', 'v_sqrt_f64', 'v_rs
 files, cur, on = {}, ('?', 0), False
 valu, salu, cyc, lds, mem = (collections.Counter() for _ in range(5))
 ops = collections.Counter()
-for line in src:
+lo, hi = 1, len(src)
+if '--lines' in sys.argv:
+    lo, hi = (int(v) for v in sys.argv[sys.argv.index('--lines') + 1].split(':'))
+for no, line in enumerate(src, 1):
     m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', line)
     if m:
         files[int(m.group(1))] = (m.group(3) or m.group(2)).split('/')[-1]
@@ -31,7 +36,7 @@ for line in src:
     if m:
         cur = (files.get(int(m.group(1)), '?'), int(m.group(2)))
         continue
-    if not on:
+    if not on or no < lo or no > hi:
         continue
     m = re.match(r'^\s+([vs]_\w+|ds_\w+|global_\w+|buffer_\w+|flat_\w+)', line)
     if not m:
