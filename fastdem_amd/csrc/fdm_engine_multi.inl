@@ -383,7 +383,6 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
     C0.scan_no0 = uint32_t(e->scan_no);
     if ((rc = launch_mbatch(e, ch, U0, B0, C0, K))) return rc;
   }
-  B.pre = 1u;
   // ... and the scouts of the batch after this one ride in this launch (option "batch_crop" 0: they never do)
   if (next_count >= 2u && gated && e->opt.batch_crop &&
       std::memcmp(scans[count].T_base_sensor, f.T_base_sensor, 16 * sizeof(double)) == 0) {

@@ -44,9 +44,14 @@
 //                lane of it a cell, and wavefronts 1-3 skip the serial part — which walks its events in scan order:
 //                strips vacated since the previous event, estimator step in registers, one record store.  (Beyond 16
 //                scans: 32 cells per block, eight threads per cell, thread q * 32 + c, the owners lanes 0-31 of
-//                wavefront 0.)  With raycast_enabled (template RAY) the walk also
+//                wavefront 0.)  In the code: mupdate_body is the front all instantiations share (round trip 1, the
+//                masks, the event numbers: mupd_commit, mupd_vacated, mupd_number), then the owners' walk of its
+//                variant, which runs the rounds of the exchange (mupd_exchange) — mupd_walk_plain, or with
+//                raycast_enabled (template RAY) mupd_walk_ray, which also
 //                resolves every scan's raycasting stage behind that scan's observation — the images come from the
 //                launches of fdm_rbatch.hpp between the launch that binned the batch and this one.
+//   the chain    of moves has one arithmetic (lane_f64, mchain_nearest, mchain_shift), used by the walker (mwalk_batch)
+//                and by the bin blocks' own walk (mbin_body).
 //
 // All per-batch parameters travel as kernel arguments (< 4 KB): no copy command, no upload kernel.
 // Algorithmic bytes are per scan what they were: 12 B/point (+4 intensity, +4 colour), 72 / 124 B per
@@ -92,7 +97,7 @@ struct MCommon {  // what all scans of a batch share
   float sp[4];
   float Tbs[16];  // T_base_sensor (one sensor per batch: a scan with another extrinsic closes the batch)
   int sensor_type, integrate_mode, do_move, gate_on_filter, has_var, bin_table;
-  int dbg, walk;                 // walk: 1 = the chain of moves is walked one launch ahead (mwalk_body).  dbg, measurement only: 1 = no scratch atomics, 2 = no chain walk (both: wrong results); 3 = every move by the reference's divide; 4 = a chain wait reports MState::err as if it had run out of polls (tests)
+  int dbg, walk;                 // walk: 1 = the chain of moves is walked one launch ahead (mwalk_body).  dbg, measurement only: 1 = no scratch atomics, 2 = no chain walk (both: wrong results); 3 = every move by the reference's divide (tests)
   int walk_from, pad;            // with walk: scans k >= walk_from take the pre-walked chain, the bin blocks of earlier scans walk their own
   unsigned long long* timeline;  // measurement only (nullable): {start, end} of every block in 100 MHz ticks
 };
@@ -107,8 +112,7 @@ struct MBin {     // bin half: batch b
   const MState* prev;                    // the previous batch's state while its update shares this launch (else null)
   unsigned prev_count;
   unsigned obs_stride;                   // points per scan slot of obs / cobs
-  unsigned pre;                          // (always 1: scouts decided the batch's pass bits before this launch)
-  unsigned pad;
+  unsigned pad[2];
   // per-scan scratch, slot k at + k * ncell (key, aux, zs as in Scratch)
   unsigned long long* key;
   uint4* aux;
@@ -187,6 +191,14 @@ struct MView {
   float min_sq, max_sq, z_min, z_max;
   int sensor_type, integrate_mode;
 };
+// the batch's shared members + one scan's transforms (null for the scouts: the crops need neither)
+__device__ __forceinline__ MView mview(const MCommon& K, const float* Twb12, const float* R) {
+  MView V;
+  V.Tbs = K.Tbs; V.Twb12 = Twb12; V.R = R; V.sp = K.sp;
+  V.min_sq = K.min_sq; V.max_sq = K.max_sq; V.z_min = K.z_min; V.z_max = K.z_max;
+  V.sensor_type = K.sensor_type; V.integrate_mode = K.integrate_mode;
+  return V;
+}
 
 // p <- T * p for a T whose last row is (0 0 0 1), stored without it: the same products and sums, in the same
 // order, as transform4 on the full matrix (the row's coefficients are the literals 0 and 1).
@@ -270,10 +282,7 @@ constexpr unsigned kMLdsBytes = sizeof(MUpdLds<COL, RAY>) > sizeof(MBinLds) ? si
 // traffic, for sixteen bits: configs[2] 10.5 us per scan, VERDICT r03 #6.)
 constexpr unsigned kMScout = 4u;
 __device__ __forceinline__ void mcrop_body(const MCrop& Cn, const MCommon& K, const unsigned k, const unsigned sb) {
-  MView V;
-  V.Tbs = K.Tbs; V.Twb12 = nullptr; V.R = nullptr; V.sp = K.sp;
-  V.min_sq = K.min_sq; V.max_sq = K.max_sq; V.z_min = K.z_min; V.z_max = K.z_max;
-  V.sensor_type = K.sensor_type; V.integrate_mode = K.integrate_mode;
+  const MView V = mview(K, nullptr, nullptr);
   const unsigned n = Cn.n[k];
   const float* __restrict__ const px = Cn.px[k];
   const float* __restrict__ const py = Cn.py[k];
@@ -330,50 +339,57 @@ __device__ __forceinline__ DevGeom mbatch_start(const MState* __restrict__ prev,
   }
   return g;
 }
+// The arithmetic of a chain of moves, shared by the walker (mwalk_batch) and the bin blocks' own walk (mbin_body): both
+// must produce the reference's numbers, so there is one copy.  move() snaps the position to the grid p0 + integer * res, so
+// in exact arithmetic the TOTAL shift after scan j's move is round((pose_j - p0) / res) whatever happened before it: lane j
+// of a wavefront rounds its scan's pose ONCE against the chain's start (mchain_nearest), with move_candidate_fast's own
+// margins (1e-4 cell off a rounding tie; the accumulated position differs from p0 + V res by ~1e-10 cell at most), and the
+// walk takes scan j's shift as that total minus the cells shifted so far.  A pose within the margin of a tie (a robot
+// advancing half a cell per scan) takes the reference's subtract + divide against the position accumulated so far, at its
+// place in the walk (mchain_shift).
+//
+// lane j's double, in every lane
+__device__ __forceinline__ double lane_f64(double v, unsigned j) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), int(j));
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), int(j));
+  return __hiloint2double(hi, lo);
+}
+// t = a rounded half away from zero; is it the reference's shift for certain?  (a = (pose - p0) / res, estimated)
+__device__ __forceinline__ bool mchain_nearest(double a, double p0, int& t) {
+  t = 0;
+  if (!(fabs(p0) < 1.0e7)) return false;
+  if (fabs(a) <= 1e-4) return true;
+  const double ue = a + 0.5 * (a > 0 ? 1 : -1);
+  t = static_cast<int>(ue);
+  const double f = fabs(ue - double(t));
+  return f > 1e-4 && f < 1.0 - 1e-4 && fabs(ue) < 1.0e6;
+}
+// scan j's move along one axis against the position walked so far: p, v cells from the chain's start.  Lane j holds
+// scan j's pose and its rounding t; bit j of `sure`: that rounding is off every tie
+__device__ __forceinline__ int mchain_shift(unsigned sure, int t, double pose, unsigned j, double p, int v, const GeomConst& G) {
+  if ((sure >> j) & 1u) return __builtin_amdgcn_readlane(t, int(j)) - v;
+  // GridMap::move's own arithmetic (the quotient correctly rounded: div_by_res)
+  const double q = div_by_res(lane_f64(pose, j) - p, G.res, G.inv_res);
+  return static_cast<int>(q + 0.5 * (q > 0 ? 1 : -1));
+}
 // One batch's chain from `g` on (every lane of one wavefront, uniformly; lane j holds scan j's pose): E / C of every scan
-// into `out` (nullable), the last scan's returned.  The arithmetic is mbin_body's chain walk (see there for `nearest`,
-// the margins and the divide).
+// into `out` (nullable), the last scan's returned.
 __device__ __forceinline__ void mwalk_batch(DevGeom g, const unsigned count, const double* __restrict__ rx,
                                             const double* __restrict__ ry, const unsigned passmask, const MCommon& K,
                                             const GeomConst& G, MState* __restrict__ out, DevGeom& e_last, DevCand& c_last) {
   const unsigned lane = threadIdx.x & 63u;
   double pose_x = 0.0, pose_y = 0.0;
   if (lane < count) { pose_x = rx[lane]; pose_y = ry[lane]; }
-  auto lane_f64 = [](double v, unsigned j) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), int(j));
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), int(j));
-    return __hiloint2double(hi, lo);
-  };
-  auto nearest = [&](double a, double p0, int& t) -> bool {
-    t = 0;
-    if (!(fabs(p0) < 1.0e7)) return false;
-    if (fabs(a) <= 1e-4) return true;
-    const double ue = a + 0.5 * (a > 0 ? 1 : -1);
-    t = static_cast<int>(ue);
-    const double f = fabs(ue - double(t));
-    return f > 1e-4 && f < 1.0 - 1e-4 && fabs(ue) < 1.0e6;
-  };
   int tx = 0, ty = 0;
-  const bool sx = nearest((pose_x - g.px) * G.inv_res, g.px, tx), sy = nearest((pose_y - g.py) * G.inv_res, g.py, ty);
+  const bool sx = mchain_nearest((pose_x - g.px) * G.inv_res, g.px, tx), sy = mchain_nearest((pose_y - g.py) * G.inv_res, g.py, ty);
   const unsigned sure_x = K.dbg == 3 ? 0u : uni(unsigned(__ballot(sx))), sure_y = K.dbg == 3 ? 0u : uni(unsigned(__ballot(sy)));
   int vx = 0, vy = 0;
   DevCand c;
   c.px = g.px; c.py = g.py; c.sr = g.sr; c.sc = g.sc; c.shr = 0; c.shc = 0;
 #pragma unroll 1
   for (unsigned k = 0; k < count; ++k) {
-    int dx, dy;
-    if ((sure_x >> k) & 1u) {
-      dx = __builtin_amdgcn_readlane(tx, int(k)) - vx;
-    } else {
-      const double t = div_by_res(lane_f64(pose_x, k) - g.px, G.res, G.inv_res);
-      dx = static_cast<int>(t + 0.5 * (t > 0 ? 1 : -1));
-    }
-    if ((sure_y >> k) & 1u) {
-      dy = __builtin_amdgcn_readlane(ty, int(k)) - vy;
-    } else {
-      const double t = div_by_res(lane_f64(pose_y, k) - g.py, G.res, G.inv_res);
-      dy = static_cast<int>(t + 0.5 * (t > 0 ? 1 : -1));
-    }
+    const int dx = mchain_shift(sure_x, tx, pose_x, k, g.px, vx, G);
+    const int dy = mchain_shift(sure_y, ty, pose_y, k, g.py, vy, G);
     c.sr = g.sr - dx; c.sc = g.sc - dy;
     wrap_index(c.sr, G.rows);
     wrap_index(c.sc, G.cols);
@@ -430,10 +446,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
   const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   MState* const ms = B.ms;
-  MView V;
-  V.Tbs = K.Tbs; V.Twb12 = B.t[k].Twb; V.R = B.t[k].R; V.sp = K.sp;
-  V.min_sq = K.min_sq; V.max_sq = K.max_sq; V.z_min = K.z_min; V.z_max = K.z_max;
-  V.sensor_type = K.sensor_type; V.integrate_mode = K.integrate_mode;
+  const MView V = mview(K, B.t[k].Twb, B.t[k].R);
   const float* __restrict__ const px = B.px[k];
   const float* __restrict__ const py = B.py[k];
   const float* __restrict__ const pz = B.pz[k];
@@ -494,19 +507,8 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   FDM_PHASE(1);
 #endif
   // The chain of moves up to this scan, given which of the earlier scans moved the map — walked by the whole first
-  // wavefront (lane j holds scan j's pose), because a serial instruction costs ~10 ns on a full chip and a block of
-  // the batch's last scan used to spend 6.6 us here.  move() snaps the position to the grid p0 + integer * res, so in
-  // exact arithmetic the TOTAL shift after scan j's move is round((pose_j - p0) / res) whatever happened before it:
-  // lane j rounds its pose ONCE, with move_candidate_fast's own margins (1e-4 cell off a rounding tie; the accumulated
-  // position differs from p0 + V res by ~1e-10 cell at most), and the walk only accumulates the position in scan
-  // order, p <- p + double(v) * res and the per-step index wrap — the operations the reference performs.  A pose that
-  // sits within the margin of a tie (a robot advancing half a cell per scan) takes the reference's subtract + divide
-  // against the position accumulated so far, at its place in the walk.
-  auto lane_f64 = [](double v, unsigned j) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), int(j));
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), int(j));
-    return __hiloint2double(hi, lo);
-  };
+  // wavefront (lane j holds scan j's pose: mchain_nearest, mchain_shift), because a serial instruction costs ~10 ns on a
+  // full chip and a block of the batch's last scan used to spend 6.6 us here.
   auto chain = [&](unsigned passmask) {  // (every lane of the first wavefront, uniformly)
     if (K.do_move && K.walk && K.dbg != 2 && K.dbg != 3 && k >= unsigned(K.walk_from) && uni(w_valid) != 0u &&
         ((uni(w_pre) ^ passmask) & lowbits(k)) == 0u) {  // pre-walked (mwalk_body): nothing to walk
@@ -526,32 +528,13 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     DevCand c;
     c.px = g.px; c.py = g.py; c.sr = g.sr; c.sc = g.sc; c.shr = 0; c.shc = 0;
     if (K.do_move) {
-      auto nearest = [&](double a, double p0, int& t) -> bool {
-        t = 0;
-        if (!(fabs(p0) < 1.0e7)) return false;
-        if (fabs(a) <= 1e-4) return true;
-        const double ue = a + 0.5 * (a > 0 ? 1 : -1);
-        t = static_cast<int>(ue);
-        const double f = fabs(ue - double(t));
-        return f > 1e-4 && f < 1.0 - 1e-4 && fabs(ue) < 1.0e6;
-      };
       int tx = 0, ty = 0;
-      const bool sx = nearest((pose_x - g.px) * G.inv_res, g.px, tx), sy = nearest((pose_y - g.py) * G.inv_res, g.py, ty);
-      const unsigned sure_x = K.dbg == 3 ? 0u : uni(unsigned(__ballot(sx))), sure_y = K.dbg == 3 ? 0u : uni(unsigned(__ballot(sy)));
+  const bool sx = mchain_nearest((pose_x - g.px) * G.inv_res, g.px, tx), sy = mchain_nearest((pose_y - g.py) * G.inv_res, g.py, ty);
+  const unsigned sure_x = K.dbg == 3 ? 0u : uni(unsigned(__ballot(sx))), sure_y = K.dbg == 3 ? 0u : uni(unsigned(__ballot(sy)));
       int vx = 0, vy = 0;  // total shift so far, in cells
       auto shift_of = [&](unsigned j, int& dx, int& dy) {  // scan j's move against the geometry walked so far
-        if ((sure_x >> j) & 1u) {
-          dx = __builtin_amdgcn_readlane(tx, int(j)) - vx;
-        } else {  // GridMap::move's own arithmetic (the quotient correctly rounded: div_by_res)
-          const double t = div_by_res(lane_f64(pose_x, j) - g.px, G.res, G.inv_res);
-          dx = static_cast<int>(t + 0.5 * (t > 0 ? 1 : -1));
-        }
-        if ((sure_y >> j) & 1u) {
-          dy = __builtin_amdgcn_readlane(ty, int(j)) - vy;
-        } else {
-          const double t = div_by_res(lane_f64(pose_y, j) - g.py, G.res, G.inv_res);
-          dy = static_cast<int>(t + 0.5 * (t > 0 ? 1 : -1));
-        }
+        dx = mchain_shift(sure_x, tx, pose_x, j, g.px, vx, G);
+        dy = mchain_shift(sure_y, ty, pose_y, j, g.py, vy, G);
       };
       unsigned m = K.dbg == 2 ? 0u : ((K.gate_on_filter ? passmask : 0xFFFFFFFFu) & lowbits(k));  // the moves ahead of scan k
       bool unwrapped = false;
@@ -829,14 +812,444 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
 // block wavefront q IS group q and wavefront 0 applies all events, one cell per lane; with 32 cells (eight threads per
 // cell) wavefront w holds groups 2 w and 2 w + 1 and the owners are lanes 0-31 of wavefront 0.  (Cell-major — thread
 // 4 c + q — left every wavefront walking the Kalman loop with one lane in four at work.)
+//
+// mupdate_body is the front every instantiation shares — round trip 1, the masks, the event numbers; its pieces are the
+// functions mupd_* below — and then the owners' walk of its variant: mupd_walk_plain (no ray stage) or mupd_walk_ray
+// (raycast_enabled).  A walk runs the rounds of the exchange (mupd_exchange, shared), applies the owner's events of each
+// round and stores the cell.
+//
+// What the front hands the walk: the thread's place in the block, its cell and the batch's scans that concern it.
+struct MCell {
+  unsigned bid, cpb;        // the block | cells per block
+  unsigned o, cl, cq;       // the cell in memory order | in the block | the thread's group of four scans
+  unsigned count;           // scans of the batch
+  bool owner;               // this thread applies the cell's events
+  unsigned nib;             // bit j: scan 4 cq + j observed the cell
+  unsigned base, total;     // the number of the thread's first event | the block's events
+  unsigned tmask, smask;    // scans that observed the cell | whose move vacated it
+  unsigned umask;           // scans that observed any cell
+  unsigned rmask, runmask;  // ray stage (else 0): scans that left evidence or a ray height in the cell | whose stage runs
+};
+
+// Block 0 behind round trip 1: thread 0 commits the geometry ring behind the batch (make_ctx does this per scan), threads
+// 64 .. 64 + kMaxBatch re-arm the state of the batch after next.
+template <int CH, bool RAY>
+__device__ __forceinline__ void mupd_commit(const MUpd& U, DevState* __restrict__ st, const unsigned bid,
+                                            const unsigned passbits, const unsigned umask, const unsigned runmask) {
+  constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
+  const unsigned lt = threadIdx.x, count = U.count;
+  MState* const ms = U.ms;
+  if (bid == 0 && lt == 0) {
+    const unsigned last = count - 1u;
+    const unsigned slot_next = (U.scan_no0 + count) & 3u;
+    DevGeom g = ms->E[last];
+    const DevCand cl2 = ms->C[last];
+    const bool applied_last = U.do_move && (!U.gate_on_filter || ((passbits >> last) & 1u) != 0u);
+    if (applied_last) { g.px = cl2.px; g.py = cl2.py; g.sr = cl2.sr; g.sc = cl2.sc; }
+    const unsigned ob_prev = st->obst[U.scan_no0 & 3u].scan;
+    st->geom[slot_next] = g;
+    st->cand[(U.scan_no0 + last) & 3u] = cl2;   // (the synchronous statistics report the last scan's shift)
+    // the last scan of the batch that observed a cell (umask: one bit per scan)
+    st->obst[slot_next].scan = umask ? U.scan_no0 + (31u - unsigned(__clz(int(umask)))) : ob_prev;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { st->flags[q].any_pass = 0u; st->flags[q].any_inside = 0u; st->flags[q].ray_any = 0u; }
+    if (umask) {
+      const unsigned first_upd = U.scan_no0 + unsigned(__ffs(int(umask))) - 1u;
+      if (has_int && st->vis_int == 0u) st->vis_int = 3u * first_upd + 2u;
+      if (has_col && st->vis_col == 0u) st->vis_col = 3u * first_upd + 2u;
+    }
+    if constexpr (RAY) {  // the three layers become visible with the first frame that runs (raycasting.cpp:223-226)
+      if (runmask && st->vis_ray == 0u) st->vis_ray = 3u * (U.scan_no0 + unsigned(__ffs(int(runmask))) - 1u) + 3u;
+    }
+  }
+  if (bid == 0 && lt >= 64u && lt < 64u + unsigned(kMaxBatch)) {
+    U.rearm->inside[lt - 64u] = 0u;
+    if (lt == 64u) { U.rearm->flags[0] = 0u; U.rearm->flags[1] = 0u; U.rearm->flags[2] = 0u; }
+  }
+}
+// Which scans' moves vacated cell o (lane k holds scan k's geometry; stripmask: the scans whose move vacated any cell).
+__device__ __forceinline__ unsigned mupd_vacated(unsigned stripmask, const GeomConst& G, const unsigned o, const bool valid,
+                                                 const int v_sr, const int v_sc, const int v_shr, const int v_shc) {
+  unsigned smask = 0u;
+  const int r = int(o % unsigned(G.s_rows)) + G.s_r0;
+  const int col = int(o / unsigned(G.s_rows)) + G.s_c0;
+  while (stripmask) {
+    const unsigned k = unsigned(__ffs(int(stripmask))) - 1u;
+    stripmask &= stripmask - 1u;
+    const int sr = __builtin_amdgcn_readlane(v_sr, int(k)), sc = __builtin_amdgcn_readlane(v_sc, int(k));
+    const int shr = __builtin_amdgcn_readlane(v_shr, int(k)), shc = __builtin_amdgcn_readlane(v_shc, int(k));
+    if (in_cleared_strip(r, sr, shr, G.rows) || in_cleared_strip(col, sc, shc, G.cols)) smask |= 1u << k;
+  }
+  if (!valid) smask = 0u;
+  return smask;
+}
+// The block's (cell, scan) events, numbered cell-major / scan-minor: a cell's events stay one run, in scan order.  Lane
+// c < cpb of EVERY wavefront holds cell c's mask, so each wavefront sums the cells in front for itself.  Returns the
+// number of the thread's first event; total: the block's events.
+__device__ __forceinline__ unsigned mupd_number(const unsigned tmask, const unsigned tpc, const unsigned cpb,
+                                                const unsigned cl, const unsigned cq, unsigned& total) {
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned mine = lane < cpb ? unsigned(__popc(tmask)) : 0u;
+  unsigned inc = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned v = __shfl_up(inc, d);
+    if (int(lane) >= d) inc += v;
+  }
+  total = unsigned(__builtin_amdgcn_readlane(int(inc), 63));
+  unsigned base = inc - mine;                                     // the events of the cells in front of this one,
+  if (tpc == 8u) base = unsigned(__shfl(int(base), int(cl)));     // (lanes 32-63: a second group of the same 32 cells)
+  base += unsigned(__popc(tmask & lowbits(unsigned(kScansPerThread) * cq)));  // the cell's own in earlier groups
+  return base;
+}
+// One round [r0, r1) of the exchange: every thread lists its (at most four) events of the round, then round trip 2
+// fetches {aux, zs, obs} of every listed event, spread evenly over the block (kEvCap / 256 per thread), leaves the
+// observations in S.ob / S.rgb for the owners and the scratch clean.  `join`: what else leaves with round trip 2.
+template <typename POLICY, int CH, typename LDS, typename JOIN>
+__device__ __forceinline__ void mupd_exchange(const MUpd& U, const typename POLICY::Layers& L, LDS& S, const MCell& c,
+                                              const unsigned long long (&kk)[kScansPerThread], const unsigned ncell,
+                                              const unsigned r0, const unsigned r1, JOIN join) {
+  constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
+  const float nanv = __uint_as_float(0x7FC00000u);
+  const unsigned lt = threadIdx.x, bid = c.bid, cpb = c.cpb;
+  {
+    unsigned e = c.base;
+#pragma unroll
+    for (int j = 0; j < kScansPerThread; ++j) {
+      if ((c.nib >> j) & 1u) {
+        if (e >= r0 && e < r1) {
+          MEvent ev;
+          ev.idx = uint32_t(kk[j]);
+          ev.cell = uint16_t(c.cl);
+          ev.k = uint16_t(c.cq * unsigned(kScansPerThread) + unsigned(j));
+          S.ev[e - r0] = ev;
+        }
+        ++e;
+      }
+    }
+  }
+  __syncthreads();
+  constexpr int kPer = kEvCap / 256;
+  MEvent ev_[kPer];
+  float2 ob_[kPer];
+  uint4 ax_[kPer];
+  uint2 zs_[kPer];
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    const unsigned j = lt + unsigned(q) * 256u;
+    ob_[q] = make_float2(kFltMax, 0.0f);  // (no finite z: FLT_MAX, variance 0 — elevation_mapping.hpp:26-34)
+    ax_[q] = make_uint4(0u, 0u, kNoIdx, 0u);
+    zs_[q] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+    ev_[q].idx = kNoIdx; ev_[q].cell = 0; ev_[q].k = 0;
+    if (r0 + j < r1) {
+      ev_[q] = S.ev[j];
+      const size_t oc = size_t(ev_[q].k) * ncell + (bid * cpb + ev_[q].cell);
+      if (ev_[q].idx != kNoIdx) ob_[q] = U.obs[size_t(ev_[q].k) * U.obs_stride + ev_[q].idx];
+      ax_[q] = U.aux[oc];
+      zs_[q] = U.zs[oc];
+    }
+  }
+  join();
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    const unsigned j = lt + unsigned(q) * 256u;
+    if (r0 + j >= r1) continue;
+    if (has_col) S.rgb[j] = U.cobs[size_t(ev_[q].k) * U.obs_stride + ax_[q].w];  // (one more dependent gather)
+    const uint32_t zm = ax_[q].x, imx = ax_[q].y, fst = ax_[q].z;
+    MObs ob;
+    ob.min_z = ob_[q].x;
+    ob.var = POLICY::obs_var(L, ob_[q].y);  // (Kalman: R, substituted here by 256 threads and not in the owners' walk)
+    // (a zero maximum takes the sign of the first zero-valued point, see Scratch::zs)
+    ob.max_z = zm ? ((zm == 0x80000000u && (zs_[q].x & 1u)) ? -0.0f : unord(zm)) : -kFltMax;
+    ob.iobs = 0.0f;
+    if (has_int) ob.iobs = (fst & 1u) ? nanv : ((imx == 0x80000000u && (zs_[q].y & 1u)) ? -0.0f : unord(imx));
+    S.ob[j] = ob;
+    FDM_PHASE(1);  // round trip 2 (observations, record) back
+    const size_t oc = size_t(ev_[q].k) * ncell + (bid * cpb + ev_[q].cell);
+    U.key[oc] = kEmptyKey;  // the scratch is clean again for the batch after next
+    U.aux[oc] = make_uint4(0u, 0u, kNoIdx, 0u);
+    if ((zs_[q].x & zs_[q].y) != 0xFFFFFFFFu) U.zs[oc] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+  }
+}
+// NaN in layers [from, to) of cell o, eight at a time: eight pointers from `layer(l)`, then eight stores through CELL*
+// (float, or float in address space 1: global memory, no flat store).
+template <typename CELL, typename SRC>
+__device__ __forceinline__ void mwipe_layers(const int from, const int to, const unsigned o, SRC layer) {
+  const float nanv = __uint_as_float(0x7FC00000u);
+  for (int l0 = from; l0 < to; l0 += 8) {
+    float* p[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) p[q] = layer(l0 + q);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (l0 + q < to) ((CELL*)p[q])[o] = nanv;
+  }
+}
+
+// ---- the owners' walk without the ray stage ----
+// It is the launch's longest dependent chain — ONE wavefront issuing in order, as long as (events of the block's busiest
+// cell) x (instructions per event) — so everything an event does not change is decided here, once.  An owner knows its
+// cell's scans (tmask) and the scans whose move vacated it (smask): the cell is wiped in front of its event of ordinal i
+// exactly when some vacating scan s has that event as the first one at or after s (scan s moves the map BEFORE it
+// observes: an event of scan s itself counts) — bit 31 - i of `wrev`, tested by sign and shifted out per event; a
+// vacating scan behind the last event wipes in the tail (wipe_tail).  No flags travel through the loop: an event happened
+// / the record and the obstacle cell are dirty <=> tmask != 0 (a wipe inside the walk is always followed by an event),
+// some strip wiped the cell <=> wrev != 0 || wipe_tail.
+template <typename POLICY, int CH>
+__device__ __forceinline__ void mupd_walk_plain(const MUpd& U, const typename POLICY::Layers& L,
+                                                MUpdLds<(CH & 2) != 0, false>& S, const MCell& c,
+                                                const unsigned long long (&kk)[kScansPerThread], const unsigned ncell,
+                                                float* const* __restrict__ all_layers, const int n_layers) {
+  constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
+  const float nanv = __uint_as_float(0x7FC00000u);
+  const unsigned o = c.o;
+  typename POLICY::State stt;
+  POLICY::set_nan(stt);
+  float sint = nanv;
+  unsigned e_next = c.base;        // the number of the owner's next event
+  uint32_t colv = 0x7FC00000u;
+  unsigned wrev = 0u, left = 0u;   // left: the owner's events still to be applied
+  const typename POLICY::WalkRegs wregs = POLICY::walk_regs(L);
+  bool wipe_tail = false, strip_walk = false;
+  float zlo = 0.0f, zhi = 0.0f;    // min_z / max_z of the cell's last observation (the obstacle layer reads only that one)
+  if (c.owner) {
+    left = unsigned(__popc(c.tmask));
+    unsigned wbefore = 0u;
+    for (unsigned sm = c.smask; sm; sm &= sm - 1u) {
+      const unsigned s = unsigned(__ffs(int(sm))) - 1u;       // (< count <= 32)
+      const unsigned at = c.tmask & ~((1u << s) - 1u);         // the cell's events of scans >= s
+      if (at) wbefore |= 1u << unsigned(__popc(c.tmask & ((1u << (unsigned(__ffs(int(at))) - 1u)) - 1u)));
+      else wipe_tail = true;
+    }
+    wrev = __brev(wbefore);
+    strip_walk = wbefore != 0u;
+  }
+#pragma unroll 1
+  for (unsigned r0 = 0; r0 < c.total; r0 += unsigned(kEvCap)) {  // one round for all but the densest corners
+    const unsigned r1 = min(r0 + unsigned(kEvCap), c.total);
+    mupd_exchange<POLICY, CH>(U, L, S, c, kk, ncell, r0, r1, [&]() {
+      if (r0 == 0u && c.owner && c.tmask) {  // (the record joins the same round trip)
+        POLICY::load(L, o, stt);
+        if (has_int) sint = L.intensity[size_t(o) * L.istride];
+      }
+    });
+    __syncthreads();
+    // The owner's events of this round are one run of the list, known before the round: counted down, the
+    // observation of event i + 1 read from LDS before the arithmetic of event i.  No scan number in the loop (the
+    // wipes go by event ordinal, see wrev); the obstacle value and the colour are the last event's, taken behind it.
+    unsigned n = (left != 0u && e_next < r1) ? min(left, r1 - e_next) : 0u;  // (left != 0: e_next >= r0)
+    if (n) {
+      const MObs* p = &S.ob[e_next - r0];
+      e_next += n;
+      left -= n;
+      auto apply = [&](const MObs& ob) {
+        const bool fresh = int(wrev) < 0;  // vacated since the last event: NaN in every layer (GridMap::move)
+        wrev <<= 1;
+        POLICY::walk_step(L, wregs, stt, ob.min_z, ob.var, ob.max_z, fresh);
+        if (has_int) {  // isnan(sint) || iobs > sint, two-sided (iobs can be NaN: a NaN intensity as the cell's first point)
+          const float hi = (ob.iobs > sint) ? ob.iobs : sint;
+          const float hn = isnan(sint) ? ob.iobs : hi;
+          sint = fresh ? ob.iobs : hn;
+        }
+      };
+      MObs nx = *p;
+      while (--n) {
+        const MObs ob = nx;
+        nx = *++p;
+        __builtin_amdgcn_sched_barrier(0);  // (the read stays in front of the arithmetic: its latency is the loop's otherwise)
+        apply(ob);
+      }
+      apply(nx);
+      zlo = nx.min_z; zhi = nx.max_z;
+      if (has_col) colv = S.rgb[p - S.ob] & 0x00FFFFFFu;  // (a later round's last event overwrites it)
+    }
+    __syncthreads();  // (the next round reuses the lists)
+  }
+  FDM_PHASE(2);  // events applied
+  // The tail behind the walk, still on the launch's longest chain: every value the owner stores is computed first —
+  // the sample variance and the bounds included — then the stores leave back to back, in the order they always had
+  // (all-layer NaN, the record's NaN, record, obstacle, intensity, colour: a lane's stores to one address stay in
+  // program order, which is all the order there is to keep), with no load from global memory and no wait between them.
+  if (c.owner) {
+    const bool any_evt = c.tmask != 0u;
+    const unsigned last1 = 32u - unsigned(__clz(int(c.tmask)));  // the last event's scan + 1 (no event: 0)
+    const bool strips = strip_walk || wipe_tail;
+    // map_.clear(obstacle) by every scan that observed a cell (elevation_mapping.cpp:144-146), behind the cell's last observation
+    const bool obst_clear = wipe_tail || (c.umask & lowbits(c.count) & ~lowbits(last1)) != 0u;
+    const float obst_v = (any_evt && !obst_clear && zhi > zlo) ? zhi : nanv;
+    if (wipe_tail) { sint = nanv; colv = 0x7FC00000u; }  // vacated behind the last event: the wipe is all that is stored
+    POLICY::finish(stt);  // (no event: of a NaN state, not stored)
+    POLICY::settle(stt);
+    if (strips) {  // the pointers from the LDS table; beyond what it holds, from memory
+      using gfloat = __attribute__((address_space(1))) float;  // (layers are global memory: no flat store)
+      static_assert(kLayTab % 8 == 0, "the wipe reads the table in groups of eight");
+      mwipe_layers<gfloat>(0, min(n_layers, kLayTab), o, [&](int l) { return S.lay[l]; });
+      mwipe_layers<gfloat>(kLayTab, n_layers, o, [&](int l) { return all_layers[min(l, n_layers - 1)]; });
+      POLICY::clear_cell(L, o);
+    }
+    if (any_evt && !wipe_tail) POLICY::store(L, o, stt);
+    if (any_evt || obst_clear) L.obstacle[o] = obst_v;
+    if (has_int && (any_evt || strips)) L.intensity[size_t(o) * L.istride] = sint;
+    if (has_col && (any_evt || strips)) reinterpret_cast<uint32_t*>(L.color)[o] = colv;
+  }
+}
+
+// ---- the owners' walk with the ray stage ----
+// Rays cross most cells of the map, so nearly every cell has an event and the cell's stored state was asked for with
+// round trip 1 (MRayEarly).  The walk goes by scan number over the cell's observations (m) and ray events (rm) together
+// and resolves scan k's raycasting stage behind scan k's observation.  (These instantiations have no register to spare:
+// loop and tail are the ones the update half had before the walk above was shortened.)
+template <typename POLICY>
+struct MRayEarly {  // the owner's record, intensity and visibility log-odds as stored
+  typename POLICY::State rec;
+  float sint, lo;
+};
+template <typename POLICY, int CH>
+__device__ __forceinline__ void mupd_walk_ray(const MUpd& U, const typename POLICY::Layers& L,
+                                              MUpdLds<(CH & 2) != 0, true>& S, const MCell& c,
+                                              const unsigned long long (&kk)[kScansPerThread], const unsigned ncell,
+                                              float* const* __restrict__ all_layers, const int n_layers,
+                                              const MRayEarly<POLICY>& early) {
+  constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
+  const float nanv = __uint_as_float(0x7FC00000u);
+  const unsigned o = c.o, cl = c.cl;
+  const MRay& ray = U.ray;
+  typename POLICY::State stt;
+  POLICY::set_nan(stt);
+  float sint = nanv;
+  unsigned lastp1 = 0u, m = c.owner ? c.tmask : 0u, e_next = c.base;  // (owner: the events still to be applied, the next one's number)
+  unsigned rm = c.owner ? c.rmask : 0u;                                // ... and its ray events
+  unsigned lastu1 = 0u;                                                // (behind the cell's last OBSERVATION; lastp1 counts ray events too)
+  bool evt = false, st_dirty = false, strip_any = false, obst_dirty = false;
+  float obst = nanv;
+  uint32_t colv = 0x7FC00000u;
+  // raycasting state of the cell: visibility log-odds, the elevation the last event left, what the raycasting layer ends
+  // up with (the LAST running frame's minimum: map.clear(raycasting) + that frame's rays)
+  float lo = nanv, elev = nanv, ray_val = nanv;
+  bool lo_dirty = false, ghost_one = false;
+  const int k_last_run = c.runmask ? 31 - __clz(int(c.runmask)) : -1;
+  // NaN in every layer of the cell: a strip GridMap::move vacated, or ElevationMap::clearAt (elevation_map.hpp:131-135)
+  auto wipe = [&]() {
+    POLICY::set_nan(stt);
+    sint = nanv;
+    colv = 0x7FC00000u;
+    strip_any = true;
+    st_dirty = false;
+    obst = nanv; obst_dirty = true; lo = nanv; lo_dirty = false; ghost_one = false; elev = nanv; ray_val = nanv;
+  };
+  // resolveGhostCells (raycasting.cpp:175-202) for this cell and scan k: the scan's evidence, then its ghost decision
+  auto resolve = [&](const unsigned k) {
+    const uint32_t cnt = S.rcnt[k * kUpdCells + cl], hmin = S.rmin[k * kUpdCells + cl];
+    if (cnt) {  // observed evidence, once per ray-scan point in the cell (raycasting.cpp:156-163)
+      if (isnan(lo)) lo = 0.0f;
+      for (uint32_t q = 0; q < cnt; ++q) {
+        const float a = lo + ray.l_obs;
+        const float nx = (ray.l_max < a) ? ray.l_max : a;  // std::min(a, l_max)
+        if (nx == lo) break;  // fixed point reached: the remaining folds change nothing
+        lo = nx;
+      }
+      lo_dirty = true;
+    }
+    float rv = nanv;
+    if (hmin != kMRayEmpty) {
+      rv = unord(hmin);
+      if (!isnan(elev) && elev > rv + ray.conflict_thr) {
+        if (isnan(lo)) lo = 0.0f;
+        lo -= ray.l_ghost;
+        lo_dirty = true;
+        if (lo < ray.clear_thr) {  // clearAt: NaN in every layer, then the marker (no min ray height for the frame)
+          wipe();
+          ghost_one = true;
+          rv = nanv;
+        }
+      }
+    }
+    if (int(k) == k_last_run) ray_val = rv;
+  };
+  if (c.owner) {
+    if (c.tmask | c.rmask) {
+      stt = early.rec;
+      if (has_int) sint = early.sint;
+      elev = POLICY::elevation(stt);
+      if (c.rmask) lo = early.lo;
+    }
+  }
+#pragma unroll 1
+  for (unsigned r0 = 0; r0 < c.total; r0 += unsigned(kEvCap)) {  // one round for all but the densest corners
+    const unsigned r1 = min(r0 + unsigned(kEvCap), c.total);
+    mupd_exchange<POLICY, CH>(U, L, S, c, kk, ncell, r0, r1, []() {});
+    __syncthreads();
+    // the cells' own threads apply their events of this round, in scan order
+    while (m | rm) {
+      const unsigned k = unsigned(__ffs(int(m | rm))) - 1u, bit = 1u << k;
+      if ((m & bit) && e_next >= r1) break;  // (its observation arrives with the next round)
+      const unsigned upto = lowbits(k + 1u), from = lowbits(lastp1);  // scans lastp1 .. k
+      if (c.smask & upto & ~from) wipe();  // vacated since the last event: NaN in every layer (GridMap::move)
+      if (m & bit) {
+        m &= ~bit;
+        const MObs ob = S.ob[e_next - r0];
+        const uint32_t rgb = has_col ? S.rgb[e_next - r0] : 0u;
+        ++e_next;
+        POLICY::step(L, stt, ob.min_z, ob.var, ob.max_z);
+        obst = (ob.max_z > ob.min_z) ? ob.max_z : nanv;
+        obst_dirty = true;
+        if (has_int && (isnan(sint) || ob.iobs > sint)) sint = ob.iobs;
+        if (has_col) colv = rgb & 0x00FFFFFFu;
+        evt = true;
+        st_dirty = true;
+        elev = POLICY::elevation(stt);
+        lastu1 = k + 1u;
+      }
+      if (rm & bit) {  // scan k's raycasting stage, behind its observation
+        rm &= ~bit;
+        resolve(k);
+      }
+      lastp1 = k + 1u;
+    }
+    __syncthreads();  // (the next round reuses the lists)
+  }
+  while (rm) {  // ray events behind the block's last observation (or of a block without any)
+    const unsigned k = unsigned(__ffs(int(rm))) - 1u;
+    rm &= rm - 1u;
+    const unsigned upto = lowbits(k + 1u), from = lowbits(lastp1);
+    if (c.smask & upto & ~from) wipe();
+    resolve(k);
+    lastp1 = k + 1u;
+  }
+  FDM_PHASE(2);  // events applied
+  if (c.owner) {  // the scans after the cell's last event, then the stores
+    const unsigned all = lowbits(c.count), from = lowbits(lastp1);
+    if (c.smask & all & ~from) {
+      strip_any = true; st_dirty = false; sint = nanv; colv = 0x7FC00000u; obst = nanv; obst_dirty = true;
+      lo = nanv; lo_dirty = false; ghost_one = false; ray_val = nanv;
+    }
+    // map_.clear(obstacle) by every scan that observed a cell (elevation_mapping.cpp:144-146), behind the cell's last observation
+    if (c.umask & all & ~lowbits(lastu1)) { obst = nanv; obst_dirty = true; }
+    if (strip_any) {
+      mwipe_layers<float>(0, n_layers, o, [&](int l) { return all_layers[min(l, n_layers - 1)]; });
+      POLICY::clear_cell(L, o);
+    }
+    if (st_dirty) {
+      POLICY::finish(stt);
+      POLICY::store(L, o, stt);
+    }
+    if (obst_dirty) L.obstacle[o] = obst;
+    if (has_int && (evt || strip_any)) L.intensity[size_t(o) * L.istride] = sint;
+    if (has_col && (evt || strip_any)) reinterpret_cast<uint32_t*>(L.color)[o] = colv;
+    if (ray.stamp) {
+      if (lo_dirty) ray.logodds[o] = lo;
+      if (ghost_one) ray.ghost[o] = 1.0f;
+      if (c.runmask) ray.ray_min[o] = ray_val;  // every cell, every running frame: the layer is cleared first (raycasting.cpp:228)
+    }
+  }
+}
+
 template <typename POLICY, int CH, bool RAY>
 __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, DevState* __restrict__ st,
                                              const typename POLICY::Layers& L,
                                              float* const* __restrict__ all_layers, int n_layers,
                                              const unsigned ncell, const unsigned bid,
                                              MUpdLds<(CH & 2) != 0, RAY>& S) {
-  constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
-  const float nanv = __uint_as_float(0x7FC00000u);
   const unsigned lt = threadIdx.x, lane = lt & 63u, wave = lt >> 6;
   const unsigned count = U.count;
   const unsigned tpc = upd_threads_per_cell(count), cpb = 256u / tpc;   // threads per cell, cells per block (block-uniform)
@@ -865,12 +1278,17 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
     v_sr = ms->E[lane].sr; v_sc = ms->E[lane].sc;
     v_shr = ms->C[lane].shr; v_shc = ms->C[lane].shc;
     v_in = ms->inside[lane];
-    if (RAY && U.ray.stamp) v_run = U.ray.rs->any[lane] == U.ray.stamp && U.ray.rs->origin_in[lane] != 0u;
+    if constexpr (RAY) {
+      if (U.ray.stamp) v_run = U.ray.rs->any[lane] == U.ray.stamp && U.ray.rs->origin_in[lane] != 0u;
+    }
   }
   // raycasting: the thread's four (evidence count, min ray height) pairs join round trip 1 (the images of a scan whose
-  // stage did not run are clean: no events)
+  // stage did not run are clean: no events) ... and so does the cell's stored state: with raycasting nearly every cell has
+  // an event, and asking for the record only once the images are back would be one more dependent round trip
   uint32_t rc_[kScansPerThread], rh_[kScansPerThread];
-  if (RAY) {
+  MRayEarly<POLICY> early;
+  unsigned runmask = 0u;  // scans whose raycasting stage runs (raycasting.cpp:207-220)
+  if constexpr (RAY) {
 #pragma unroll
     for (int j = 0; j < kScansPerThread; ++j) {
       const unsigned k = cq * unsigned(kScansPerThread) + unsigned(j);
@@ -880,49 +1298,21 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
         rh_[j] = U.ray.rc_min[size_t(k) * ncell + o];
       }
     }
+    POLICY::set_nan(early.rec);
+    early.sint = early.lo = __uint_as_float(0x7FC00000u);
+    if (owner) {
+      POLICY::load(L, o, early.rec);
+      if ((CH & 1) != 0) early.sint = L.intensity[size_t(o) * L.istride];
+      if (U.ray.stamp) early.lo = U.ray.logodds[o];
+    }
+    runmask = uni(unsigned(__ballot(v_run)));
   }
-  // ... and so does the cell's stored state: with raycasting nearly every cell has an event, and asking for the record
-  // only once the images are back would be one more dependent round trip
-  typename POLICY::State rec_early;
-  POLICY::set_nan(rec_early);
-  float sint_early = nanv, lo_early = nanv;
-  if (RAY && owner) {
-    POLICY::load(L, o, rec_early);
-    if (has_int) sint_early = L.intensity[size_t(o) * L.istride];
-    if (U.ray.stamp) lo_early = U.ray.logodds[o];
-  }
-  const unsigned runmask = RAY ? uni(unsigned(__ballot(v_run))) : 0u;  // scans whose raycasting stage runs (raycasting.cpp:207-220)
   const unsigned passbits = uni(ms->flags[0]);
   const bool v_applied = lane < count && U.do_move && (!U.gate_on_filter || ((passbits >> lane) & 1u) != 0u);
   const unsigned umask = uni(unsigned(__ballot(lane < count && v_in != 0u)));                     // scans that observed a cell
-  unsigned stripmask = uni(unsigned(__ballot(v_applied && (v_shr != 0 || v_shc != 0))));         // scans whose move vacated cells
+  const unsigned stripmask = uni(unsigned(__ballot(v_applied && (v_shr != 0 || v_shc != 0))));   // scans whose move vacated cells
 
-  if (bid == 0 && lt == 0) {  // commit the geometry ring behind the batch (make_ctx does this per scan)
-    const unsigned last = count - 1u;
-    const unsigned slot_next = (U.scan_no0 + count) & 3u;
-    DevGeom g = ms->E[last];
-    const DevCand cl2 = ms->C[last];
-    const bool applied_last = U.do_move && (!U.gate_on_filter || ((passbits >> last) & 1u) != 0u);
-    if (applied_last) { g.px = cl2.px; g.py = cl2.py; g.sr = cl2.sr; g.sc = cl2.sc; }
-    const unsigned ob_prev = st->obst[U.scan_no0 & 3u].scan;
-    st->geom[slot_next] = g;
-    st->cand[(U.scan_no0 + last) & 3u] = cl2;   // (the synchronous statistics report the last scan's shift)
-    // the last scan of the batch that observed a cell (umask: one bit per scan)
-    st->obst[slot_next].scan = umask ? U.scan_no0 + (31u - unsigned(__clz(int(umask)))) : ob_prev;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { st->flags[q].any_pass = 0u; st->flags[q].any_inside = 0u; st->flags[q].ray_any = 0u; }
-    if (umask) {
-      const unsigned first_upd = U.scan_no0 + unsigned(__ffs(int(umask))) - 1u;
-      if (has_int && st->vis_int == 0u) st->vis_int = 3u * first_upd + 2u;
-      if (has_col && st->vis_col == 0u) st->vis_col = 3u * first_upd + 2u;
-    }
-    if (RAY && runmask && st->vis_ray == 0u)  // the three layers become visible with the first frame that runs (raycasting.cpp:223-226)
-      st->vis_ray = 3u * (U.scan_no0 + unsigned(__ffs(int(runmask))) - 1u) + 3u;
-  }
-  if (bid == 0 && lt >= 64u && lt < 64u + unsigned(kMaxBatch)) {  // re-arm the state of the batch after next
-    U.rearm->inside[lt - 64u] = 0u;
-    if (lt == 64u) { U.rearm->flags[0] = 0u; U.rearm->flags[1] = 0u; U.rearm->flags[2] = 0u; }
-  }
+  mupd_commit<CH, RAY>(U, st, bid, passbits, umask, runmask);
 
   unsigned nib = 0u;
 #pragma unroll
@@ -933,7 +1323,7 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
   if constexpr (!RAY) {
     if (wave == 1u) S.lay[lane] = lay_p;  // (all kLayTab entries: null beyond n_layers, read but never stored through)
   }
-  if (RAY) {
+  if constexpr (RAY) {
     unsigned rb = 0u;
 #pragma unroll
     for (int j = 0; j < kScansPerThread; ++j) {
@@ -950,18 +1340,7 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
   }
   // which scans' moves vacated THIS cell (asked by the owners only)
   unsigned smask = 0u;
-  if (stripmask && cq == 0u) {
-    const int r = int(o % unsigned(G.s_rows)) + G.s_r0;
-    const int col = int(o / unsigned(G.s_rows)) + G.s_c0;
-    while (stripmask) {
-      const unsigned k = unsigned(__ffs(int(stripmask))) - 1u;
-      stripmask &= stripmask - 1u;
-      const int sr = __builtin_amdgcn_readlane(v_sr, int(k)), sc = __builtin_amdgcn_readlane(v_sc, int(k));
-      const int shr = __builtin_amdgcn_readlane(v_shr, int(k)), shc = __builtin_amdgcn_readlane(v_shc, int(k));
-      if (in_cleared_strip(r, sr, shr, G.rows) || in_cleared_strip(col, sc, shc, G.cols)) smask |= 1u << k;
-    }
-    if (!valid) smask = 0u;
-  }
+  if (stripmask && cq == 0u) smask = mupd_vacated(stripmask, G, o, valid, v_sr, v_sc, v_shr, v_shc);
 
   __syncthreads();
   unsigned tmask = 0u, rmask = 0u;  // the cell's scans | its ray events: scans whose stage left evidence or a ray height in it
@@ -971,326 +1350,16 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
 #pragma unroll
     for (unsigned g = 4; g < 8u; ++g) tmask |= S.mk.tpart[g * cpb + cl];
   }
-  if (RAY && cq == 0u) {
-    for (unsigned g = 0; g < tpc; ++g) rmask |= S.mk.rpart[g * cpb + cl];
+  if constexpr (RAY) {
+    if (cq == 0u)
+      for (unsigned g = 0; g < tpc; ++g) rmask |= S.mk.rpart[g * cpb + cl];
   }
+  unsigned total;
+  const unsigned base = mupd_number(tmask, tpc, cpb, cl, cq, total);
 
-  // ---- the block's (cell, scan) events, numbered cell-major / scan-minor: a cell's events stay one run, in scan
-  // order.  Lane c < cpb of EVERY wavefront holds cell c's mask, so each wavefront sums the cells in front for itself ----
-  const unsigned mine = lane < cpb ? unsigned(__popc(tmask)) : 0u;
-  unsigned inc = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned v = __shfl_up(inc, d);
-    if (int(lane) >= d) inc += v;
-  }
-  const unsigned total = unsigned(__builtin_amdgcn_readlane(int(inc), 63));
-  unsigned base = inc - mine;                                     // the events of the cells in front of this one,
-  if (tpc == 8u) base = unsigned(__shfl(int(base), int(cl)));     // (lanes 32-63: a second group of the same 32 cells)
-  base += unsigned(__popc(tmask & lowbits(unsigned(kScansPerThread) * cq)));  // the cell's own in earlier groups
-
-  typename POLICY::State stt;
-  POLICY::set_nan(stt);
-  float sint = nanv;
-  unsigned lastp1 = 0u, m = owner ? tmask : 0u, e_next = base;  // (owner: the events still to be applied, the next one's number)
-  unsigned rm = (RAY && owner) ? rmask : 0u;                        // ... and its ray events
-  unsigned lastu1 = 0u;                                             // (RAY: behind the cell's last OBSERVATION; lastp1 counts ray events too)
-  bool evt = false, st_dirty = false, strip_any = false, obst_dirty = false;
-  float obst = nanv;
-  uint32_t colv = 0x7FC00000u;
-  // raycasting state of the cell: visibility log-odds, the elevation the last event left, what the raycasting layer ends
-  // up with (the LAST running frame's minimum: map.clear(raycasting) + that frame's rays)
-  float lo = nanv, elev = nanv, ray_val = nanv;
-  bool lo_dirty = false, ghost_one = false;
-  const int k_last_run = runmask ? 31 - __clz(int(runmask)) : -1;
-  // NaN in every layer of the cell: a strip GridMap::move vacated, or ElevationMap::clearAt (elevation_map.hpp:131-135)
-  auto wipe = [&]() {
-    POLICY::set_nan(stt);
-    sint = nanv;
-    colv = 0x7FC00000u;
-    strip_any = true;
-    st_dirty = false;
-    if (RAY) { obst = nanv; obst_dirty = true; lo = nanv; lo_dirty = false; ghost_one = false; elev = nanv; ray_val = nanv; }
-  };
-  // resolveGhostCells (raycasting.cpp:175-202) for this cell and scan k: the scan's evidence, then its ghost decision
-  auto resolve = [&](const unsigned k) {
-    const uint32_t cnt = S.rcnt[k * kUpdCells + cl], hmin = S.rmin[k * kUpdCells + cl];
-    if (cnt) {  // observed evidence, once per ray-scan point in the cell (raycasting.cpp:156-163)
-      if (isnan(lo)) lo = 0.0f;
-      for (uint32_t q = 0; q < cnt; ++q) {
-        const float a = lo + U.ray.l_obs;
-        const float nx = (U.ray.l_max < a) ? U.ray.l_max : a;  // std::min(a, l_max)
-        if (nx == lo) break;  // fixed point reached: the remaining folds change nothing
-        lo = nx;
-      }
-      lo_dirty = true;
-    }
-    float ray = nanv;
-    if (hmin != kMRayEmpty) {
-      ray = unord(hmin);
-      if (!isnan(elev) && elev > ray + U.ray.conflict_thr) {
-        if (isnan(lo)) lo = 0.0f;
-        lo -= U.ray.l_ghost;
-        lo_dirty = true;
-        if (lo < U.ray.clear_thr) {  // clearAt: NaN in every layer, then the marker (no min ray height for the frame)
-          wipe();
-          ghost_one = true;
-          ray = nanv;
-        }
-      }
-    }
-    if (int(k) == k_last_run) ray_val = ray;
-  };
-  // Without the ray stage the owners' walk is the launch's longest dependent chain — ONE wavefront issuing in order, as
-  // long as (events of the block's busiest cell) x (instructions per event) — so everything an event does not change is
-  // decided here, once.  An owner knows its cell's scans (tmask) and the scans whose move vacated it (smask): the cell is
-  // wiped in front of its event of ordinal i exactly when some vacating scan s has that event as the first one at or
-  // after s (scan s moves the map BEFORE it observes: an event of scan s itself counts) — bit 31 - i of `wrev`, tested
-  // by sign and shifted out per event; a vacating scan behind the last event wipes in the tail (wipe_tail).  The flags
-  // the old loop carried as lane masks follow: an event happened / the record and the obstacle cell are dirty <=> tmask
-  // != 0 (a wipe inside the walk is always followed by an event), some strip wiped the cell <=> wrev != 0 || wipe_tail.
-  unsigned wrev = 0u, left = 0u;   // left: the owner's events still to be applied
-  const typename POLICY::WalkRegs wregs = POLICY::walk_regs(L);
-  bool wipe_tail = false, strip_walk = false;
-  float zlo = 0.0f, zhi = 0.0f;    // min_z / max_z of the cell's last observation (the obstacle layer reads only that one)
-  if constexpr (!RAY) {
-    if (owner) {
-      left = unsigned(__popc(tmask));
-      unsigned wbefore = 0u;
-      for (unsigned sm = smask; sm; sm &= sm - 1u) {
-        const unsigned s = unsigned(__ffs(int(sm))) - 1u;       // (< count <= 32)
-        const unsigned at = tmask & ~((1u << s) - 1u);           // the cell's events of scans >= s
-        if (at) wbefore |= 1u << unsigned(__popc(tmask & ((1u << (unsigned(__ffs(int(at))) - 1u)) - 1u)));
-        else wipe_tail = true;
-      }
-      wrev = __brev(wbefore);
-      strip_walk = wbefore != 0u;
-    }
-  }
-  if (RAY && owner) {  // (rays cross most cells of the map: the cell's state was fetched with round trip 1, see rec_early)
-    if (tmask | rmask) {
-      stt = rec_early;
-      if (has_int) sint = sint_early;
-      elev = POLICY::elevation(stt);
-      if (rmask) lo = lo_early;
-    }
-  }
-#pragma unroll 1
-  for (unsigned r0 = 0; r0 < total; r0 += unsigned(kEvCap)) {  // one round for all but the densest corners
-    const unsigned r1 = min(r0 + unsigned(kEvCap), total);
-    {  // every thread lists its (at most four) events of this round
-      unsigned e = base;
-#pragma unroll
-      for (int j = 0; j < kScansPerThread; ++j) {
-        if ((nib >> j) & 1u) {
-          if (e >= r0 && e < r1) {
-            MEvent ev;
-            ev.idx = uint32_t(kk[j]);
-            ev.cell = uint16_t(cl);
-            ev.k = uint16_t(cq * unsigned(kScansPerThread) + unsigned(j));
-            S.ev[e - r0] = ev;
-          }
-          ++e;
-        }
-      }
-    }
-    __syncthreads();
-    // round trip 2: every event of the round, spread evenly over the block (kEvCap / 256 per thread), and the
-    // cells' stored state
-    constexpr int kPer = kEvCap / 256;
-    MEvent ev_[kPer];
-    float2 ob_[kPer];
-    uint4 ax_[kPer];
-    uint2 zs_[kPer];
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) {
-      const unsigned j = lt + unsigned(q) * 256u;
-      ob_[q] = make_float2(kFltMax, 0.0f);  // (no finite z: FLT_MAX, variance 0 — elevation_mapping.hpp:26-34)
-      ax_[q] = make_uint4(0u, 0u, kNoIdx, 0u);
-      zs_[q] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-      ev_[q].idx = kNoIdx; ev_[q].cell = 0; ev_[q].k = 0;
-      if (r0 + j < r1) {
-        ev_[q] = S.ev[j];
-        const size_t oc = size_t(ev_[q].k) * ncell + (bid * cpb + ev_[q].cell);
-        if (ev_[q].idx != kNoIdx) ob_[q] = U.obs[size_t(ev_[q].k) * U.obs_stride + ev_[q].idx];
-        ax_[q] = U.aux[oc];
-        zs_[q] = U.zs[oc];
-      }
-    }
-    if (!RAY && r0 == 0u && owner && tmask) {  // (the record joins the same round trip)
-      POLICY::load(L, o, stt);
-      if (has_int) sint = L.intensity[size_t(o) * L.istride];
-    }
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) {
-      const unsigned j = lt + unsigned(q) * 256u;
-      if (r0 + j >= r1) continue;
-      if (has_col) S.rgb[j] = U.cobs[size_t(ev_[q].k) * U.obs_stride + ax_[q].w];  // (one more dependent gather)
-      const uint32_t zm = ax_[q].x, imx = ax_[q].y, fst = ax_[q].z;
-      MObs ob;
-      ob.min_z = ob_[q].x;
-      ob.var = POLICY::obs_var(L, ob_[q].y);  // (Kalman: R, substituted here by 256 threads and not in the owners' walk)
-      // (a zero maximum takes the sign of the first zero-valued point, see Scratch::zs)
-      ob.max_z = zm ? ((zm == 0x80000000u && (zs_[q].x & 1u)) ? -0.0f : unord(zm)) : -kFltMax;
-      ob.iobs = 0.0f;
-      if (has_int) ob.iobs = (fst & 1u) ? nanv : ((imx == 0x80000000u && (zs_[q].y & 1u)) ? -0.0f : unord(imx));
-      S.ob[j] = ob;
-      FDM_PHASE(1);  // round trip 2 (observations, record) back
-      const size_t oc = size_t(ev_[q].k) * ncell + (bid * cpb + ev_[q].cell);
-      U.key[oc] = kEmptyKey;  // the scratch is clean again for the batch after next
-      U.aux[oc] = make_uint4(0u, 0u, kNoIdx, 0u);
-      if ((zs_[q].x & zs_[q].y) != 0xFFFFFFFFu) U.zs[oc] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-    }
-    __syncthreads();
-    // the cells' own threads apply their events of this round, in scan order
-    if constexpr (!RAY) {
-      // The owner's events of this round are one run of the list, known before the round: counted down, the
-      // observation of event i + 1 read from LDS before the arithmetic of event i.  No scan number in the loop (the
-      // wipes go by event ordinal, see wrev); the obstacle value and the colour are the last event's, taken behind it.
-      unsigned n = (left != 0u && e_next < r1) ? min(left, r1 - e_next) : 0u;  // (left != 0: e_next >= r0)
-      if (n) {
-        const MObs* p = &S.ob[e_next - r0];
-        e_next += n;
-        left -= n;
-        auto apply = [&](const MObs& ob) {
-          const bool fresh = int(wrev) < 0;  // vacated since the last event: NaN in every layer (GridMap::move)
-          wrev <<= 1;
-          POLICY::walk_step(L, wregs, stt, ob.min_z, ob.var, ob.max_z, fresh);
-          if (has_int) {  // isnan(sint) || iobs > sint, two-sided (iobs can be NaN: a NaN intensity as the cell's first point)
-            const float hi = (ob.iobs > sint) ? ob.iobs : sint;
-            const float hn = isnan(sint) ? ob.iobs : hi;
-            sint = fresh ? ob.iobs : hn;
-          }
-        };
-        MObs nx = *p;
-        while (--n) {
-          const MObs ob = nx;
-          nx = *++p;
-          __builtin_amdgcn_sched_barrier(0);  // (the read stays in front of the arithmetic: its latency is the loop's otherwise)
-          apply(ob);
-        }
-        apply(nx);
-        zlo = nx.min_z; zhi = nx.max_z;
-        if (has_col) colv = S.rgb[p - S.ob] & 0x00FFFFFFu;  // (a later round's last event overwrites it)
-      }
-    } else {
-      while (m | rm) {
-        const unsigned k = unsigned(__ffs(int(m | rm))) - 1u, bit = 1u << k;
-        if ((m & bit) && e_next >= r1) break;  // (its observation arrives with the next round)
-        const unsigned upto = lowbits(k + 1u), from = lowbits(lastp1);  // scans lastp1 .. k
-        if (smask & upto & ~from) wipe();  // vacated since the last event: NaN in every layer (GridMap::move)
-        if (m & bit) {
-          m &= ~bit;
-          const MObs ob = S.ob[e_next - r0];
-          const uint32_t rgb = has_col ? S.rgb[e_next - r0] : 0u;
-          ++e_next;
-          POLICY::step(L, stt, ob.min_z, ob.var, ob.max_z);
-          obst = (ob.max_z > ob.min_z) ? ob.max_z : nanv;
-          obst_dirty = true;
-          if (has_int && (isnan(sint) || ob.iobs > sint)) sint = ob.iobs;
-          if (has_col) colv = rgb & 0x00FFFFFFu;
-          evt = true;
-          st_dirty = true;
-          if (RAY) { elev = POLICY::elevation(stt); lastu1 = k + 1u; }
-        }
-        if (RAY && (rm & bit)) {  // scan k's raycasting stage, behind its observation
-          rm &= ~bit;
-          resolve(k);
-        }
-        lastp1 = k + 1u;
-      }
-    }
-    __syncthreads();  // (the next round reuses the lists)
-  }
-  if (RAY) {  // ray events behind the block's last observation (or of a block without any)
-    while (rm) {
-      const unsigned k = unsigned(__ffs(int(rm))) - 1u;
-      rm &= rm - 1u;
-      const unsigned upto = lowbits(k + 1u), from = lowbits(lastp1);
-      if (smask & upto & ~from) wipe();
-      resolve(k);
-      lastp1 = k + 1u;
-    }
-  }
-  FDM_PHASE(2);  // events applied
-  if constexpr (!RAY) {
-    // The tail behind the walk, still on the launch's longest chain: every value the owner stores is computed first —
-    // the sample variance and the bounds included — then the stores leave back to back, in the order they always had
-    // (all-layer NaN, the record's NaN, record, obstacle, intensity, colour: a lane's stores to one address stay in
-    // program order, which is all the order there is to keep), with no load from global memory and no wait between them.
-    if (owner) {
-      const bool any_evt = tmask != 0u;
-      const unsigned last1 = 32u - unsigned(__clz(int(tmask)));  // the last event's scan + 1 (no event: 0)
-      const bool strips = strip_walk || wipe_tail;
-      // map_.clear(obstacle) by every scan that observed a cell (elevation_mapping.cpp:144-146), behind the cell's last observation
-      const bool obst_clear = wipe_tail || (umask & lowbits(count) & ~lowbits(last1)) != 0u;
-      const float obst_v = (any_evt && !obst_clear && zhi > zlo) ? zhi : nanv;
-      if (wipe_tail) { sint = nanv; colv = 0x7FC00000u; }  // vacated behind the last event: the wipe is all that is stored
-      POLICY::finish(stt);  // (no event: of a NaN state, not stored)
-      POLICY::settle(stt);
-      using gfloat = __attribute__((address_space(1))) float;  // (layers are global memory: no flat store)
-      if (strips) {
-        const int n_tab = min(n_layers, kLayTab);
-        static_assert(kLayTab % 8 == 0, "the wipe reads the table in groups of eight");
-        for (int l0 = 0; l0 < n_tab; l0 += 8) {
-          float* p[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) p[q] = S.lay[l0 + q];
-#pragma unroll
-          for (int q = 0; q < 8; ++q)
-            if (l0 + q < n_tab) ((gfloat*)p[q])[o] = nanv;
-        }
-        for (int l0 = kLayTab; l0 < n_layers; l0 += 8) {  // (more layers than the table holds: their pointers from memory)
-          float* p[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) p[q] = all_layers[min(l0 + q, n_layers - 1)];
-#pragma unroll
-          for (int q = 0; q < 8; ++q)
-            if (l0 + q < n_layers) ((gfloat*)p[q])[o] = nanv;
-        }
-        POLICY::clear_cell(L, o);
-      }
-      if (any_evt && !wipe_tail) POLICY::store(L, o, stt);
-      if (any_evt || obst_clear) L.obstacle[o] = obst_v;
-      if (has_int && (any_evt || strips)) L.intensity[size_t(o) * L.istride] = sint;
-      if (has_col && (any_evt || strips)) reinterpret_cast<uint32_t*>(L.color)[o] = colv;
-    }
-  }
-  // (RAY: the tail as it was — its instantiations have no register to spare) the scans after the cell's last event
-  if (RAY && owner) {
-    const unsigned all = lowbits(count), from = lowbits(lastp1);
-    const unsigned tail = all & ~from;
-    if (smask & tail) {
-      strip_any = true; st_dirty = false; sint = nanv; colv = 0x7FC00000u; obst = nanv; obst_dirty = true;
-      if (RAY) { lo = nanv; lo_dirty = false; ghost_one = false; ray_val = nanv; }
-    }
-    // map_.clear(obstacle) by every scan that observed a cell (elevation_mapping.cpp:144-146), behind the cell's last observation
-    const unsigned tail_u = RAY ? (all & ~lowbits(lastu1)) : tail;
-    if (umask & tail_u) { obst = nanv; obst_dirty = true; }
-    if (strip_any) {
-      for (int l0 = 0; l0 < n_layers; l0 += 8) {
-        float* p[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) p[q] = all_layers[min(l0 + q, n_layers - 1)];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-          if (l0 + q < n_layers) p[q][o] = nanv;
-      }
-      POLICY::clear_cell(L, o);
-    }
-    if (st_dirty) {
-      POLICY::finish(stt);
-      POLICY::store(L, o, stt);
-    }
-    if (obst_dirty) L.obstacle[o] = obst;
-    if (has_int && (evt || strip_any)) L.intensity[size_t(o) * L.istride] = sint;
-    if (has_col && (evt || strip_any)) reinterpret_cast<uint32_t*>(L.color)[o] = colv;
-    if (RAY && U.ray.stamp) {
-      if (lo_dirty) U.ray.logodds[o] = lo;
-      if (ghost_one) U.ray.ghost[o] = 1.0f;
-      if (runmask) U.ray.ray_min[o] = ray_val;  // every cell, every running frame: the layer is cleared first (raycasting.cpp:228)
-    }
-  }
+  const MCell c{bid, cpb, o, cl, cq, count, owner, nib, base, total, tmask, smask, umask, rmask, runmask};
+  if constexpr (RAY) mupd_walk_ray<POLICY, CH>(U, L, S, c, kk, ncell, all_layers, n_layers, early);
+  else mupd_walk_plain<POLICY, CH>(U, L, S, c, kk, ncell, all_layers, n_layers);
   // touched-cell count of the batch's last scan (what the synchronous statistics report), per update block
   const unsigned long long mt = __ballot(owner && ((tmask >> (count - 1u)) & 1u) != 0u);
   if (lane == 0u) S.s_t[wave] = unsigned(__popcll(mt));

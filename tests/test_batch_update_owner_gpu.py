@@ -180,3 +180,38 @@ def test_ray_events_with_and_without_observations(gpu, R, batch_max):
         poses.append(T(px, py, 0.0, yaw=0.1 * k))
     cleared = batch_vs_oracle(gpu, eng, ref, scans, T(z=1.5), poses)
     assert cleared > 0
+
+
+@pytest.mark.parametrize("extra", [3, 60])
+@pytest.mark.parametrize("batch_max", [16, 32])
+def test_ray_wipe_of_every_layer(gpu, R, batch_max, extra):
+    """raycast_enabled with plain layers added before the first scan: the owners' all-layer wipe (a vacated strip, or a
+    ghost cell's clearAt) fetches its pointers in groups of eight, the last group clamped to the last layer — with 3 added
+    layers the layer count is no multiple of eight, with 60 it is beyond 64.  12 x 9 = 108 cells: the last update block
+    is partial at 64 and at 32 cells per block.  One-cell LOCAL shifts in front of some scans, the batch's last one
+    among them.  Every layer, the added ones included, against the oracle."""
+    eng, ref = pair(gpu, R, 1.2, 0.9, 0.1, ray_on(_open, rc_log_odds_ghost=0.9, rc_clear_threshold=-0.5,
+                                                   rc_height_conflict_threshold=0.02))
+    assert eng.geometry().rows * eng.geometry().cols == 108
+    eng.set_option("batch_max", batch_max)
+    for o in (eng, ref):
+        for i in range(extra):
+            o.add("extra_%02d" % i, 1.0 + i)
+    rng = np.random.default_rng(300 + batch_max + extra)
+    scans, poses = [], []
+    px = 0.0
+    for k in range(32):
+        n = int(rng.integers(100, 301))
+        s = cloud(rng, n, 0.7, intensity=True)
+        s["x"] = np.abs(s["x"])  # points and rays ahead of the robot only: the cells behind it keep what they hold
+        s["z"] = (s["z"] + F32(0.6) * (rng.uniform(size=n) < 0.3)).astype(F32)  # bumps that later rays pass through
+        scans.append(s)
+        # the first scan goes alone (it creates the estimator's layers), then launches of batch_max: a shift in front
+        # of scans 5 and 11, and of the last scan of every launch (16, 31 | 31)
+        if k in (5, 11, 16, 31):
+            px += 0.1
+        poses.append(T(px, 0.0, 0.0))
+    cleared = batch_vs_oracle(gpu, eng, ref, scans, T(z=1.5), poses)
+    assert cleared > 0
+    last = eng.layer("extra_%02d" % (extra - 1))
+    assert np.isnan(last).any() and (last == F32(extra)).any()
