@@ -365,6 +365,7 @@ struct fdm_engine {
   size_t region_cap = 0;
   float* d_post_pool = nullptr;      // per-thread lists of the big-neighbourhood stencil kernels
   size_t post_pool_cap = 0;          // in floats
+  const char* last_post_kernel = ""; // kernel of the last stencil-stage call, as its launch site spells it ("": none was launched)
   FeatEntry* d_feat_tab = nullptr;   // kMaxRegion entries: the region as k_features_tiled reads it
   std::vector<RegionEntry> h_region; // what d_region holds (upload_region skips an identical table)
   std::vector<FeatEntry> h_feat_tab; // what d_feat_tab holds

@@ -68,11 +68,15 @@ int ensure_tmp2(fdm_engine* e) {
   if (!e->d_tmp2) HIPCK(hipMalloc(reinterpret_cast<void**>(&e->d_tmp2), e->ncell * sizeof(float)));
   return FDM_OK;
 }
+// Every launch site of the four stages names its kernel through this macro: the engine keeps the name, spelled as here,
+// for fdm_engine_debug_last_post_kernel (fdm_engine_debug.h) — the tests assert which branch of the dispatch a call took.
+#define FDM_POST_KERNEL(...) (e->last_post_kernel = #__VA_ARGS__, (__VA_ARGS__))
 }  // namespace
 
 int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid, int inplace) {
   if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
+  e->last_post_kernel = "";  // (a call that returns before it launches leaves the empty name)
   HIPCK(hipSetDevice(e->device));
   int rc;
   if ((rc = check_halo(e, max_iterations > 0 ? max_iterations : 0))) return rc;  // one cell per pass
@@ -100,11 +104,11 @@ int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid
   bool in_layer = start_in_layer;
   for (int it = 0; it < iters; ++it) {
     if (e->opt.dbg_post & 4)
-      hipLaunchKernelGGL(k_inpaint_pass, dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
+      hipLaunchKernelGGL(FDM_POST_KERNEL(k_inpaint_pass), dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
                          in_layer ? A : B, in_layer ? As : 1, in_layer ? B : A, in_layer ? 1 : As, min_valid,
                          unsigned(e->ncell));
     else
-      hipLaunchKernelGGL(k_inpaint_pass_tiled, dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
+      hipLaunchKernelGGL(FDM_POST_KERNEL(k_inpaint_pass_tiled), dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
                          in_layer ? A : B, in_layer ? As : 1, in_layer ? B : A, in_layer ? 1 : As, min_valid);
     in_layer = !in_layer;
   }
@@ -115,6 +119,7 @@ int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid
 int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int kernel_size, int min_valid) {
   if (int rc = join_streams(e)) return rc;
   if (!e || !layer) return fail(FDM_ERR_INVALID, "null argument");
+  e->last_post_kernel = "";  // (a call that returns before it launches leaves the empty name)
   // (any kernel size the reference accepts: region(Size(k, k)) spans dr, dc in [-k/2, k/2] — for an even k that is the
   // (k + 1)-wide box; a window beyond kMaxRegion cells takes the pooled kernel)
   if (kernel_size < 1 || kernel_size > 4096) return fail(FDM_ERR_INVALID, "kernel_size must be in [1, 4096]");
@@ -127,26 +132,26 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
   if ((rc = ensure_tmp(e))) return rc;
   if ((rc = copy_strided(e, e->d_tmp, 1, lptr(e, *l), lstride(e, *l)))) return rc;  // the double buffer
   if (kernel_size == 3 && !(e->opt.dbg_post & 4))
-    hipLaunchKernelGGL(k_median3_tiled, dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_median3_tiled), dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), min_valid);
   else if (kernel_size == 3)
-    hipLaunchKernelGGL(k_median3, dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_median3), dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), min_valid, unsigned(e->ncell));
   else if ((2 * (kernel_size / 2) + 1) * (2 * (kernel_size / 2) + 1) <= kMaxRegion)
-    hipLaunchKernelGGL(k_median, dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_median), dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), kernel_size, min_valid,
                        unsigned(e->ncell));
   else if (median_sel_lds_bytes(kernel_size) <= 160u * 1024u && !(e->opt.dbg_post & 8)) {
     // selection by bisection on an LDS tile (fdm_post.hpp k_median_sel): every window up to ~175 x 175
     const unsigned lds = median_sel_lds_bytes(kernel_size);
     if ((rc = allow_lds(k_median_sel, lds))) return rc;
-    hipLaunchKernelGGL(k_median_sel, dim3(tile3_blocks(e)), dim3(256), lds, e->stream, e->G, e->d_state, int(e->scan_no & 3),
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_median_sel), dim3(tile3_blocks(e)), dim3(256), lds, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                        e->d_tmp, lptr(e, *l), lstride(e, *l), kernel_size, min_valid);
   } else {
     const size_t side = size_t(2 * (kernel_size / 2) + 1);
     unsigned blocks = 0;
     if ((rc = ensure_pool(e, side * side, 256u, &blocks, side * side))) return rc;
-    hipLaunchKernelGGL(k_median_big, dim3(blocks), dim3(256), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_median_big), dim3(blocks), dim3(256), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                        e->d_tmp, lptr(e, *l), lstride(e, *l), kernel_size, min_valid, unsigned(e->ncell), e->d_post_pool);
   }
   HIPCK(hipGetLastError());
@@ -157,6 +162,7 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
 int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* cfg) {
   if (int rc = join_streams(e)) return rc;
   if (!e || !cfg) return fail(FDM_ERR_INVALID, "null argument");
+  e->last_post_kernel = "";  // (a call that returns before it launches leaves the empty name)
   if (!cfg->enabled) return FDM_OK;
   HIPCK(hipSetDevice(e->device));
   int rc;
@@ -205,22 +211,22 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
     // one instantiation per disc size there is below 30 cells (the sorting network shrinks with it: 171 exchanges for 29
     // samples, 19 for the 9 of the shipped 0.15 m on a 0.1 m map); dbg_post 128: the 29-slot kernel with branches
     const size_t nreg = (e->opt.dbg_post & 128) ? 0 : reg.size();
-    if (nreg == 29) launch_f64(k_fusion_f64_tiled<29, true>);
-    else if (nreg == 25) launch_f64(k_fusion_f64_tiled<25, true>);
-    else if (nreg == 21) launch_f64(k_fusion_f64_tiled<21, true>);
-    else if (nreg == 13) launch_f64(k_fusion_f64_tiled<13, true>);
-    else if (nreg == 9) launch_f64(k_fusion_f64_tiled<9, true>);
-    else if (nreg == 5) launch_f64(k_fusion_f64_tiled<5, true>);
-    else launch_f64(k_fusion_f64_tiled<29, false>);
+    if (nreg == 29) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<29, true>));
+    else if (nreg == 25) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<25, true>));
+    else if (nreg == 21) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<21, true>));
+    else if (nreg == 13) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<13, true>));
+    else if (nreg == 9) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<9, true>));
+    else if (nreg == 5) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<5, true>));
+    else launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<29, false>));
   } else if (reg.size() <= 32 && halo <= kFusHaloMax && !(e->opt.dbg_ray & 1024) && !(e->opt.dbg_post & 2)) {
     // samples as 64-bit integers sorted in registers, neighbourhood staged in LDS (round 2; any quantile)
     const unsigned tblocks = unsigned((e->G.s_rows + kFusTileR - 1) / kFusTileR) *
                              unsigned((e->G.s_cols + kFusTileC - 1) / kFusTileC);
-    hipLaunchKernelGGL(k_fusion_net32_tiled, dim3(tblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_net32_tiled), dim3(tblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, halo, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo));
   } else if (reg.size() <= 32 && !(e->opt.dbg_ray & 1024)) {  // the same from L2
-    hipLaunchKernelGGL(k_fusion_net32, dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_net32), dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
   } else if (int(reg.size()) <= kFusionWaveMax && !(e->opt.dbg_post & 16)) {  // one wavefront per cell, the samples sorted in LDS
@@ -229,7 +235,7 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
     const unsigned lds = fusion_wave_lds_bytes(n_pad);
     if ((rc = allow_lds(k_fusion_wave, lds))) return rc;
     const unsigned wblocks = unsigned(std::min<size_t>((e->ncell + 1) / 2, 8192));
-    hipLaunchKernelGGL(k_fusion_wave, dim3(wblocks), dim3(kFusionWaveThreads), lds, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_wave), dim3(wblocks), dim3(kFusionWaveThreads), lds, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, n_pad, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
   } else if (int(reg.size()) <= kFusionLdsEntries) {  // sample lists in LDS
@@ -241,17 +247,17 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
                                 int(size_t(4) * kFusionLdsEntries * kFusionThreads * sizeof(float))));
       raised = true;
     }
-    hipLaunchKernelGGL(k_fusion<true>, dim3(fblocks), dim3(kFusionThreads), lds, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion<true>), dim3(fblocks), dim3(kFusionThreads), lds, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
   } else if (reg.size() <= size_t(kMaxRegion)) {
-    hipLaunchKernelGGL(k_fusion<false>, dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion<false>), dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
   } else {  // any radius the reference accepts (config/postprocess.hpp:35)
     unsigned blocks = 0;
     if ((rc = ensure_pool(e, 4 * reg.size(), unsigned(kFusionThreads), &blocks, reg.size()))) return rc;
-    hipLaunchKernelGGL(k_fusion_big, dim3(blocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_big), dim3(blocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell), e->d_post_pool);
   }
@@ -262,6 +268,7 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
 int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_valid, float lo_pct, float hi_pct) {
   if (int rc = join_streams(e)) return rc;
   if (!e) return fail(FDM_ERR_INVALID, "null engine");
+  e->last_post_kernel = "";  // (a call that returns before it launches leaves the empty name)
   HIPCK(hipSetDevice(e->device));
   int rc;
   if ((rc = check_halo(e, int(std::floor(radius / static_cast<float>(e->G.res) + 1e-4f))))) return rc;
@@ -344,32 +351,37 @@ int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_val
                          e->d_feat_tab, F, halo, elev_p, elev_s, O);
     };
     if (e->opt.dbg_post & 64) {  // (measurement: the two-instruction insertion chains of round 2)
-      if (need_lo <= 8 && need_hi <= 8) launch_tiled(k_features_tiled<8, 8, false>);
-      else launch_tiled(k_features_tiled<16, 16, false>);
-    } else if (need_lo <= 2 && need_hi <= 3) launch_tiled(k_features_tiled<2, 3>);  // the defaults on a 29-cell disc (0.3 m on a 0.1 m map)
-    else if (need_lo <= 4 && need_hi <= 4) launch_tiled(k_features_tiled<4, 4>);
-    else if (need_lo <= 6 && need_hi <= 7) launch_tiled(k_features_tiled<6, 7>);  // the defaults on a 113-cell disc: 6 from the bottom, 7 from the top
-    else if (need_lo <= 8 && need_hi <= 8) launch_tiled(k_features_tiled<8>);
-    else launch_tiled(k_features_tiled<16>);
-  } else if (pct_ok && need_lo <= 8 && need_hi <= 8) launch_feat(k_features<8>);
-  else if (pct_ok && need_lo <= 16 && need_hi <= 16) launch_feat(k_features<16>);
-  else if (reg.size() <= size_t(kMaxRegion) && (e->opt.dbg_post & 8)) launch_feat(k_features<0>);
+      if (need_lo <= 8 && need_hi <= 8) launch_tiled(FDM_POST_KERNEL(k_features_tiled<8, 8, false>));
+      else launch_tiled(FDM_POST_KERNEL(k_features_tiled<16, 16, false>));
+    } else if (need_lo <= 2 && need_hi <= 3) launch_tiled(FDM_POST_KERNEL(k_features_tiled<2, 3>));  // the defaults on a 29-cell disc (0.3 m on a 0.1 m map)
+    else if (need_lo <= 4 && need_hi <= 4) launch_tiled(FDM_POST_KERNEL(k_features_tiled<4, 4>));
+    else if (need_lo <= 6 && need_hi <= 7) launch_tiled(FDM_POST_KERNEL(k_features_tiled<6, 7>));  // the defaults on a 113-cell disc: 6 from the bottom, 7 from the top
+    else if (need_lo <= 8 && need_hi <= 8) launch_tiled(FDM_POST_KERNEL(k_features_tiled<8>));
+    else launch_tiled(FDM_POST_KERNEL(k_features_tiled<16>));
+  } else if (pct_ok && need_lo <= 8 && need_hi <= 8) launch_feat(FDM_POST_KERNEL(k_features<8>));
+  else if (pct_ok && need_lo <= 16 && need_hi <= 16) launch_feat(FDM_POST_KERNEL(k_features<16>));
+  else if (reg.size() <= size_t(kMaxRegion) && (e->opt.dbg_post & 8)) launch_feat(FDM_POST_KERNEL(k_features<0>));
   else if (features_sel_lds_bytes(halo, int(reg.size())) <= 160u * 1024u && !(e->opt.dbg_post & 8)) {
     // any disc, any percentile pair: order statistics by bisection on an LDS tile (fdm_post.hpp k_features_sel)
     const unsigned lds = features_sel_lds_bytes(halo, int(reg.size()));
     if ((rc = allow_lds(k_features_sel, lds))) return rc;
-    hipLaunchKernelGGL(k_features_sel, dim3(tile3_blocks(e)), dim3(256), lds, e->stream, e->G, e->d_state, int(e->scan_no & 3),
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_features_sel), dim3(tile3_blocks(e)), dim3(256), lds, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                        e->d_region, F, halo, elev_p, O);
-  } else if (reg.size() <= size_t(kMaxRegion)) launch_feat(k_features<0>);
+  } else if (reg.size() <= size_t(kMaxRegion)) launch_feat(FDM_POST_KERNEL(k_features<0>));
   else {  // any radius the reference accepts (config/postprocess.hpp:45): the sorted heights in the global pool
     unsigned blocks = 0;
     if ((rc = ensure_pool(e, reg.size(), 256u, &blocks, reg.size()))) return rc;
-    hipLaunchKernelGGL(k_features_big, dim3(blocks), dim3(256), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_features_big), dim3(blocks), dim3(256), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                        e->d_region, F, elev_p, elev_s, O, unsigned(e->ncell), e->d_post_pool);
   }
   HIPCK(hipGetLastError());
   return FDM_OK;
 }
 
+int fdm_engine_debug_last_post_kernel(fdm_engine* e, char* out, int cap) {
+  if (!e || !out || cap < 1) return fail(FDM_ERR_INVALID, "null argument");
+  std::snprintf(out, size_t(cap), "%s", e->last_post_kernel);
+  return FDM_OK;
+}
 
 }  // extern "C"

@@ -369,6 +369,13 @@ class Engine:
         _ck(self._lib.fdm_engine_debug_batch_launches(self._h, out))
         return int(out[0]), int(out[1])
 
+    def debug_last_post_kernel(self):
+        """Name of the kernel the last stencil-stage call launched ("k_median_sel", "k_features_tiled<6, 7>", ...); "" if it
+        returned before launching."""
+        buf = C.create_string_buffer(128)
+        _ck(self._lib.fdm_engine_debug_last_post_kernel(self._h, buf, len(buf)))
+        return buf.value.decode()
+
     def debug_timeline(self, cap_blocks=1 << 16):
         """(option dbg_timeline=1) -> (ticks[n_blocks, 2] uint64 of the 100 MHz clock, n_update_blocks) of the
         last fused large-scan launch."""

@@ -31,6 +31,12 @@ int fdm_engine_debug_timeline(fdm_engine* e, uint64_t* ticks, uint64_t cap_block
  * pipeline they mean to check. */
 int fdm_engine_debug_batch_launches(fdm_engine* e, uint64_t out[2]);
 
+/* Which kernel the last fdm_engine_apply_inpainting / _spatial_smoothing / _uncertainty_fusion / _feature_extraction call
+ * launched, with its template arguments as the launch site spells them ("k_fusion_f64_tiled<29, true>", "k_median_sel"),
+ * copied into out[cap] and always terminated; the empty string when the call returned before it launched (a disabled
+ * fusion, a missing layer, zero inpainting passes).  Host bookkeeping only: nothing is read from the device. */
+int fdm_engine_debug_last_post_kernel(fdm_engine* e, char* out, int cap);
+
 /* fdm_pcd_debug_profile(1): the calling thread's PCD kernels are timed with device events from now on (off by
  * default; scripts/pcd_bench.py).  fdm_pcd_debug_last_kernel_ms: ms2[0] the k_pcd_decode launch of the last
  * fdm_pcd_decode / fdm_pcd_build_dem of a binary file, ms2[1] the k_pcd_pack launch of the last binary fdm_pcd_encode /

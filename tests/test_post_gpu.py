@@ -11,6 +11,7 @@ Tolerances (stated per stage):
 import numpy as np
 import pytest
 
+import post_cases as PC
 from helpers import assert_arrays_close, assert_layers_equal, pair, run_both
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +101,7 @@ def test_inpainting_parity(gpu, R):
     el = terrain(rng, shape, holes=0.55)
     for iters, mv, inplace in ((3, 2, False), (1, 3, False), (4, 1, True), (0, 2, False)):
         both((eng, ref), lambda o: (o.set_layer("elevation", el), o.apply_inpainting(iters, mv, inplace)))
+        assert eng.debug_last_post_kernel() == ("k_inpaint_pass_tiled" if iters else "")
         exact(eng, ref)
     both((eng, ref), lambda o: o.apply_inpainting(3, 2))
     assert np.isfinite(eng.layer("elevation_inpainted")).sum() > np.isfinite(el).sum()
@@ -111,10 +113,12 @@ def test_median_smoothing_parity(gpu, R):
     el = terrain(rng, shape, holes=0.2)
     el[rng.uniform(size=shape) < 0.02] = 50.0  # spikes
     # odd kernels, EVEN kernels (region(Size(k, k)) spans [-k/2, k/2]: the (k + 1)-wide box) and windows beyond 256
-    # cells (17 x 17 = 289, 22 -> 23 x 23 = 529: the pooled kernel) — every size the reference accepts
+    # cells (17 x 17 = 289, 22 -> 23 x 23 = 529) — every size the reference accepts
     # (17 and up: k_median_sel, selection by bisection on an LDS tile; 41 x 41 = 1 681 cells needs 48 KB of it)
-    for k, mv in ((3, 5), (5, 9), (7, 1), (4, 5), (15, 30), (17, 40), (22, 3), (41, 200)):
+    for k, mv, kernel in ((3, 5, "k_median3_tiled"), (5, 9, "k_median"), (7, 1, "k_median"), (4, 5, "k_median"),
+                          (15, 30, "k_median"), (17, 40, "k_median_sel"), (22, 3, "k_median_sel"), (41, 200, "k_median_sel")):
         both((eng, ref), lambda o: (o.set_layer("elevation", el), o.apply_spatial_smoothing("elevation", k, mv)))
+        assert eng.debug_last_post_kernel() == kernel, k
         exact(eng, ref, ["elevation"])
     with pytest.raises(gpu.EngineError):
         eng.apply_spatial_smoothing("elevation", 0, 5)
@@ -139,28 +143,24 @@ def test_uncertainty_fusion_small_discs_ties_and_quantile_edges(gpu, R):
     ends of the range it takes (0 and > 1 go to the integer-sample kernel) — all bit for bit against the oracle."""
     rng = np.random.default_rng(41)
     eng, ref, shape = rolled_pair(gpu, R, rng, size=12.0, res=0.05)
-    el = terrain(rng, shape, holes=0.35)
-    half = np.abs(rng.normal(0.05, 0.03, shape)).astype(F32) + F32(0.005)
-    up, lo = el + half, el - half
-    # plateaus of equal bounds (ties keep the entry order), signed zeros, and pairs so far apart that the weight is <= 1e-6
-    up[20:60, 20:60] = np.where(np.isfinite(up[20:60, 20:60]), F32(0.25), up[20:60, 20:60])
-    lo[20:60, 20:60] = np.where(np.isfinite(lo[20:60, 20:60]), F32(-0.125), lo[20:60, 20:60])
-    z = rng.uniform(size=shape) < 0.05
-    lo[z & np.isfinite(lo)] = F32(-0.0)
-    z2 = rng.uniform(size=shape) < 0.05
-    up[z2 & np.isfinite(up) & (lo <= 0)] = F32(0.0)
-    far = rng.uniform(size=shape) < 0.05
-    up[far & np.isfinite(up)] = F32(3.0e6)   # 1 / (range + 1e-4) * w_spatial <= 1e-6: counted as valid, never sampled
-    inv = rng.uniform(size=shape) < 0.02
-    up[inv & np.isfinite(up)] = F32(-5.0)    # upper below lower: a negative range, a negative (or huge) weight
-    cases = []
-    for radius in (0.049, 0.05, 0.0708, 0.1, 0.112, 0.1415, 0.15):   # 1, 5, 9, 13, 21, 25, 29 cells
+    # plateaus of equal bounds (ties keep the entry order), signed zeros, pairs so far apart that the weight is <= 1e-6
+    # (counted as valid, never sampled), upper below lower (a negative range, a negative or huge weight), holes
+    up, lo = PC.bound_field(shape, 41)
+    cases, kernels = [], []
+    for radius, kernel in ((0.049, "k_fusion_f64_tiled<29, false>"), (0.05, "k_fusion_f64_tiled<5, true>"),
+                           (0.0708, "k_fusion_f64_tiled<9, true>"), (0.1, "k_fusion_f64_tiled<13, true>"),
+                           (0.112, "k_fusion_f64_tiled<21, true>"), (0.1415, "k_fusion_f64_tiled<25, true>"),
+                           (0.15, "k_fusion_f64_tiled<29, true>")):   # 1, 5, 9, 13, 21, 25, 29 cells
         cases.append((True, radius, 0.05, 0.01, 0.99, 3))
+        kernels.append(kernel)
     cases += [(True, 0.15, 0.05, 1e-6, 1.0, 1), (True, 0.15, 0.05, 0.0, 1.0, 3), (True, 0.15, 0.05, 0.5, 0.5, 29),
               (True, 0.15, 0.05, 0.25, 1.5, 3), (True, 0.1, 0.02, 0.01, 0.99, 14), (True, 0.15, 0.3, 0.999, 0.001, 2)]
-    for cfgv in cases:
+    kernels += ["k_fusion_f64_tiled<29, true>", "k_fusion_net32_tiled", "k_fusion_f64_tiled<29, true>",
+                "k_fusion_net32_tiled", "k_fusion_f64_tiled<13, true>", "k_fusion_f64_tiled<29, true>"]
+    for cfgv, kernel in zip(cases, kernels):
         both((eng, ref), lambda o: (o.set_layer("upper_bound", up), o.set_layer("lower_bound", lo),
                                     o.apply_uncertainty_fusion(*cfgv)))
+        assert eng.debug_last_post_kernel() == kernel, cfgv
         exact(eng, ref, ["upper_bound", "lower_bound"])
     # the same call twice in a row: the second one finds its region table on the device
     both((eng, ref), lambda o: (o.apply_uncertainty_fusion(*cases[6]), o.apply_uncertainty_fusion(*cases[6])))
@@ -178,9 +178,12 @@ def test_feature_extraction_order_statistic_slots(gpu, R):
     R.set_trig_mode(1)
     try:
         # slots: 6 / 7, 8 / 8, 16 / 16, 4 / 4 (49-cell disc), 6 / 7, 2 / 3 (29-cell disc: the defaults on a 0.1 m map), 2 / 3 (13 cells)
-        for radius, lo, hi in ((0.3, 0.05, 0.95), (0.3, 0.06, 0.94), (0.3, 0.13, 0.87), (0.2, 0.05, 0.95), (0.3, 0.0, 0.95),
-                               (0.15, 0.05, 0.95), (0.1, 0.05, 0.95), (0.3, 0.05, 0.95)):
+        for radius, lo, hi, kernel in ((0.3, 0.05, 0.95, "k_features_tiled<6, 7>"), (0.3, 0.06, 0.94, "k_features_tiled<8>"),
+                                       (0.3, 0.13, 0.87, "k_features_tiled<16>"), (0.2, 0.05, 0.95, "k_features_tiled<4, 4>"),
+                                       (0.3, 0.0, 0.95, "k_features_tiled<6, 7>"), (0.15, 0.05, 0.95, "k_features_tiled<2, 3>"),
+                                       (0.1, 0.05, 0.95, "k_features_tiled<2, 3>"), (0.3, 0.05, 0.95, "k_features_tiled<6, 7>")):
             both((eng, ref), lambda o: (o.set_layer("elevation", el), o.apply_feature_extraction(radius, 4, lo, hi)))
+            assert eng.debug_last_post_kernel() == kernel, (radius, lo, hi)
             exact(eng, ref, ["step", "slope", "roughness", "curvature", "_normal_x", "_normal_y", "_normal_z"])
         # a publish cycle runs fusion and feature extraction one after the other, again and again: each keeps its table on
         # the device, neither disturbs the other's (and a changed parameter still uploads)
@@ -197,19 +200,23 @@ def test_feature_extraction_order_statistic_slots(gpu, R):
 
 def test_discs_of_more_than_256_cells(gpu, R):
     """config/postprocess.hpp:35,45 put no bound on the radii: 0.3 m on a 0.02 m map is a disc of 709 cells, 0.15 m
-    one of 177.  The big-neighbourhood kernels (per-cell lists in a global pool) against the oracle: fusion bit-exact;
-    feature extraction bit-exact with correctly rounded trig (as the tiled kernel's test), `step` included."""
+    one of 177.  What runs there: k_fusion_wave at n_pad 1 024 (one wavefront per cell, the samples sorted in LDS) and
+    k_features_sel (order statistics by bisection on an LDS tile) — the pooled kernels these shapes took before those two
+    existed are held to the oracle by tests/test_post_dispatch_gpu.py.  Fusion bit-exact; feature extraction bit-exact
+    with correctly rounded trig (as the tiled kernel's test), `step` included."""
     rng = np.random.default_rng(29)
     eng, ref, shape = rolled_pair(gpu, R, rng, size=3.0, res=0.02)  # 150 x 150 cells
     el = terrain(rng, shape, holes=0.2, noise=0.005)
     half = np.abs(rng.normal(0.03, 0.02, shape)).astype(F32) + F32(0.004)
     both((eng, ref), lambda o: (o.set_layer("upper_bound", el + half), o.set_layer("lower_bound", el - half),
                                 o.apply_uncertainty_fusion(True, 0.3, 0.1, 0.05, 0.95, 5)))
+    assert eng.debug_last_post_kernel() == "k_fusion_wave"
     exact(eng, ref, ["upper_bound", "lower_bound"])
     assert not np.array_equal(eng.layer("upper_bound"), el + half, equal_nan=True)
     R.set_trig_mode(1)
     try:
         both((eng, ref), lambda o: (o.set_layer("elevation", el), o.apply_feature_extraction(0.3, 4, 0.05, 0.95)))
+        assert eng.debug_last_post_kernel() == "k_features_sel"
         assert np.isfinite(eng.layer("slope")).sum() > 0.5 * el.size
         exact(eng, ref, ["step", "slope", "roughness", "curvature", "_normal_x", "_normal_y", "_normal_z"])
     finally:
@@ -224,8 +231,10 @@ def test_feature_extraction_any_percentile_pair(gpu, R):
     el = terrain(rng, shape, holes=0.2, noise=0.01)
     R.set_trig_mode(1)
     try:
-        for lo, hi in ((0.3, 0.7), (0.0, 1.0), (0.5, 0.5)):
+        # (0 / 1 are the smallest and the largest height: among the tiled kernel's two / three slots)
+        for lo, hi, kernel in ((0.3, 0.7, "k_features_sel"), (0.0, 1.0, "k_features_tiled<2, 3>"), (0.5, 0.5, "k_features_sel")):
             both((eng, ref), lambda o: (o.set_layer("elevation", el), o.apply_feature_extraction(0.3, 4, lo, hi)))
+            assert eng.debug_last_post_kernel() == kernel, (lo, hi)
             exact(eng, ref, ["step", "slope", "roughness", "curvature", "_normal_x", "_normal_y", "_normal_z"])
     finally:
         R.set_trig_mode(0)
