@@ -25,13 +25,17 @@
 //   bin half     512 points per block (two per thread), scan k of the batch; the first wavefront walks the chain of k
 //                moves (every lane rounds its own scan's pose once; only the position is accumulated in scan order;
 //                the reference's divide only for poses on a rounding tie) while the point loads are in flight.
-//                Points fold straight into a per-block LDS cell table (axis_fast indexing), the table's occupied
-//                entries are compacted and flushed with memory-side atomics on the block's unique cells.
+//                Points fold straight into a per-block LDS cell table (axis_fast indexing): both points of a thread
+//                probe it in one batch, and the lane that finds a slot empty has CLAIMED it and numbers the cell's
+//                record there (a ballot and one LDS add per wavefront) — so behind the fold's one barrier the records
+//                are listed already, and they are flushed with memory-side atomics on the block's unique cells.
 //                No second look at the scan: the thread that merges a block-local minimum into the scratch also
 //                evaluates that point's sigma_z^2 (the block keeps its points' sensor-frame coordinates in LDS) and
 //                stores {map-frame z, sigma_z^2} in an observation array at the block's SLOT for the cell (lb * kMBlock
-//                + the cell's rank in the block's compacted list: a block's winners are one contiguous run); likewise
-//                the colour of a block-local last point.  The update finds the winner's entry through the slot in the
+//                + the record's number: a block's winners are one contiguous run); likewise the colour of a
+//                block-local last point.  The order of the slots BETWEEN blocks is the order of the points ("the first
+//                point wins", "the last colour wins"); the order inside a block is the order of the claims, depends on
+//                timing and shows in no output.  The update finds the winner's entry through the slot in the
 //                reduced key (aux.w for the colour), and the caller's arrays are dead as soon as the launch has run.
 //   update half  64 cells per block (memory order), four threads per cell, laid out group-major: thread q * 64 + c looks
 //                after scans 4 q .. 4 q + 3 of cell c, so wavefront q holds one group of four scans of all 64 cells and
@@ -242,9 +246,10 @@ struct MBinLds {
   unsigned long long t_key[kMBlock];
   uint32_t t_cell[kMBlock], t_zmx[kMBlock], t_imx[kMBlock], t_fst[kMBlock], t_lst[kMBlock];
   float4 s_pt[kMBlock];  // sensor-frame x, y, z | map-frame z of the block's points
-  uint16_t s_list[kMBlock];  // the occupied table slots, compacted for the flush
+  uint16_t s_list[kMBlock];  // the table slots of the block's records, in the order they were claimed
   DevCand s_cand;
-  unsigned s_pass[4], s_in[4], s_occ[4 * kMPts];
+  unsigned s_pass[4], s_in[4];
+  unsigned s_nrec;  // records so far: a wavefront adds its claims (mbin_body's fold)
 };
 struct MEvent { uint32_t idx; uint16_t cell, k; };  // winner's slot in obs | cell in tile | scan
 struct alignas(16) MObs { float min_z, var, max_z, iobs; };  // (one 128-bit LDS access)
@@ -502,6 +507,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     S.t_cell[t] = kEmptyCell;
     S.t_zmx[t] = 0u; S.t_imx[t] = 0u; S.t_fst[t] = kNoIdx; S.t_lst[t] = 0u;
   }
+  if (threadIdx.x == 0) S.s_nrec = 0u;
 #if FDM_MB_PHASES == 2
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   FDM_PHASE(1);
@@ -630,13 +636,16 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   uint32_t* const S_cobs = B.cobs + size_t(k) * B.obs_stride;
 
   // one cell's reduction goes to the scan's scratch; the merging thread also leaves what the update needs of the
-  // block-local winner / last point in the block's SLOT for the cell: slot = lb * kMBlock + j, j = the cell's rank in
-  // the block's compacted list.  The slot replaces the point index in the low word of the key and in aux.w, so that
-  // a block's observations form one contiguous run (a few lines) instead of one isolated store per cell, and the
-  // update's gather of neighbouring cells shares lines.  Order is kept: block lb owns points [lb kMBlock, lb kMBlock
-  // + kMBlock) and holds one entry per cell, so a lower slot on equal ord(z) is still the earlier point (strict "<",
-  // elevation_mapping.cpp:41-92), and a higher slot is still the later last point.  j < the block's inside points, so
-  // slot < n: inside the scan's slot of obs / cobs and never kNoIdx.  fst and zs stay point indices (never gathered).
+  // block-local winner / last point in the block's SLOT for the cell: slot = lb * kMBlock + j, j = the number the
+  // cell's record got when its table slot was claimed (the fold below).  The slot replaces the point index in the low
+  // word of the key and in aux.w, so that a block's observations form one contiguous run (a few lines) instead of one
+  // isolated store per cell, and the update's gather of neighbouring cells shares lines.  Order is kept where it
+  // matters: block lb owns points [lb kMBlock, lb kMBlock + kMBlock) and holds ONE entry per cell, so between two
+  // blocks a lower slot on equal ord(z) is still the earlier point (strict "<", elevation_mapping.cpp:41-92), and a
+  // higher slot is still the later last point.  The order of the records INSIDE a block is the order in which its
+  // wavefronts reached the counter — it depends on timing, and no output may depend on it: a cell never compares two
+  // slots of one block.  j < the block's claims <= its inside points, so slot < n: inside the scan's slot of obs / cobs
+  // and never kNoIdx.  fst and zs stay point indices (never gathered).
   auto merge = [&](uint32_t c, unsigned long long key, uint32_t zmx, uint32_t imx, uint32_t fst, uint32_t lst,
                    uint32_t slot) {
     if (K.dbg == 1) return;
@@ -669,6 +678,11 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   bool any_glob = false;
   const bool any_start = cand.sr != 0 || cand.sc != 0;
   const double off_r = (G.half_x + cand.px) * G.inv_res_k, off_c = (G.half_y + cand.py) * G.inv_res_k;
+  // what each of the thread's points contributes to its cell, and whether the point goes to the table itself
+  int cells[kMPts];
+  bool commit[kMPts];
+  unsigned long long keys[kMPts];
+  uint32_t zmxs[kMPts], imxs[kMPts], fsts[kMPts], lsts[kMPts];
 #pragma unroll
   for (int h = 0; h < kMPts; ++h) {
     const unsigned i = i0 + unsigned(h) * 256u;
@@ -692,7 +706,6 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
       if (z == 0.0f) atomicMin(S_zs + size_t(cell) * 2, (i << 1) | (__float_as_uint(z) >> 31));
       if (has_int && vint == 0.0f) atomicMin(S_zs + size_t(cell) * 2 + 1, (i << 1) | (__float_as_uint(vint) >> 31));
     }
-    // what this point contributes to its cell
     unsigned long long key = kEmptyKey;
     uint32_t zmx = 0u, imx = 0u, fst = kNoIdx, lst = 0u;
     if (inside) {
@@ -711,7 +724,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     // registers first (segmented scan over runs of equal cell, as k_bin does) and only the run TAILS touch the table;
     // a firing-order LiDAR scan (neighbouring lanes = different beams: every lane its own run) skips the merge —
     // decided per wavefront from two ballots.  min / max are idempotent: either way the table ends up the same.
-    bool commit = inside;
+    commit[h] = inside;
     {
       const int prev_cell = __shfl_up(inside ? cell : -1, 1);
       const bool head = inside && (lane == 0u || prev_cell != cell);
@@ -734,29 +747,63 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
         }
         // (lst: the tail of a run is its highest point index already)
         const int next_cell = __shfl_down(mcell, 1);
-        commit = inside && (lane == 63u || next_cell != cell);
+        commit[h] = inside && (lane == 63u || next_cell != cell);
       }
     }
-    if (commit) {
-#ifdef FDM_X_MHASH  // (measurement build, profiles/r06/batch_max.txt: a multiplicative hash instead of cell mod 512)
-      uint32_t hh = (uint32_t(cell) * 2654435761u) >> 23;
-#else
-      uint32_t hh = uint32_t(cell) & (kMBlock - 1u);
-#endif
-      while (true) {
-        const uint32_t prev = atomicCAS(&S.t_cell[hh], kEmptyCell, uint32_t(cell));
-        if (prev == kEmptyCell || prev == uint32_t(cell)) break;
-        hh = (hh + 1) & (kMBlock - 1u);
-      }
-      atomicMin(&S.t_key[hh], key);
-      atomicMax(&S.t_zmx[hh], zmx);  // (max with 0: no-op)
-      if (has_int) {
-        atomicMax(&S.t_imx[hh], imx);
-        atomicMin(&S.t_fst[hh], fst);
-      }
-      if (has_col) atomicMax(&S.t_lst[hh], lst);
-    }
+    cells[h] = cell; keys[h] = key; zmxs[h] = zmx; imxs[h] = imx; fsts[h] = fst; lsts[h] = lst;
     niw += unsigned(__popcll(__ballot(inside)));
+  }
+  // ---- fold: the thread's points probe the table in ONE batch (the probes' LDS round trips overlap; a second look
+  // only on a real collision), then the atomics.  The lane whose probe found the slot EMPTY has claimed it — exactly
+  // one lane per cell of the block — and numbers the cell's record there: a ballot of the claims and one LDS add per
+  // wavefront for all its points together (as fdm_tbin2.hpp).  No compaction pass over the table behind the fold.
+  uint32_t hs[kMPts], seen[kMPts];
+#pragma unroll
+  for (int h = 0; h < kMPts; ++h) {
+#ifdef FDM_X_MHASH  // (measurement build, profiles/r06/batch_max.txt: a multiplicative hash instead of cell mod 512)
+    hs[h] = (uint32_t(cells[h]) * 2654435761u) >> 23;
+#else
+    hs[h] = uint32_t(cells[h]) & (kMBlock - 1u);
+#endif
+    seen[h] = uint32_t(cells[h]);
+    if (commit[h]) seen[h] = atomicCAS(&S.t_cell[hs[h]], kEmptyCell, uint32_t(cells[h]));
+  }
+  unsigned long long claims[kMPts];
+  unsigned n_claims = 0u;
+#pragma unroll
+  for (int h = 0; h < kMPts; ++h) {
+    bool claimed = commit[h] && seen[h] == kEmptyCell;
+    if (commit[h] && !claimed && seen[h] != uint32_t(cells[h])) {  // a real collision: linear probing
+      uint32_t hh = hs[h];
+      while (true) {
+        hh = (hh + 1) & (kMBlock - 1u);
+        const uint32_t prev = atomicCAS(&S.t_cell[hh], kEmptyCell, uint32_t(cells[h]));
+        claimed = prev == kEmptyCell;
+        if (claimed || prev == uint32_t(cells[h])) break;
+      }
+      hs[h] = hh;
+    }
+    claims[h] = __ballot(claimed);
+    n_claims += unsigned(__popcll(claims[h]));
+    if (commit[h]) {
+      atomicMin(&S.t_key[hs[h]], keys[h]);
+      atomicMax(&S.t_zmx[hs[h]], zmxs[h]);  // (max with 0: no-op)
+      if (has_int) {
+        atomicMax(&S.t_imx[hs[h]], imxs[h]);
+        atomicMin(&S.t_fst[hs[h]], fsts[h]);
+      }
+      if (has_col) atomicMax(&S.t_lst[hs[h]], lsts[h]);
+    }
+  }
+  if (n_claims) {  // (wave-uniform) claims <= the block's inside points <= kMBlock: the list cannot overflow
+    unsigned base = 0u;
+    if (lane == 0u) base = atomicAdd(&S.s_nrec, n_claims);
+    base = uni(base);
+#pragma unroll
+    for (int h = 0; h < kMPts; ++h) {
+      if ((claims[h] >> lane) & 1ull) S.s_list[base + lane_rank(claims[h])] = uint16_t(hs[h]);
+      base += unsigned(__popcll(claims[h]));
+    }
   }
   // (the ballot BEFORE the lane test: inside `if (lane == 0)` it would see lane 0 alone — a small scan whose first
   // point lies outside the map then never reported "observed", and the obstacle layer kept the previous scan's values)
@@ -765,35 +812,13 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     S.s_in[wave] = niw;
     if (wave_glob) ms->inside[k] = 1u;
   }
-  // ---- flush: the occupied slots are compacted first, so that the sigma_z^2 evaluation and the memory-side
-  // atomics of a block's ~100 cells keep two wavefronts busy instead of four, twice ----
+  // ---- flush: the block's records in claim order, so that the sigma_z^2 evaluation and the memory-side atomics of a
+  // block's ~100 cells keep two wavefronts busy instead of four, twice ----
 #if FDM_MB_PHASES != 2
   FDM_PHASE(2);  // index + LDS fold done
 #endif
-  __syncthreads();
-  uint32_t tc[kMPts];
-  unsigned before[kMPts];
-#pragma unroll
-  for (int h = 0; h < kMPts; ++h) {
-    tc[h] = S.t_cell[threadIdx.x + unsigned(h) * 256u];
-    const unsigned long long mo = __ballot(tc[h] != kEmptyCell);
-    before[h] = unsigned(__popcll(mo & ((1ull << lane) - 1ull)));
-    if (lane == 0u) S.s_occ[h * 4 + int(wave)] = unsigned(__popcll(mo));
-  }
-  __syncthreads();
-  unsigned n_occ = 0u;
-#pragma unroll
-  for (int h = 0; h < kMPts; ++h) {
-    unsigned base = 0u;
-#pragma unroll
-    for (int q = 0; q < 4 * kMPts; ++q) {
-      const unsigned c = S.s_occ[q];
-      if (q < h * 4 + int(wave)) base += c;
-      if (h == 0) n_occ += c;
-    }
-    if (tc[h] != kEmptyCell) S.s_list[base + before[h]] = uint16_t(threadIdx.x + unsigned(h) * 256u);
-  }
-  __syncthreads();
+  __syncthreads();  // the table, the record list and its count are complete
+  const unsigned n_occ = uni(S.s_nrec);
   for (unsigned j = threadIdx.x; j < n_occ; j += 256u) {
     const unsigned t = S.s_list[j];
     merge(S.t_cell[t], S.t_key[t], S.t_zmx[t], S.t_imx[t], S.t_fst[t], S.t_lst[t], lb * kMBlock + j);
