@@ -10,13 +10,15 @@ Layout (only what the path needs):
   cpp/         C++17 host mirror of fastdem::FastDEM / ElevationMap over the C ABI
 """
 from . import capi, synth  # noqa: F401
-from .engine import (DEMConfig, Engine, EngineError, HostArray, RegistrationResult, align_gicp, align_icp,  # noqa: F401
-                     align_plane_icp, align_settings, build_dem, estimate_normals, from_point_cloud, grid_max_z,
-                     host_array, linearize, normals_last_stats, register_last_stats, sor_last_stats,
+from .engine import (DEMConfig, Engine, EngineError, HostArray, RansacResult, RegistrationResult, align_gicp,  # noqa: F401
+                     align_icp, align_plane_icp, align_settings, build_dem, estimate_normals, from_point_cloud,
+                     grid_max_z, host_array, linearize, normals_last_stats, register_last_stats, segment_ground,
+                     segment_last_stats, segment_multiple_planes, segment_plane, sor_last_stats,
                      statistical_outlier_removal, voxel_grid)
 from . import pcd  # noqa: F401,E402
 
 __all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud", "DEMConfig", "build_dem",
            "statistical_outlier_removal", "sor_last_stats", "voxel_grid", "grid_max_z", "estimate_normals",
            "normals_last_stats", "align_icp", "align_plane_icp", "align_gicp", "linearize", "align_settings",
-           "register_last_stats", "RegistrationResult", "capi", "synth", "pcd"]
+           "register_last_stats", "RegistrationResult", "segment_ground", "segment_plane", "segment_multiple_planes",
+           "segment_last_stats", "RansacResult", "capi", "synth", "pcd"]

@@ -145,6 +145,30 @@ class FdmRegisterStats(C.Structure):  # fdm_register_stats
                 ("voxel", C.c_float), ("ring_limit", C.c_int32), ("linearizations", C.c_int32), ("ms", C.c_float * 3)]
 
 
+class FdmGroundSegConfig(C.Structure):
+    """fdm_ground_seg_config == nanopcl::segmentation::GroundSegConfig (segmentation/ground_seg.hpp:34-40)."""
+
+    _fields_ = [("grid_resolution", C.c_float), ("cell_percentile", C.c_float), ("ground_thickness", C.c_float),
+                ("max_ground_height", C.c_float), ("min_points_per_cell", C.c_uint64)]
+
+
+class FdmRansacConfig(C.Structure):
+    """fdm_ransac_config == nanopcl::segmentation::RansacConfig (segmentation/ransac_plane.hpp:104-110)."""
+
+    _fields_ = [("distance_threshold", C.c_float), ("max_iterations", C.c_int32), ("probability", C.c_double),
+                ("min_inliers", C.c_uint64), ("refine_model", C.c_int32)]
+
+
+class FdmRansacResult(C.Structure):  # fdm_ransac_result
+    _fields_ = [("coefficients", C.c_float * 4), ("fitness", C.c_double), ("iterations", C.c_int32),
+                ("success", C.c_int32), ("n_inliers", C.c_uint64)]
+
+
+class FdmSegmentStats(C.Structure):  # fdm_segment_stats
+    _fields_ = [("n_batches", C.c_uint64), ("n_hypotheses", C.c_uint64), ("n_invalid_samples", C.c_uint64),
+                ("batch", C.c_uint32), ("ms", C.c_float * 4)]
+
+
 REGISTER_METHOD = {"icp": 0, "plane": 1, "gicp": 2}
 ROBUST_KERNEL = {"none": 0, "huber": 1, "tukey": 2, "cauchy": 3}
 
@@ -334,6 +358,14 @@ PROTOTYPES = {
     "fdm_cloud_register_linearize": (C.c_int, [C.c_int, C.POINTER(FdmRegisterClouds), _P, C.POINTER(FdmAlignSettings),
                                                C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), _P]),
     "fdm_register_last_stats": (C.c_int, [C.POINTER(FdmRegisterStats)]),
+    "fdm_cloud_segment_ground": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.POINTER(FdmGroundSegConfig), C.c_int, _P, _P,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fdm_cloud_segment_plane": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, _P, C.c_uint64, C.POINTER(FdmRansacConfig),
+                                          C.c_int, _P, C.POINTER(FdmRansacResult)]),
+    "fdm_cloud_segment_planes": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.POINTER(FdmRansacConfig), C.c_uint64,
+                                           C.c_double, C.c_int, _P, C.POINTER(FdmRansacResult), C.POINTER(C.c_uint64)]),
+    "fdm_segment_last_stats": (C.c_int, [C.POINTER(FdmSegmentStats)]),
+    "fdm_segment_debug_batch": (C.c_int, [C.c_int]),
     "fdm_cloud_debug_profile": (C.c_int, [C.c_int]),
     "fdm_cloud_debug_last_ms": (C.c_int, [_F]),
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),

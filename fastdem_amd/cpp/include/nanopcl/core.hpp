@@ -200,3 +200,4 @@ class PointCloud {
 
 #include "nanopcl/geometry/normal_estimation.hpp"  // estimateNormals, estimateCovariances, estimateNormalsCovariances
 #include "nanopcl/registration.hpp"                // alignICP, alignPlaneICP, alignGICP
+#include "nanopcl/segmentation.hpp"                // segmentGround, segmentPlane, segmentMultiplePlanes

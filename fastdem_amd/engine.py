@@ -1120,3 +1120,131 @@ def register_last_stats():
     return {"n_source": int(st.n_source), "n_target": int(st.n_target), "grid_x": int(st.grid_x), "grid_y": int(st.grid_y),
             "voxel": float(st.voxel), "ring_limit": int(st.ring_limit), "linearizations": int(st.linearizations),
             "ms": tuple(float(v) for v in st.ms)}
+
+
+# ---- cloud segmentation (fdm_cloud_segment_ground / _plane / _planes: include/fdm_engine.h) ----
+def _seg_cloud(x, y, z, device):
+    """(n, pointers of x y z, on_device, device, the arrays kept alive, torch module or None)."""
+    if _is_torch(x):
+        import torch
+        torch.cuda.current_stream(x.device).synchronize()
+        dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        keep = tuple(v.contiguous().float() for v in (x, y, z))
+        return keep[0].numel(), [_dptr(v) for v in keep], 1, dev, keep, torch
+    keep = tuple(_f32(v).reshape(-1) for v in (x, y, z))
+    return keep[0].size, [_ptr(v) for v in keep], 0, int(device), keep, None
+
+
+def _seg_u32(torch, n, like):
+    """An index array of capacity n where the cloud lives; (array, pointer)."""
+    if torch is not None:
+        a = torch.zeros(max(n, 1), dtype=torch.int32, device=like.device)
+        return a, _dptr(a)
+    a = np.zeros(max(n, 1), dtype=np.uint32)
+    return a, _ptr(a)
+
+
+def _seg_take(torch, a, k):
+    return (a[:k].long() & 0xFFFFFFFF) if torch is not None else a[:k].copy()
+
+
+def segment_ground(x, y, z, grid_resolution=0.5, cell_percentile=0.2, ground_thickness=0.3, max_ground_height=0.5,
+                   min_points_per_cell=2, device=0):
+    """nanopcl::segmentation::segmentGround(cloud, config) on the device: (ground, obstacles), the point indices of each
+    in ascending order — uint32 numpy arrays for numpy input, int64 device tensors for torch device tensors."""
+    lib = capi.load()
+    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
+    cfg = capi.FdmGroundSegConfig(float(np.float32(grid_resolution)), float(np.float32(cell_percentile)),
+                                  float(np.float32(ground_thickness)), float(np.float32(max_ground_height)),
+                                  int(min_points_per_cell))
+    ground, pg = _seg_u32(torch, n, keep[0])
+    obstacles, po = _seg_u32(torch, n, keep[0])
+    ng, no = C.c_uint64(0), C.c_uint64(0)
+    _ck(lib.fdm_cloud_segment_ground(n, *ptrs, on_device, C.byref(cfg), dev, pg, po, C.byref(ng), C.byref(no)))
+    return _seg_take(torch, ground, int(ng.value)), _seg_take(torch, obstacles, int(no.value))
+
+
+class RansacResult:
+    """nanopcl::segmentation::RansacResult: coefficients (float32[4]: nx, ny, nz, d), inliers (indices into the cloud, in
+    index-list order), fitness, iterations, success."""
+
+    def __init__(self, coefficients, inliers, fitness, iterations, success):
+        self.coefficients, self.inliers = coefficients, inliers
+        self.fitness, self.iterations, self.success = float(fitness), int(iterations), bool(success)
+
+    def outliers(self, total):
+        """RansacResult::outliers(total_points): the indices 0 .. total - 1 that are no inlier, ascending."""
+        if _is_torch(self.inliers):
+            import torch
+            mask = torch.ones(int(total), dtype=torch.bool, device=self.inliers.device)
+            mask[self.inliers] = False
+            return torch.nonzero(mask).reshape(-1)
+        mask = np.ones(int(total), dtype=bool)
+        mask[self.inliers] = False
+        return np.nonzero(mask)[0].astype(np.uint32)
+
+    def __repr__(self):
+        return (f"RansacResult(success={self.success}, coefficients={self.coefficients.tolist()}, "
+                f"inliers={len(self.inliers)}, fitness={self.fitness:.6f}, iterations={self.iterations})")
+
+
+def _ransac_config(distance_threshold, max_iterations, probability, min_inliers, refine_model):
+    return capi.FdmRansacConfig(float(np.float32(distance_threshold)), int(max_iterations), float(probability),
+                                int(min_inliers), 1 if refine_model else 0)
+
+
+def _ransac_result(torch, r, inliers):
+    return RansacResult(np.array(r.coefficients, dtype=np.float32), _seg_take(torch, inliers, int(r.n_inliers)),
+                        r.fitness, r.iterations, r.success)
+
+
+def segment_plane(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, min_inliers=3,
+                  refine_model=True, indices=None, device=0):
+    """nanopcl::segmentation::segmentPlane (RANSAC, fixed seed) over the whole cloud or over `indices` (positions are
+    sampled in that list, which may repeat a point).  Returns a RansacResult; its inliers are a uint32 numpy array for
+    numpy input, an int64 device tensor for torch device tensors."""
+    lib = capi.load()
+    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
+    cfg = _ransac_config(distance_threshold, max_iterations, probability, min_inliers, refine_model)
+    p_idx, m, idx = None, n, None
+    if indices is not None:
+        if torch is not None:
+            idx = indices.to(device=keep[0].device, dtype=torch.int64).to(torch.int32).contiguous()
+            p_idx, m = _dptr(idx), idx.numel()
+        else:
+            idx = np.ascontiguousarray(np.asarray(indices).astype(np.uint32)).reshape(-1)
+            p_idx, m = _ptr(idx), idx.size
+    inliers, pi = _seg_u32(torch, m, keep[0])
+    r = capi.FdmRansacResult()
+    _ck(lib.fdm_cloud_segment_plane(n, *ptrs, on_device, p_idx, m, C.byref(cfg), dev, pi, C.byref(r)))
+    del idx
+    return _ransac_result(torch, r, inliers)
+
+
+def segment_multiple_planes(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, min_inliers=3,
+                            refine_model=True, max_planes=5, min_fitness=0.1, device=0):
+    """nanopcl::segmentation::segmentMultiplePlanes: planes are taken one after the other, each from the points the
+    earlier ones left, until max_planes, fewer than 3 points, or a result without success or below min_fitness.
+    Returns a list of RansacResult."""
+    lib = capi.load()
+    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
+    cfg = _ransac_config(distance_threshold, max_iterations, probability, min_inliers, refine_model)
+    inliers, pi = _seg_u32(torch, n, keep[0])
+    res = (capi.FdmRansacResult * max(int(max_planes), 1))()
+    count = C.c_uint64(0)
+    _ck(lib.fdm_cloud_segment_planes(n, *ptrs, on_device, C.byref(cfg), int(max_planes), float(min_fitness), dev, pi, res,
+                                     C.byref(count)))
+    out, at = [], 0
+    for k in range(int(count.value)):
+        out.append(_ransac_result(torch, res[k], inliers[at:]))
+        at += int(res[k].n_inliers)
+    return out
+
+
+def segment_last_stats():
+    """What this thread's last segmentation call did: n_batches (launches of the scoring kernel), n_hypotheses,
+    n_invalid_samples, batch (iterations per launch), ms (zeros unless fdm_cloud_debug_profile is on)."""
+    st = capi.FdmSegmentStats()
+    _ck(capi.load().fdm_segment_last_stats(C.byref(st)))
+    return {"n_batches": int(st.n_batches), "n_hypotheses": int(st.n_hypotheses),
+            "n_invalid_samples": int(st.n_invalid_samples), "batch": int(st.batch), "ms": tuple(float(v) for v in st.ms)}

@@ -739,6 +739,101 @@ typedef struct fdm_register_stats {  /* the calling thread's last fdm_cloud_regi
 } fdm_register_stats;
 int fdm_register_last_stats(fdm_register_stats* out);
 
+/* ---- cloud segmentation: nanopcl::segmentation::segmentGround (segmentation/impl/ground_seg_impl.hpp:27-123) and
+ * segmentPlane / segmentMultiplePlanes (RANSAC; segmentation/impl/ransac_plane_impl.hpp:29-405) ----
+ * Engine-free and synchronous, on `device`; host arrays (on_device 0) or device arrays, the outputs where the inputs
+ * are; counts and results are host words.  The thread's current device is put back before a call returns.  All fp32
+ * arithmetic is done without contraction.  euclideanCluster is not offered: its output order follows a hash map's
+ * iteration order and an unstable sort.
+ *
+ * SEGMENT GROUND (:68-112).  A point's cell is gx = int(floor(x / grid_resolution)), gy likewise: a correctly rounded
+ * fp32 DIVISION (:33-34), not a product with a reciprocal.  A cell of fewer than min_points_per_cell points is
+ * obstacle-only (:46-48).  Otherwise its z values are sorted ascending, idx = size_t(cell_percentile * float(count - 1))
+ * — a float product, truncated — idx = min(idx, count - 1), robust = z_sorted[idx] (:54-57); robust > max_ground_height
+ * makes the cell obstacle-only (:60-62).  A point of another cell is an obstacle iff z > robust + ground_thickness, a
+ * strict comparison with an fp32 sum (:100-102).  ground and obstacles (capacity n each, either may be NULL) receive the
+ * point indices in ascending order; together they hold every point once.  n == 0: FDM_OK, both counts 0.
+ * FDM_ERR_INVALID, where the reference is undefined, with the lists untouched: a coordinate that is not finite; a floor
+ * outside int32; a resolution that is not finite and > 0; a percentile that is NaN or < 0 (one > 1 is clamped by the
+ * min, as in the reference); n > 2^32 - 4097 (the sorts' limit); a null x, y or z. */
+typedef struct fdm_ground_seg_config {  /* GroundSegConfig (segmentation/ground_seg.hpp), field for field */
+  float grid_resolution;                /* 0.5 */
+  float cell_percentile;                /* 0.2 */
+  float ground_thickness;               /* 0.3 */
+  float max_ground_height;              /* 0.5 */
+  uint64_t min_points_per_cell;         /* 2 */
+} fdm_ground_seg_config;
+/* cfg NULL = the defaults */
+int fdm_cloud_segment_ground(uint64_t n, const float* x, const float* y, const float* z, int on_device,
+                             const fdm_ground_seg_config* cfg, int device, uint32_t* ground, uint32_t* obstacles,
+                             uint64_t* n_ground, uint64_t* n_obstacles);
+
+/* SEGMENT PLANE (:241-334) over the index list (`indices` NULL = every point, in order; n_indices is then ignored and n
+ * is used).  XorShift64(42) is restarted on every call (:251); an iteration draws three POSITIONS in the list, then
+ * redraws the second while it equals the first and the third while it equals either (:265-273); the draws never depend
+ * on the model.  PlaneModel::fromPoints (:196-215): v1 = p2 - p1, v2 = p3 - p1, n = v1 x v2 as Eigen writes the cross
+ * product, norm = sqrt(n0*n0 + (n1*n1 + n2*n2)) correctly rounded (the three-term order ASSUMED: DESIGN.md §6); norm <
+ * 1e-10f: invalid; else n /= norm, d = -(n0*p1x + (n1*p1y + n2*p1z)); a model is valid iff d is finite, so a sampled NaN
+ * or infinite point gives an invalid model.  A point is an inlier iff |((nx*px + ny*py) + nz*pz) + d| < distance_threshold
+ * (:91).  A strictly greater count replaces the best and sets adaptive = computeAdaptiveIterations(count / double(n_indices),
+ * probability) in double (:56-71; a value no int holds is saturated); the loop ends at iter >= min(max_iterations,
+ * adaptive).  The engine scores the hypotheses of `batch` iterations per launch and replays the loop on the host over
+ * their counts in order: it stops at the exact iteration the sequential code stops at, and nothing computed past it
+ * influences the result.
+ * The default result — coefficients (0, 0, 1, 0), no inliers, fitness 0, iterations 0, success 0 — is returned for
+ * n_indices < 3 (:247) and for a best count below min_inliers (:310).  Otherwise the inliers of the best model are
+ * collected in list order; with refine_model and >= 3 of them the model is refined (:134-188) and, the refined model
+ * being valid, the inliers are collected again with it; fitness = n_inliers / double(n_indices); iterations = the loop
+ * passes made; success = the list is not empty.
+ * REFINEMENT.  The centroid in double, then the six central second moments in double about it, the symmetric 3 x 3
+ * eigenproblem in double, the eigenvector of the smallest eigenvalue cast to float and normalized in fp32, d = -(n .
+ * float(centroid)) in the three-term order.  Two things cannot be restated.  SUMMATION ORDER: the engine's sums are a
+ * fixed tree — the same for the same inlier count, no floating-point atomics — and differ from the reference's
+ * sequential sums by at most the rounding of n_inliers double additions.  EIGENVECTOR SIGN: Eigen's follows its QL
+ * iteration; THIS PROJECT'S DEFINITION: the refined normal's dot with the unrefined best model's normal (the float
+ * products summed in double) is not negative, and where it is exactly 0 the first non-zero component is positive.
+ * inliers: capacity n_indices (n for a NULL list).  FDM_ERR_INVALID: n >= 2^32; a list — or, without one, a cloud — of
+ * more than 2^32 - 4097 entries (blocks of 256 list positions are counted in 32 bits); an index >= n —
+ * found by a pass that only reads the list, before any kernel uses an entry as an address; a threshold that is NaN; a
+ * null x, y, z, inliers or result. */
+typedef struct fdm_ransac_config {  /* RansacConfig (segmentation/ransac_plane.hpp), field for field */
+  float distance_threshold;         /* 0.1 */
+  int32_t max_iterations;           /* 1000 */
+  double probability;               /* 0.99 */
+  uint64_t min_inliers;             /* 3 */
+  int32_t refine_model;             /* 1 */
+} fdm_ransac_config;
+typedef struct fdm_ransac_result {
+  float coefficients[4];            /* nx, ny, nz, d */
+  double fitness;
+  int32_t iterations;
+  int32_t success;
+  uint64_t n_inliers;
+} fdm_ransac_result;
+/* cfg NULL = the defaults */
+int fdm_cloud_segment_plane(uint64_t n, const float* x, const float* y, const float* z, int on_device,
+                            const uint32_t* indices, uint64_t n_indices, const fdm_ransac_config* cfg, int device,
+                            uint32_t* inliers, fdm_ransac_result* result);
+/* segmentMultiplePlanes (:366-405): the list of remaining indices starts as every point and stays on the device; after
+ * each accepted plane its inliers are struck out, the order of the rest kept.  The loop ends at max_planes, at fewer
+ * than 3 remaining indices, or at the first result without success or with fitness < min_fitness, which is not
+ * returned.  inliers (capacity n) receives the planes' lists one after the other, results[max_planes] their results,
+ * *n_planes how many. */
+int fdm_cloud_segment_planes(uint64_t n, const float* x, const float* y, const float* z, int on_device,
+                             const fdm_ransac_config* cfg, uint64_t max_planes, double min_fitness, int device,
+                             uint32_t* inliers, fdm_ransac_result* results, uint64_t* n_planes);
+typedef struct fdm_segment_stats {  /* the calling thread's last segmentation call (of segment_planes: summed over its planes) */
+  uint64_t n_batches;               /* launches of the scoring kernel */
+  uint64_t n_hypotheses;            /* hypotheses they scored, those past the loop's stop included */
+  uint64_t n_invalid_samples;       /* loop passes whose sample gave no valid model */
+  uint32_t batch;                   /* iterations per launch */
+  /* device ms while fdm_cloud_debug_profile (fdm_engine_debug.h) is on, zeros otherwise.  segment_plane(s): models and
+   * scoring, summed; collecting; the refinement's sums; the strike-out.  segment_ground: keys; the two sorts; run heads,
+   * cuts and classification; the two compactions */
+  float ms[4];
+} fdm_segment_stats;
+int fdm_segment_last_stats(fdm_segment_stats* out);
+
 typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
   float resolution;
   int32_t method;              /* RasterMethod: 0 Max, 1 Min, 2 Mean, 3 MinMax */

@@ -51,6 +51,11 @@ int fdm_pcd_debug_last_kernel_ms(float ms2[2]);
 int fdm_cloud_debug_profile(int on);
 int fdm_cloud_debug_last_ms(float ms3[3]);
 
+/* fdm_segment_debug_batch(b): the calling thread's fdm_cloud_segment_plane / _planes calls score b hypotheses per launch
+ * from now on (1 .. 128; 0 = the default again; scripts/segment_bench.py).  The result does not depend on it: the loop
+ * is replayed in order whatever the batch (fdm_segment_stats.batch reports what a call used). */
+int fdm_segment_debug_batch(int batch);
+
 #ifdef __cplusplus
 }
 #endif
