@@ -169,6 +169,19 @@ class FdmSegmentStats(C.Structure):  # fdm_segment_stats
                 ("batch", C.c_uint32), ("ms", C.c_float * 4)]
 
 
+class FdmClusterConfig(C.Structure):
+    """fdm_cluster_config == nanopcl::segmentation::ClusterConfig (segmentation/euclidean_cluster.hpp:44-48)."""
+
+    _fields_ = [("tolerance", C.c_float), ("min_size", C.c_uint64), ("max_size", C.c_uint64)]
+
+
+class FdmClusterStats(C.Structure):  # fdm_cluster_stats
+    _fields_ = [("n_points", C.c_uint64), ("n_components", C.c_uint64), ("n_kept", C.c_uint64), ("n_rejected", C.c_uint64),
+                ("n_clustered", C.c_uint64), ("candidate_pairs", C.c_uint64), ("tests", C.c_uint64),
+                ("neighbour_pairs", C.c_uint64), ("unions", C.c_uint64), ("range", C.c_int32), ("key_bits", C.c_uint32),
+                ("ms", C.c_float * 6)]
+
+
 REGISTER_METHOD = {"icp": 0, "plane": 1, "gicp": 2}
 ROBUST_KERNEL = {"none": 0, "huber": 1, "tukey": 2, "cauchy": 3}
 
@@ -366,6 +379,9 @@ PROTOTYPES = {
                                            C.c_double, C.c_int, _P, C.POINTER(FdmRansacResult), C.POINTER(C.c_uint64)]),
     "fdm_segment_last_stats": (C.c_int, [C.POINTER(FdmSegmentStats)]),
     "fdm_segment_debug_batch": (C.c_int, [C.c_int]),
+    "fdm_cloud_cluster": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, _P, C.c_uint64, C.POINTER(FdmClusterConfig), C.c_int,
+                                    _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "fdm_cluster_last_stats": (C.c_int, [C.POINTER(FdmClusterStats)]),
     "fdm_cloud_debug_profile": (C.c_int, [C.c_int]),
     "fdm_cloud_debug_last_ms": (C.c_int, [_F]),
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),

@@ -51,6 +51,35 @@ struct Color {
   constexpr Color(uint8_t r_, uint8_t g_, uint8_t b_) : r(r_), g(g_), b(b_) {}
 };
 
+struct Label {  // upper 16 bits: semantic class, lower 16 bits: instance id
+  uint32_t val;
+  constexpr Label() : val(0) {}
+  explicit constexpr Label(uint32_t v) : val(v) {}
+  constexpr operator uint32_t() const { return val; }
+  constexpr uint16_t semanticClass() const { return uint16_t(val >> 16); }
+  constexpr uint16_t instanceId() const { return uint16_t(val & 0xFFFFu); }
+};
+
+// core/span.hpp: a view over contiguous elements (what ClusterResult::clusterIndices hands out)
+template <typename T>
+class Span {
+ public:
+  constexpr Span() noexcept : data_(nullptr), size_(0) {}
+  constexpr Span(T* data, size_t size) noexcept : data_(data), size_(size) {}
+  constexpr T* data() const noexcept { return data_; }
+  constexpr size_t size() const noexcept { return size_; }
+  constexpr bool empty() const noexcept { return size_ == 0; }
+  constexpr T& operator[](size_t i) const { return data_[i]; }
+  constexpr T* begin() const noexcept { return data_; }
+  constexpr T* end() const noexcept { return data_ + size_; }
+  constexpr T& front() const { return data_[0]; }
+  constexpr T& back() const { return data_[size_ - 1]; }
+
+ private:
+  T* data_;
+  size_t size_;
+};
+
 // core/types.hpp:19-22 — Eigen::Vector4f there; the same 16 bytes here
 struct alignas(16) Point4 {
   float v[4];
@@ -112,6 +141,7 @@ class PointCloud {
     if (use_color_) rgb_.resize(n);
     if (use_normal_) { nx_.resize(n); ny_.resize(n); nz_.resize(n); }
     if (use_cov_) cov_.resize(n * 9);
+    if (use_label_) label_.resize(n);
   }
   void clear() { resize(0); }
 
@@ -121,6 +151,7 @@ class PointCloud {
     if (use_color_) rgb_.push_back(0u);
     if (use_normal_) { nx_.push_back(0.0f); ny_.push_back(0.0f); nz_.push_back(0.0f); }
     if (use_cov_) cov_.resize(cov_.size() + 9, 0.0f);
+    if (use_label_) label_.push_back(Label());
   }
   void add(float x, float y, float z, Intensity i) {
     if (!use_intensity_) useIntensity();
@@ -166,6 +197,38 @@ class PointCloud {
   NormalRef normal(size_t i) { return NormalRef{nx_[i], ny_[i], nz_[i]}; }
   NormalsView normals() { return NormalsView{this}; }
 
+  // label channel (nanopcl/core/point_cloud.hpp): what applyClusterLabels writes
+  bool hasLabel() const { return use_label_; }
+  void useLabel() { use_label_ = true; label_.resize(size(), Label()); }
+  std::vector<Label>& labels() { return label_; }
+  const std::vector<Label>& labels() const { return label_; }
+  Label& label(size_t i) { return label_[i]; }
+  const Label& label(size_t i) const { return label_[i]; }
+
+  // the listed points, in list order, with every channel this cloud carries and its metadata
+  // (core/impl/point_cloud_impl.hpp:176-216)
+  PointCloud extract(const std::vector<size_t>& idx) const {
+    PointCloud out;
+    out.frame_id_ = frame_id_;
+    out.timestamp_ns_ = timestamp_ns_;
+    if (use_intensity_) out.useIntensity();
+    if (use_color_) out.useColor();
+    if (use_normal_) out.useNormal();
+    if (use_cov_) out.useCovariance();
+    if (use_label_) out.useLabel();
+    out.resize(idx.size());
+    for (size_t k = 0; k < idx.size(); ++k) {
+      const size_t i = idx[k];
+      out.x_[k] = x_[i]; out.y_[k] = y_[i]; out.z_[k] = z_[i];
+      if (use_intensity_) out.intensity_[k] = intensity_[i];
+      if (use_color_) out.rgb_[k] = rgb_[i];
+      if (use_normal_) { out.nx_[k] = nx_[i]; out.ny_[k] = ny_[i]; out.nz_[k] = nz_[i]; }
+      if (use_cov_) for (size_t q = 0; q < 9; ++q) out.cov_[k * 9 + q] = cov_[i * 9 + q];
+      if (use_label_) out.label_[k] = label_[i];
+    }
+    return out;
+  }
+
   const std::string& frameId() const { return frame_id_; }
   void setFrameId(const std::string& id) { frame_id_ = id; }
   uint64_t timestamp() const { return timestamp_ns_; }
@@ -191,13 +254,14 @@ class PointCloud {
   HostVector<float> x_, y_, z_, intensity_, nx_, ny_, nz_;
   HostVector<uint32_t> rgb_;  // 0x00RRGGBB
   std::vector<float> cov_;
+  std::vector<Label> label_;
   std::string frame_id_;
   uint64_t timestamp_ns_ = 0;
-  bool use_intensity_ = false, use_color_ = false, use_cov_ = false, use_normal_ = false;
+  bool use_intensity_ = false, use_color_ = false, use_cov_ = false, use_normal_ = false, use_label_ = false;
 };
 
 }  // namespace nanopcl
 
 #include "nanopcl/geometry/normal_estimation.hpp"  // estimateNormals, estimateCovariances, estimateNormalsCovariances
 #include "nanopcl/registration.hpp"                // alignICP, alignPlaneICP, alignGICP
-#include "nanopcl/segmentation.hpp"                // segmentGround, segmentPlane, segmentMultiplePlanes
+#include "nanopcl/segmentation.hpp"                // segmentGround, segmentPlane(s), euclideanCluster, applyClusterLabels

@@ -33,12 +33,7 @@ struct Ring {
   explicit constexpr Ring(uint16_t v = 0) : val(v) {}
   constexpr operator uint16_t() const { return val; }
 };
-struct Label {
-  uint32_t val;
-  constexpr Label() : val(0) {}
-  explicit constexpr Label(uint32_t v) : val(v) {}
-  constexpr operator uint32_t() const { return val; }
-};
+// (Label, core/types.hpp, lives in nanopcl/core.hpp: the SoA cloud carries the channel too, for applyClusterLabels)
 inline double toSec(uint64_t ns) { return double(ns) * 1e-9; }
 inline uint64_t fromSec(double s) { return static_cast<uint64_t>(s * 1e9); }
 

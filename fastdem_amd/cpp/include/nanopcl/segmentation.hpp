@@ -5,10 +5,12 @@
 // order and the refined normal's sign included).  Names, signatures and defaults are the reference's.  PlaneModel's own
 // arithmetic (fromPoints, signedDistance, distance, isValid) runs on the host, in the order the header states.
 //
-// Not mirrored: euclideanCluster and applyClusterLabels — the clusters' order follows the iteration order of a voxel hash
-// and an unstable std::sort, which cannot be restated; the function is declared deleted so that a call fails at compile
-// time with its name.
+// euclideanCluster, ClusterConfig, ClusterResult and applyClusterLabels (segmentation/euclidean_cluster.hpp) over
+// fdm_cloud_cluster: the clusters are the reference's — the connected components of its radius relation, filtered by size —
+// in THIS PROJECT'S order: descending size, equal sizes by their smallest member's list position, members in ascending
+// list position (the reference's final std::sort read as a stable one; its BFS order inside a cluster is not reproduced).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -192,10 +194,98 @@ constexpr int kDevice = 0;
   return segmentGround(cloud, config);
 }
 
-// the reference's Euclidean clustering (euclidean_cluster.hpp): not provided — see the head of this file
-struct ClusterConfig;
-struct ClusterResult;
-ClusterResult euclideanCluster(const PointCloud& cloud, const ClusterConfig& config) = delete;
+// ---- Euclidean clustering (segmentation/euclidean_cluster.hpp) ----
+struct ClusterConfig {
+  float tolerance = 0.5f;    // distance threshold for neighbours
+  size_t min_size = 10;      // points a cluster has at least
+  size_t max_size = 100000;  // ... and at most: a larger component is dropped whole
+};
+
+struct ClusterResult {  // CSR: all clustered point indices, and where each cluster starts
+  std::vector<uint32_t> indices;
+  std::vector<uint32_t> offsets;  // [0, n0, n0 + n1, ...]
+
+  [[nodiscard]] size_t numClusters() const noexcept { return offsets.empty() ? 0 : offsets.size() - 1; }
+  [[nodiscard]] size_t clusterSize(size_t i) const noexcept { return offsets[i + 1] - offsets[i]; }
+  [[nodiscard]] size_t totalClusteredPoints() const noexcept { return indices.size(); }
+  [[nodiscard]] bool empty() const noexcept { return numClusters() == 0; }
+  [[nodiscard]] Span<const uint32_t> clusterIndices(size_t i) const {
+    return Span<const uint32_t>(indices.data() + offsets[i], offsets[i + 1] - offsets[i]);
+  }
+  // cluster i as a cloud of its own, every channel of `cloud` kept
+  [[nodiscard]] PointCloud extract(const PointCloud& cloud, size_t i) const {
+    const Span<const uint32_t> members = clusterIndices(i);
+    return cloud.extract(std::vector<size_t>(members.begin(), members.end()));
+  }
+  // the indices 0 .. total_points - 1 that are in no cluster, ascending
+  [[nodiscard]] std::vector<uint32_t> noiseIndices(size_t total_points) const {
+    std::vector<bool> clustered(total_points, false);
+    for (uint32_t idx : indices) clustered[idx] = true;
+    std::vector<uint32_t> noise;
+    noise.reserve(total_points - std::min(total_points, indices.size()));
+    for (size_t i = 0; i < total_points; ++i)
+      if (!clustered[i]) noise.push_back(static_cast<uint32_t>(i));
+    return noise;
+  }
+  [[nodiscard]] std::vector<size_t> clusterSizes() const {
+    std::vector<size_t> sizes(numClusters());
+    for (size_t i = 0; i < sizes.size(); ++i) sizes[i] = clusterSize(i);
+    return sizes;
+  }
+};
+
+namespace detail {
+// indices NULL: every point of the cloud, in order
+inline ClusterResult cluster(const PointCloud& cloud, const uint32_t* indices, size_t count, const ClusterConfig& config) {
+  ClusterResult result;
+  if (count == 0) {  // an empty cloud or list: one offset, no device call
+    result.offsets.push_back(0);
+    return result;
+  }
+  fdm_cluster_config c{};
+  c.tolerance = config.tolerance;
+  c.min_size = config.min_size;
+  c.max_size = config.max_size;
+  result.indices.resize(count);
+  result.offsets.resize(count + 1);
+  uint64_t n_clusters = 0;
+  const int rc = fdm_cloud_cluster(cloud.size(), cloud.xData(), cloud.yData(), cloud.zData(), 0, indices, count, &c,
+                                   kDevice, result.indices.data(), result.offsets.data(), nullptr, &n_clusters);
+  if (rc < 0) throw std::runtime_error(std::string("euclideanCluster: ") + fdm_last_error());
+  result.offsets.resize(n_clusters + 1);
+  result.indices.resize(result.offsets.back());
+  return result;
+}
+}  // namespace detail
+
+[[nodiscard]] inline ClusterResult euclideanCluster(const PointCloud& cloud, const ClusterConfig& config = ClusterConfig{}) {
+  return detail::cluster(cloud, nullptr, cloud.size(), config);
+}
+[[nodiscard]] inline ClusterResult euclideanCluster(const PointCloud& cloud, float tolerance, size_t min_size = 10,
+                                                    size_t max_size = 100000) {
+  return euclideanCluster(cloud, ClusterConfig{tolerance, min_size, max_size});
+}
+// over a subset of the cloud: the returned indices are the list's entries, i.e. they reference `cloud`
+[[nodiscard]] inline ClusterResult euclideanCluster(const PointCloud& cloud, const std::vector<uint32_t>& subset_indices,
+                                                    const ClusterConfig& config = ClusterConfig{}) {
+  return detail::cluster(cloud, subset_indices.data(), subset_indices.size(), config);
+}
+[[nodiscard]] inline ClusterResult euclideanCluster(const PointCloud& cloud, const std::vector<uint32_t>& subset_indices,
+                                                    float tolerance, size_t min_size = 10, size_t max_size = 100000) {
+  return euclideanCluster(cloud, subset_indices, ClusterConfig{tolerance, min_size, max_size});
+}
+
+// the Label channel from a clustering: instance id = cluster number + 1 (16 bits, truncated), 0 for noise; the semantic
+// class in the upper 16 bits.  Labels the cloud already has are overwritten.
+inline void applyClusterLabels(PointCloud& cloud, const ClusterResult& result, uint16_t semantic_class = 0) {
+  cloud.useLabel();
+  const uint32_t upper = static_cast<uint32_t>(semantic_class) << 16;
+  for (Label& l : cloud.labels()) l = Label(upper);
+  for (size_t k = 0; k < result.numClusters(); ++k) {
+    const Label mark(upper | static_cast<uint16_t>(k + 1));
+    for (uint32_t idx : result.clusterIndices(k)) cloud.labels()[idx] = mark;
+  }
+}
 
 }  // namespace segmentation
 }  // namespace nanopcl

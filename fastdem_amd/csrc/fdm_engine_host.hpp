@@ -50,6 +50,8 @@
 #include "fdm_register_host.hpp"
 #include "fdm_segment.hpp"
 #include "fdm_segment_host.hpp"
+#include "fdm_cluster.hpp"
+#include "fdm_cluster_host.hpp"
 
 using namespace fdm;
 

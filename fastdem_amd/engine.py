@@ -1248,3 +1248,100 @@ def segment_last_stats():
     _ck(capi.load().fdm_segment_last_stats(C.byref(st)))
     return {"n_batches": int(st.n_batches), "n_hypotheses": int(st.n_hypotheses),
             "n_invalid_samples": int(st.n_invalid_samples), "batch": int(st.batch), "ms": tuple(float(v) for v in st.ms)}
+
+
+# ---- Euclidean clustering (fdm_cloud_cluster: include/fdm_engine.h) ----
+class ClusterResult:
+    """nanopcl::segmentation::ClusterResult in CSR form: indices (every clustered point's index into the cloud, cluster
+    after cluster), offsets (num_clusters + 1 boundaries), and labels (per list position 0 = noise, else cluster number
+    + 1).  Kept clusters come in descending size, equal sizes by their smallest list position; inside a cluster the list
+    positions ascend.  uint32 numpy arrays for numpy input, int64 device tensors for torch device tensors."""
+
+    def __init__(self, indices, offsets, labels):
+        self.indices, self.offsets, self.labels = indices, offsets, labels
+
+    @property
+    def num_clusters(self):
+        return max(len(self.offsets) - 1, 0)
+
+    def __len__(self):
+        return self.num_clusters
+
+    @property
+    def total_clustered_points(self):
+        return len(self.indices)
+
+    def cluster_size(self, i):
+        return int(self.offsets[i + 1]) - int(self.offsets[i])
+
+    def cluster_indices(self, i):
+        """ClusterResult::clusterIndices(i): a view, no copy."""
+        return self.indices[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def cluster_sizes(self):
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def noise_indices(self, total):
+        """ClusterResult::noiseIndices(total_points): the indices 0 .. total - 1 in no cluster, ascending."""
+        if _is_torch(self.indices):
+            import torch
+            mask = torch.ones(int(total), dtype=torch.bool, device=self.indices.device)
+            mask[self.indices] = False
+            return torch.nonzero(mask).reshape(-1)
+        mask = np.ones(int(total), dtype=bool)
+        mask[self.indices] = False
+        return np.nonzero(mask)[0].astype(np.uint32)
+
+    def __repr__(self):
+        return f"ClusterResult(num_clusters={self.num_clusters}, total_clustered_points={self.total_clustered_points})"
+
+
+def euclidean_cluster(x, y, z, indices=None, tolerance=0.5, min_size=10, max_size=100000, device=0):
+    """nanopcl::segmentation::euclideanCluster on the device over the whole cloud or over `indices` (the values written
+    are then the list's entries, i.e. indices into the cloud; a duplicate entry counts as two points).  Returns a
+    ClusterResult; the relation and the order are stated in include/fdm_engine.h."""
+    lib = capi.load()
+    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
+    cfg = capi.FdmClusterConfig(float(np.float32(tolerance)), int(min_size), int(max_size))
+    p_idx, m, idx = None, n, None
+    if indices is not None:
+        if torch is not None:
+            idx = indices.to(device=keep[0].device, dtype=torch.int64).to(torch.int32).contiguous()
+            p_idx, m = _dptr(idx), idx.numel()
+        else:
+            idx = np.ascontiguousarray(np.asarray(indices).astype(np.uint32)).reshape(-1)
+            p_idx, m = _ptr(idx), idx.size
+    out, po = _seg_u32(torch, m, keep[0])
+    offsets, pf = _seg_u32(torch, m + 1, keep[0])
+    labels, pl = _seg_u32(torch, m, keep[0])
+    count = C.c_uint64(0)
+    _ck(lib.fdm_cloud_cluster(n, *ptrs, on_device, p_idx, m, C.byref(cfg), dev, po, pf, pl, C.byref(count)))
+    del idx
+    k = int(count.value)
+    off = _seg_take(torch, offsets, k + 1)
+    return ClusterResult(_seg_take(torch, out, int(off[k])), off, _seg_take(torch, labels, m))
+
+
+def apply_cluster_labels(result, total, semantic_class=0):
+    """nanopcl::segmentation::applyClusterLabels: the uint32 Label channel of a cloud of `total` points,
+    (semantic_class << 16) | uint16(cluster number + 1) for a clustered point — the instance id truncated to 16 bits as
+    in the reference — and (semantic_class << 16) for noise.  A numpy array."""
+    sem = np.uint32((int(semantic_class) & 0xFFFF) << 16)
+    out = np.full(int(total), sem, dtype=np.uint32)
+    ind = result.indices.cpu().numpy() if _is_torch(result.indices) else np.asarray(result.indices)
+    off = result.offsets.cpu().numpy() if _is_torch(result.offsets) else np.asarray(result.offsets)
+    if ind.size:
+        sizes = np.diff(off.astype(np.int64))
+        ids = (np.arange(sizes.size, dtype=np.int64) + 1) & 0xFFFF
+        out[ind.astype(np.int64)] = sem | np.repeat(ids, sizes).astype(np.uint32)
+    return out
+
+
+def cluster_last_stats():
+    """What this thread's last euclidean_cluster did: the counts of fdm_cluster_stats and ms (zeros unless
+    fdm_cloud_debug_profile is on)."""
+    st = capi.FdmClusterStats()
+    _ck(capi.load().fdm_cluster_last_stats(C.byref(st)))
+    out = {k: int(getattr(st, k)) for k, _ in capi.FdmClusterStats._fields_ if k != "ms"}
+    out["ms"] = tuple(float(v) for v in st.ms)
+    return out

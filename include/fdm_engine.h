@@ -743,8 +743,7 @@ int fdm_register_last_stats(fdm_register_stats* out);
  * segmentPlane / segmentMultiplePlanes (RANSAC; segmentation/impl/ransac_plane_impl.hpp:29-405) ----
  * Engine-free and synchronous, on `device`; host arrays (on_device 0) or device arrays, the outputs where the inputs
  * are; counts and results are host words.  The thread's current device is put back before a call returns.  All fp32
- * arithmetic is done without contraction.  euclideanCluster is not offered: its output order follows a hash map's
- * iteration order and an unstable sort.
+ * arithmetic is done without contraction.  euclideanCluster: fdm_cloud_cluster, below.
  *
  * SEGMENT GROUND (:68-112).  A point's cell is gx = int(floor(x / grid_resolution)), gy likewise: a correctly rounded
  * fp32 DIVISION (:33-34), not a product with a reciprocal.  A cell of fewer than min_points_per_cell points is
@@ -833,6 +832,63 @@ typedef struct fdm_segment_stats {  /* the calling thread's last segmentation ca
   float ms[4];
 } fdm_segment_stats;
 int fdm_segment_last_stats(fdm_segment_stats* out);
+
+/* ---- Euclidean clustering: nanopcl::segmentation::euclideanCluster (segmentation/impl/euclidean_cluster_impl.hpp:89-225
+ * over search/impl/voxel_hash_impl.hpp:118-161 and core/voxel.hpp:28-80) ----
+ * Engine-free and synchronous like the segmentation calls; host arrays (on_device 0) or device arrays, the outputs
+ * where the cloud is; *n_clusters is a host word.  The list is `indices` (n_indices entries) or, for NULL, every point in
+ * order; m = its length.  A "position" is a position in the list; a duplicate entry is two points.
+ * THE RELATION, restated exactly.  inv = 1.0f / tolerance, range = int(ceil(tolerance * inv)) (1 for every tolerance
+ * tried; 2 is handled), r_sq = tolerance * tolerance, in fp32.  A point's voxel is floor(c * inv) per axis: the fp32
+ * PRODUCT, not segment_ground's division.  Two listed points are neighbours iff their voxels differ by at most `range`
+ * on every axis (part of the relation: the voxels the reference's radius search visits) and dist_sq <= r_sq, where
+ * dist_sq = dx*dx + (dy*dy + dz*dz) of the fp32 differences, without contraction: the three-term order of DESIGN.md §6,
+ * FIXED here (the reference's is its compiler's).  The clusters are the connected components of that relation; a
+ * component is kept iff min_size <= size <= max_size (an oversized one is dropped whole).
+ * THE ORDER, this project's definition: kept clusters in descending size, clusters of equal size by their smallest
+ * position ascending; inside a cluster ascending position.  The reference takes its seeds in ascending index, so its
+ * clusters exist in ascending order of their smallest member before its final std::sort by size: this is that sort read
+ * as a STABLE one.  (The reference's order inside a cluster is its BFS order over hash chains; it is not reproduced.)
+ * The sequence of sizes equals the reference's, every cluster equals a reference cluster as a set, and a cluster's
+ * first element is the reference's seed.
+ * OUTPUT: CSR.  cluster_indices (capacity m) holds the list's ENTRIES — indices into the cloud — cluster after cluster;
+ * offsets (capacity m + 1) holds n_clusters + 1 words, offsets[0] = 0; labels (NULL, or capacity m) gets per position 0
+ * (in no kept cluster) or its cluster's number + 1.  m == 0: FDM_OK, *n_clusters = 0, offsets[0] = 0.
+ * FDM_ERR_INVALID, with the outputs untouched: a listed coordinate that is not finite (the reference casts it to int);
+ * a voxel coordinate outside [-2^20 + range, 2^20 - 1 - range] (the reference clamps it: its table degenerates); a
+ * tolerance that is <= 0, NaN or infinite, or whose range is not 1 or 2; an entry >= n (found by a pass that reads the
+ * list alone, before any kernel addresses with an entry); n >= 2^32; m >= 2^32 - 4097; a null x, y, z, offsets or (m > 0)
+ * cluster_indices; MORE THAN 1.5e11 CANDIDATE PAIRS — the sum over the points of the points at a lower sorted position in
+ * the voxels they search, which is the work of the merge as it is of the reference's search: a voxel of c points costs
+ * c^2 / 2.  The bound is 0.6 - 1.1 s of the MI355X (measured: profiles/r13/cluster/README.md); the call returns instead
+ * of running for longer.  No kernel of this call waits on another block, and every loop of its union-find is counted: a find
+ * that does not end within m steps or a unite that loses its swap 4096 times returns FDM_ERR_HIP with its message. */
+typedef struct fdm_cluster_config {  /* ClusterConfig (segmentation/euclidean_cluster.hpp), field for field */
+  float tolerance;                   /* 0.5 */
+  uint64_t min_size;                 /* 10 */
+  uint64_t max_size;                 /* 100000 */
+} fdm_cluster_config;
+/* cfg NULL = the defaults */
+int fdm_cloud_cluster(uint64_t n, const float* x, const float* y, const float* z, int on_device,
+                      const uint32_t* indices, uint64_t n_indices, const fdm_cluster_config* cfg, int device,
+                      uint32_t* cluster_indices, uint32_t* offsets, uint32_t* labels, uint64_t* n_clusters);
+typedef struct fdm_cluster_stats {   /* the calling thread's last fdm_cloud_cluster */
+  uint64_t n_points;                 /* m */
+  uint64_t n_components;             /* connected components; n_kept + n_rejected */
+  uint64_t n_kept;                   /* = *n_clusters */
+  uint64_t n_rejected;               /* below min_size or above max_size */
+  uint64_t n_clustered;              /* points in kept clusters */
+  uint64_t candidate_pairs;          /* the work bound's measure */
+  uint64_t tests;                    /* distance tests made: every candidate pair once */
+  uint64_t neighbour_pairs;          /* of them within the tolerance */
+  uint64_t unions;                   /* links made: n_points - n_components */
+  int32_t range;
+  uint32_t key_bits;                 /* of the voxel key over the bounding box */
+  /* device ms while fdm_cloud_debug_profile (fdm_engine_debug.h) is on, zeros otherwise: checks and voxels; keys, sort
+   * and gather; candidate intervals; merge; roots, sizes and the kept positions; ordering sort, offsets, indices, labels */
+  float ms[6];
+} fdm_cluster_stats;
+int fdm_cluster_last_stats(fdm_cluster_stats* out);
 
 typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
   float resolution;
