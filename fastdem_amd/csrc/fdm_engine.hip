@@ -386,7 +386,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const ScanInputs& in,
   e->S.ras_z = nullptr;
   e->S.cap_drop_nan = ray_on ? 1 : 0;
   // (a scan with raycasting and nothing else optional is held back like a plain one: its stage runs behind its update)
-  const bool ray_held = ray_on && e->opt.ray_hold && e->opt.overlap && e->key2[1] && !e->cap_pre && !e->cap_ras;
+  const bool ray_held = ray_on && e->opt.overlap && e->key2[1] && !e->cap_pre && !e->cap_ras;
   if (ray_held && n) {
     if (n > e->rcap_cap) {
       if (int rc_sync = sync_all(e)) return rc_sync;
@@ -458,7 +458,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const ScanInputs& in,
   // ordinary stream contract.  (The tiled pipeline never looks at a scan twice.)
   if (gather && (!gather->x || !n)) gather = nullptr;
   ScanInputs slot_gather;
-  if (!tiled && plain && !gather && n && !in_engine_slot && !e->opt.borrow_inputs) {
+  if (!tiled && plain && !gather && n && !in_engine_slot) {
     StageSlot slot;
     if ((rc = next_stage_slot(e, n, &slot))) return rc;
     slot_gather = slot.as_gather();
@@ -498,16 +498,13 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const ScanInputs& in,
   if (tiled && (rc = ensure_tile_pool(e, size_t(bin_blocks) * per_block, bin_blocks))) return rc;
   e->last_bin_blocks = bin_blocks;
   e->last_bin_part = e->S.bin_part;
-  P.dbg_no_atomics = e->opt.dbg_no_atomics;
-  P.bin_table = e->opt.bin_table;
-  P.dbg_upd = e->opt.dbg_upd;
   P.move_basic = e->opt.move_clear_basic;
   P.drop_nonfinite = e->next_drop_nonfinite;
   e->next_drop_nonfinite = 0;
   int32_t* ids = e->want_ids ? e->d_cell_ids : nullptr;
   // a scan that asks for nothing optional takes the LEAN bin body (fdm_kernels.hpp)
   // (2: lean, but x / y / z written through for the held-back update's gather)
-  const int lean = (ids || e->S.cap_x || P.drop_nonfinite || P.dbg_no_atomics) ? 0 : (e->S.wt_x ? 2 : 1);
+  const int lean = (ids || e->S.cap_x || P.drop_nonfinite) ? 0 : (e->S.wt_x ? 2 : 1);
   const fdm_engine::BinVariant bv{use_bin4, P.has_intensity != 0, P.has_color != 0, e->opt.wave_merge != 0, bin_threads, lean};
   // a held-back update leaves now: fused with this bin if the two belong to the same pipeline and
   // this scan is a plain one, alone otherwise
@@ -574,7 +571,7 @@ int enqueue_scan(fdm_engine* e, ScanParams& P, uint64_t n, const ScanInputs& in,
   u.in = gather ? ScanInputs{gather->x, gather->y, gather->z, nullptr, in.rgb ? gather->rgb : nullptr,
                              in.var ? gather->var : nullptr}
                 : in;
-  u.upd_blocks = e->n_tiles;
+  u.n_upd_blocks = e->n_tiles;
   if (tiled) {
     u.Q = e->pool[parity];
     u.A = TileAux{e->tile_stamp32, e->upd_part32, e->S.ras_z, e->d_timeline};
@@ -758,13 +755,14 @@ int read_stats(fdm_engine* e, fdm_scan_stats* out, int* status) {
     // what a synchronous integrate() of a VLP-16 scan takes end to end).
     bool seen = false;
     // (a scan of more than ~100 K points keeps the device busy for longer than the poll window: sleep at once)
-    if (e->opt.sync_spin_us > 0 && e->last_n <= 131072u && e->last_kind != 1) {
+    constexpr int kSyncSpinUs = 150;  // how long the pinned block is polled before the stream wait
+    if (e->last_n <= 131072u && e->last_kind != 1) {
       const auto t0 = std::chrono::steady_clock::now();
       const volatile unsigned long long* const w = &e->h_stats->seq;
       for (;;) {
         if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == e->stats_seq) { seen = true; break; }
         if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >
-            e->opt.sync_spin_us)
+            kSyncSpinUs)
           break;
       }
     }

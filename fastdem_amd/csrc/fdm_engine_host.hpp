@@ -97,32 +97,17 @@ const char* const kP2N[5] = {"_p2_n0", "_p2_n1", "_p2_n2", "_p2_n3", "_p2_n4"};
 struct EngineOptions {
   // ---- the scan path ----
   int wave_merge = 1;               // option "wave_merge": k_bin merges same-cell runs inside the wavefront before the atomics
-  int bin_table = 1;                 // k_bin: per-block LDS cell table (option "bin_table")
   int bin_variant = 0;  // 0 = by scan size, 4 = k_bin4 (LDS-staged), 1 = k_bin (one point/thread)
   int overlap = 1;                  // option "overlap": the update of a plain scan is held back and leaves with the next scan's bin half (enqueue_scan)
-  int borrow_inputs = 0;             // option "borrow_inputs": a held-back update gathers from the CALLER's device arrays
-                                    // (1: device arrays of enqueue-only scans stay untouched by the caller until the NEXT-BUT-ONE
-                                    // scan is enqueued, or a flush: no staging copy)
   // fdm_engine_integrate_async: scans of up to this many points whose arrays are PINNED host memory
   // are read in place by the bin kernel (0 = always stage with copy commands; option "zero_copy")
   int zero_copy = 1 << 30;
-  int sync_spin_us = 150;           // read_stats polls the pinned block this long before a stream wait (option)
   int records = 1;                  // option "records": pack the active estimator's state into cell records (1, default) or one array per layer (0)
   int move_clear_basic = 0;         // option "move_clear_basic": GridMap::move()'s strips clear {elevation, elevation_min, elevation_max} only (the other reading of nanoGrid: DESIGN.md §6); such an engine takes no batch launches
   // ---- the large-scan (tiled) pipeline ----
   int tiled = 1;                    // option "tiled": large scans go through per-tile record pools
   int tiled_min = 2048;             // ... from this many points up (on a map of >= 512 tiles the pipeline wins at every
                                     // size measured: 2 K points 13.1 vs 14.6 us, 32 K 16.6 vs 20.5, 262 K 18.9 vs 34.3)
-  int upd_blocks = 768;             // option "upd_blocks": update blocks (four tile wavefronts each) of a FUSED launch
-  int upd_blocks_alone = 2048;      // option "upd_blocks_alone": ... of an update launch of its own
-  int upd_prio = 1;                 // option "upd_prio": update wavefronts run at raised issue priority
-  int tiled_lds_pad = -1;           // option "tiled_lds_pad": extra dynamic LDS per block of the large-scan bin / fused launches; -1 = as much as
-                                    // makes it SIX blocks per CU (seven: configs[3] 32.3 -> 31.8 us at six; five — what the fixed 4 KB of round 5
-                                    // came to for a scan with an intensity channel, 29.7 KB per block — 31.4 -> 30.3 us at six, profiles/r06/probe_l.json)
-  int cnt_shift = 5;                // option "cnt_shift": one tile counter per 2^cnt_shift words (TilePool::cnt_shift); takes effect before the pools exist
-  int bin_delay = 0;                // option "bin_delay": see TileWork::delay (measurement: profiles/r06/probe_delay.json)
-  int bin_delay_blocks = 1024;      // option "bin_delay_blocks"
-  int bin_stagger = 0;              // option "bin_stagger": start stagger of the fused launch's first-round bin blocks (TileWork::stagger)
   // ---- the batch pipeline ----
   int batch = 1;                     // option "batch": fdm_engine_integrate_device_batch groups eligible scans
   int batch_max = 0;                 // option "batch_max": scans per launch (2 .. kMaxBatch = 32); 0 = automatic: 32 with the quantile
@@ -137,7 +122,6 @@ struct EngineOptions {
   int batch_ray_seg = 4;             // option "batch_ray_seg": lanes per ray of k_rb_ray (1, 4, 8, 16)
   int batch_ray_lds = 1;             // option "batch_ray_lds": 0 = always the global-atomic walk (k_rb_ray)
   int batch_ray_parts = 0;           // option "batch_ray_parts": workgroups per quadrant and scan of k_rb_ray_lds (0 = fill the chip)
-  int batch_ray_words = 0;           // option "batch_ray_words": LDS image words of k_rb_ray_lds (0 = twice a centred sensor's quadrant)
   // ---- the raycasting stage ----
   int voxel_small = 1;               // option "voxel_small": scans of <= 64 K points take the sort-free voxel filter
   int voxel_small_max = 1 << 16;     // option "voxel_small_max": largest scan that takes it
@@ -145,14 +129,12 @@ struct EngineOptions {
   // std::sort leaves (fdm_introsort.hpp), so VoxelMode::ANY picks what a g++ build of the reference picks.  While it is
   // on, the sort-free small-scan filter is not used and batch calls with raycasting go scan by scan (multi_run)
   int voxel_any_order = 0;
-  int ray_hold = 1;                  // option "ray_hold": the stage of a plain scan is held back with the scan's update and runs right behind it
   // scans from this many points up: bucketed ray queue, one lane per ray (option "ray_large_min").  Stage time, shared-
   // ray segments vs this path: 131 K points 0.48 vs 0.52 ms, 262 K 0.78 vs 0.57, 524 K 1.17 vs 0.67, RGB-D 272 K 0.23 vs 0.19
   int ray_large_min = 196608;
   // large scans: the walk keeps an angular sector's minimum-height image in LDS (option "ray_wedge", fdm_raywedge.hpp;
   // 0 = one lane per ray on memory-side atomics, k_ray<., 1>)
   int ray_wedge = 1;
-  int ray_wedge_parts = 0;           // option "ray_wedge_parts": workgroups per sector (0 = by the scan's size)
   // two stages in flight (option "ray_overlap", fdm_engine_ray.inl): the map-independent part of a large scan's stage
   // (voxel filter, queue, walk) leaves on a stream of its own as soon as the scan's bin half has been launched, by scan
   // parity; k_ray_resolve stays behind the scan's update on the main stream
@@ -165,11 +147,8 @@ struct EngineOptions {
                                      // more than that (bench.py by the time of its large raycasting leg) the three streams of a stage
                                      // share queues and the events serialise them: 339 -> 365 us (profiles/r06/ray_overlap_ab.txt)
   // ---- measurement only ----
-  int dbg_no_atomics = 0;            // option "dbg_no_atomics": results are wrong when set
-  int dbg_upd = 0;                   // option "dbg_upd" (ScanParams::dbg_upd)
   int dbg_batch = 0;                 // measurement only (option "dbg_batch")
   int dbg_ray = 0;                   // option "dbg_ray": bit switches of the raycasting stage (RayParams::dbg)
-  int dbg_post = 0;                  // measurement only: 1 = untiled feature kernel, 32 = fusion with integer samples, 64 = features with min / max chains
 };
 
 // Everything ONE raycasting stage in flight writes, and what orders its uses (fdm_engine_ray.inl).  Every helper of the
@@ -262,7 +241,7 @@ struct fdm_engine {
   bool cap_cov = false;                   // ... the preprocessed cloud with its 3x3 covariance channel
   float* d_cap = nullptr;            // 4 channels x cap_cap points
   size_t cap_cap = 0;
-  // the preprocessed cloud of a scan whose raycasting stage is HELD BACK with its update (option "ray_hold"): by scan
+  // the preprocessed cloud of a scan whose raycasting stage is HELD BACK with its update (enqueue_scan's ray_held): by scan
   // parity — the next scan's bin half writes its own while the stage of this one has not run yet; 3 channels x rcap_cap
   float* d_rcap[2] = {nullptr, nullptr};
   size_t rcap_cap = 0;
@@ -303,7 +282,7 @@ struct fdm_engine {
     ScanInputs in;          // scratch pipeline: where the winning points are gathered from
     TilePool Q;             // tiled pipeline: the record pool of the scan's parity
     TileAux A;
-    unsigned upd_blocks = 0;
+    unsigned n_upd_blocks = 0;
     // the scan's raycasting stage (fastdem.cpp:152-159), which runs right behind this update wherever that is launched
     bool ray = false;
     int ray_pre = 0;        // 1 + bank if the stage's first part already left on that bank's stream (ray_overlap)

@@ -9,11 +9,11 @@ int launch_update_alone(fdm_engine* e, const fdm_engine::PendingUpdate& u) {
   return with_policy(e, [&](auto tag, const auto& layers) -> int {
     using POLICY = decltype(tag);
     if (u.S.dense) {
-      hipLaunchKernelGGL(k_update<POLICY>, dim3(u.upd_blocks), dim3(256), 0, e->stream, u.P, e->G, e->d_state, layers,
+      hipLaunchKernelGGL(k_update<POLICY>, dim3(u.n_upd_blocks), dim3(256), 0, e->stream, u.P, e->G, e->d_state, layers,
                          e->d_layer_ptrs, e->n_layer_ptrs, u.S, u.in.x, u.in.y, u.in.z, u.in.intensity, u.in.rgb,
                          u.in.var, unsigned(e->ncell));
     } else {  // stamp-gated: kStampTiles tiles per block, idle tiles cost one scalar load
-      hipLaunchKernelGGL(k_update_stamped<POLICY>, dim3((u.upd_blocks + kStampTiles - 1) / kStampTiles), dim3(256), 0,
+      hipLaunchKernelGGL(k_update_stamped<POLICY>, dim3((u.n_upd_blocks + kStampTiles - 1) / kStampTiles), dim3(256), 0,
                          e->stream, u.P, e->G, e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs, u.S, u.in.x,
                          u.in.y, u.in.z, u.in.intensity, u.in.rgb, u.in.var, unsigned(e->ncell));
     }
@@ -34,7 +34,7 @@ int launch_update_fused(fdm_engine* e, const fdm_engine::PendingUpdate& u, const
     auto go = [&](auto kern, unsigned threads) {
       // tiles per update block: threads / 256, times kStampTiles slots on stamp-gated maps
       const unsigned per = (threads / 256u) * (u.S.dense ? 1u : kStampTiles);
-      const unsigned ub = (u.upd_blocks + per - 1u) / per;
+      const unsigned ub = (u.n_upd_blocks + per - 1u) / per;
       hipLaunchKernelGGL(kern, dim3(ub + bin_blocks_b), dim3(threads), 0, e->stream, u.P, e->G, e->d_state, layers,
                          e->d_layer_ptrs, e->n_layer_ptrs, u.S, u.in, unsigned(e->ncell), ub, Pb, Sb, Ib, ids_b);
     };

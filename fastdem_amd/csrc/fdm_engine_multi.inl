@@ -26,7 +26,7 @@ uint32_t multi_run(fdm_engine* e, uint32_t count, const fdm_device_scan* scans) 
   }
   poll_dense_paid(e);
   if (e->obst_dense_pending || e->last_kind == 1 || e->next_drop_nonfinite) return 0u;
-  if (e->opt.dbg_no_atomics || e->opt.dbg_upd || e->opt.move_clear_basic) return 0u;
+  if (e->opt.move_clear_basic) return 0u;
   const fdm_device_scan& f = scans[0];
   const size_t kt = e->ncell / 1024u;  // (the thresholds below were measured in units of 1 024 cells, round 2)
   uint32_t run = 0;
@@ -191,7 +191,7 @@ int launch_rbatch(fdm_engine* e, const RBatch& R) {
     // (LDS for twice a centred sensor's quadrant — a LOCAL map follows the robot, a GLOBAL map's sensor may wander: a
     // larger quadrant takes the kernel's global-atomic loop — or for the whole map when that is less)
     const unsigned words = unsigned(std::min<size_t>({size_t(e->rb_lds_words), size_t(e->G.rows) * size_t(e->G.cols),
-                                                      e->opt.batch_ray_words > 0 ? size_t(e->opt.batch_ray_words) : quadrant * 2}));
+                                                      quadrant * 2}));
     if (e->opt.dbg_ray & (1 << 20))  // (dbg_ray 1048576, measurement only: the integer image of round 4)
       hipLaunchKernelGGL(k_rb_ray_lds<false>, dim3(4u * parts, R.count), dim3(kRbRayThreads), words * sizeof(uint32_t),
                          e->stream, R, e->G, parts, words);
@@ -323,7 +323,6 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   K.do_move = P.do_move;
   K.gate_on_filter = P.gate_on_filter;
   K.has_var = hv ? 1 : 0;
-  K.bin_table = e->opt.bin_table;
   K.dbg = e->opt.dbg_batch;
   // the chain of moves walked one launch ahead (mwalk_body): automatic = every scan of a quantile-estimator batch; for
   // Kalman without the ray stage only the scans from kKalmanWalkFrom on (the longest chains) — the earlier rows walk their

@@ -136,7 +136,7 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2) {
   return FDM_OK;
 }
 
-// ---- fdm_engine_set_option: one table (kOptions), one lookup-and-apply routine, five hooks ----
+// ---- fdm_engine_set_option: one table (kOptions), one lookup-and-apply routine, four hooks ----
 // What a row accepts and how the value is normalised before it is stored.
 struct OptRule {
   enum Kind { kBool, kRaw, kAtLeast, kRange, kOneOf } kind;
@@ -179,9 +179,6 @@ static int opt_tiled_min(fdm_engine* e, int) {  // set by hand: no map-size cond
   e->tiled_forced = true;
   return FDM_OK;
 }
-static int opt_cnt_shift(fdm_engine* e, int) {
-  return e->pool[0].cnt ? fail(FDM_ERR_INVALID, "cnt_shift: the record pools exist already") : FDM_OK;
-}
 
 struct OptionRow {
   const char* name;
@@ -195,26 +192,15 @@ struct OptionRow {
 static const OptionRow kOptions[] = {
   // the scan path
   {"wave_merge", &EngineOptions::wave_merge, opt_bool(), false, nullptr},
-  {"bin_table", &EngineOptions::bin_table, opt_bool(), false, nullptr},
   {"bin_variant", &EngineOptions::bin_variant, opt_one_of(1 | 2 | 16, "0, 1 or 4"), false, nullptr},
   {"overlap", &EngineOptions::overlap, opt_bool(), false, nullptr},
-  {"borrow_inputs", &EngineOptions::borrow_inputs, opt_bool(), false, nullptr},
   {"zero_copy", &EngineOptions::zero_copy, opt_range(0, kAnyCount, "a point count (0 = off)"), false, nullptr},
-  {"sync_spin_us", &EngineOptions::sync_spin_us, opt_at_least(0), false, nullptr},
   {"records", &EngineOptions::records, opt_bool(), false, opt_records},
   {"dense", nullptr, opt_bool(), false, opt_dense},
   {"move_clear_basic", &EngineOptions::move_clear_basic, opt_bool(), true, nullptr},
   // the large-scan pipeline
   {"tiled", &EngineOptions::tiled, opt_bool(), false, nullptr},
   {"tiled_min", &EngineOptions::tiled_min, opt_range(0, kAnyCount, "a point count"), false, opt_tiled_min},
-  {"upd_blocks", &EngineOptions::upd_blocks, opt_range(1, 65535, "1 .. 65535"), true, nullptr},
-  {"upd_blocks_alone", &EngineOptions::upd_blocks_alone, opt_range(1, 65535, "1 .. 65535"), true, nullptr},
-  {"upd_prio", &EngineOptions::upd_prio, opt_bool(), false, nullptr},
-  {"tiled_lds_pad", &EngineOptions::tiled_lds_pad, opt_range(-1, 120 * 1024, "-1 (automatic) or 0 .. 122880 bytes"), false, nullptr},
-  {"cnt_shift", &EngineOptions::cnt_shift, opt_range(0, 5, "0 .. 5"), false, opt_cnt_shift},
-  {"bin_delay", &EngineOptions::bin_delay, opt_range(0, 65535, "0 .. 65535"), false, nullptr},
-  {"bin_delay_blocks", &EngineOptions::bin_delay_blocks, opt_range(0, 65535, "0 .. 65535"), false, nullptr},
-  {"bin_stagger", &EngineOptions::bin_stagger, opt_range(0, 64, "0 .. 64"), false, nullptr},
   // the batch pipeline
   {"batch", &EngineOptions::batch, opt_bool(), false, nullptr},
   {"batch_max", &EngineOptions::batch_max, opt_one_of(1 | bits(2, kMaxBatch), "0 (automatic) or 2 .. 32 scans per launch"), false, nullptr},
@@ -225,24 +211,18 @@ static const OptionRow kOptions[] = {
   {"batch_ray_seg", &EngineOptions::batch_ray_seg, opt_one_of(bits(1, 1) | bits(4, 4) | bits(8, 8) | bits(16, 16), "1, 4, 8 or 16 lanes per ray"), false, nullptr},
   {"batch_ray_lds", &EngineOptions::batch_ray_lds, opt_bool(), false, nullptr},
   {"batch_ray_parts", &EngineOptions::batch_ray_parts, opt_range(0, 64, "0 (automatic) .. 64"), false, nullptr},
-  {"batch_ray_words", &EngineOptions::batch_ray_words, opt_range(0, kAnyCount, ">= 0"), false, nullptr},
-  // the raycasting stage.  (Its options are read when a scan's stage is LAUNCHED; under ray_hold the previous scan's stage
+  // the raycasting stage.  (Its options are read when a scan's stage is LAUNCHED; a held-back stage of the previous scan
   // may still be pending: the join every option starts with sends it off first, so that a switch never lands in the scan
   // before it — results are the same either way, A/B timings are attributed to the right scan)
   {"voxel_small", &EngineOptions::voxel_small, opt_bool(), false, nullptr},
   {"voxel_small_max", &EngineOptions::voxel_small_max, opt_range(1, 1 << 20, "1 .. 2^20 points"), false, nullptr},
   {"voxel_any_order", &EngineOptions::voxel_any_order, opt_range(0, 1, "0 (stable), 1 (std::sort)"), true, nullptr},
-  {"ray_hold", &EngineOptions::ray_hold, opt_bool(), false, nullptr},
   {"ray_large_min", &EngineOptions::ray_large_min, opt_at_least(1), false, nullptr},
   {"ray_wedge", &EngineOptions::ray_wedge, opt_bool(), false, nullptr},
-  {"ray_wedge_parts", &EngineOptions::ray_wedge_parts, opt_range(0, 16, "0 .. 16"), false, nullptr},
   {"ray_overlap", &EngineOptions::ray_overlap, opt_range(-1, 1, "-1 (automatic), 0, 1"), true, nullptr},
   // measurement only
-  {"dbg_no_atomics", &EngineOptions::dbg_no_atomics, opt_raw(), false, nullptr},
-  {"dbg_upd", &EngineOptions::dbg_upd, opt_raw(), false, nullptr},
   {"dbg_batch", &EngineOptions::dbg_batch, opt_raw(), false, nullptr},
   {"dbg_ray", &EngineOptions::dbg_ray, opt_raw(), false, nullptr},
-  {"dbg_post", &EngineOptions::dbg_post, opt_raw(), false, nullptr},
   {"dbg_timeline", nullptr, opt_raw(), true, opt_dbg_timeline},
 };
 

@@ -103,13 +103,8 @@ int fdm_engine_apply_inpainting(fdm_engine* e, int max_iterations, int min_valid
   }
   bool in_layer = start_in_layer;
   for (int it = 0; it < iters; ++it) {
-    if (e->opt.dbg_post & 4)
-      hipLaunchKernelGGL(FDM_POST_KERNEL(k_inpaint_pass), dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
-                         in_layer ? A : B, in_layer ? As : 1, in_layer ? B : A, in_layer ? 1 : As, min_valid,
-                         unsigned(e->ncell));
-    else
-      hipLaunchKernelGGL(FDM_POST_KERNEL(k_inpaint_pass_tiled), dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
-                         in_layer ? A : B, in_layer ? As : 1, in_layer ? B : A, in_layer ? 1 : As, min_valid);
+    hipLaunchKernelGGL(FDM_POST_KERNEL(k_inpaint_pass_tiled), dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state, slot,
+                       in_layer ? A : B, in_layer ? As : 1, in_layer ? B : A, in_layer ? 1 : As, min_valid);
     in_layer = !in_layer;
   }
   HIPCK(hipGetLastError());
@@ -131,17 +126,14 @@ int fdm_engine_apply_spatial_smoothing(fdm_engine* e, const char* layer, int ker
   if (!l || l->pending) return FDM_OK;  // spatial_smoothing.hpp:42
   if ((rc = ensure_tmp(e))) return rc;
   if ((rc = copy_strided(e, e->d_tmp, 1, lptr(e, *l), lstride(e, *l)))) return rc;  // the double buffer
-  if (kernel_size == 3 && !(e->opt.dbg_post & 4))
+  if (kernel_size == 3)
     hipLaunchKernelGGL(FDM_POST_KERNEL(k_median3_tiled), dim3(tile3_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), min_valid);
-  else if (kernel_size == 3)
-    hipLaunchKernelGGL(FDM_POST_KERNEL(k_median3), dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
-                       int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), min_valid, unsigned(e->ncell));
   else if ((2 * (kernel_size / 2) + 1) * (2 * (kernel_size / 2) + 1) <= kMaxRegion)
     hipLaunchKernelGGL(FDM_POST_KERNEL(k_median), dim3(cell_blocks(e)), dim3(256), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_tmp, lptr(e, *l), lstride(e, *l), kernel_size, min_valid,
                        unsigned(e->ncell));
-  else if (median_sel_lds_bytes(kernel_size) <= 160u * 1024u && !(e->opt.dbg_post & 8)) {
+  else if (median_sel_lds_bytes(kernel_size) <= 160u * 1024u) {
     // selection by bisection on an LDS tile (fdm_post.hpp k_median_sel): every window up to ~175 x 175
     const unsigned lds = median_sel_lds_bytes(kernel_size);
     if ((rc = allow_lds(k_median_sel, lds))) return rc;
@@ -194,12 +186,11 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
   F.q_upper = cfg->quantile_upper;
   F.min_valid = cfg->min_valid_neighbors;
   F.n_entries = int(reg.size());
-  const unsigned fblocks = unsigned((e->ncell + kFusionThreads - 1) / kFusionThreads);
   int halo = 0;
   for (const RegionEntry& r : reg) halo = std::max(halo, std::max(std::abs(r.dr), std::abs(r.dc)));
   const auto q_ok = [](float q) { return q >= 1e-6f && q <= 1.0f; };  // (k_fusion_f64_tiled's walk: a positive target within the total)
-  if (reg.size() <= 29 && halo <= kFusHaloMax && !(e->opt.dbg_ray & 1024) && !(e->opt.dbg_post & (2 | 32)) && q_ok(F.q_lower) &&
-      q_ok(F.q_upper)) {  // (a disc of a radius has 1, 5, 9, 13, 21, 25, 29, 37 .. cells: nothing between 29 and 32)
+  if (reg.size() <= 29 && halo <= kFusHaloMax && q_ok(F.q_lower) && q_ok(F.q_upper)) {
+    // (a disc of a radius has 1, 5, 9, 13, 21, 25, 29, 37 .. cells: nothing between 29 and 32)
     // samples as doubles sorted by v_min_f64 / v_max_f64 (the default radius: 29 cells), neighbourhood staged in LDS
     const unsigned tblocks = unsigned((e->G.s_rows + kFusTileR - 1) / kFusTileR) *
                              unsigned((e->G.s_cols + kFusTileC - 1) / kFusTileC);
@@ -209,8 +200,8 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
                          lptr(e, *lo), lstride(e, *lo));
     };
     // one instantiation per disc size there is below 30 cells (the sorting network shrinks with it: 171 exchanges for 29
-    // samples, 19 for the 9 of the shipped 0.15 m on a 0.1 m map); dbg_post 128: the 29-slot kernel with branches
-    const size_t nreg = (e->opt.dbg_post & 128) ? 0 : reg.size();
+    // samples, 19 for the 9 of the shipped 0.15 m on a 0.1 m map); a disc of one cell: the 29-slot kernel with branches
+    const size_t nreg = reg.size();
     if (nreg == 29) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<29, true>));
     else if (nreg == 25) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<25, true>));
     else if (nreg == 21) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<21, true>));
@@ -218,18 +209,14 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
     else if (nreg == 9) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<9, true>));
     else if (nreg == 5) launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<5, true>));
     else launch_f64(FDM_POST_KERNEL(k_fusion_f64_tiled<29, false>));
-  } else if (reg.size() <= 32 && halo <= kFusHaloMax && !(e->opt.dbg_ray & 1024) && !(e->opt.dbg_post & 2)) {
+  } else if (reg.size() <= 32 && halo <= kFusHaloMax) {
     // samples as 64-bit integers sorted in registers, neighbourhood staged in LDS (round 2; any quantile)
     const unsigned tblocks = unsigned((e->G.s_rows + kFusTileR - 1) / kFusTileR) *
                              unsigned((e->G.s_cols + kFusTileC - 1) / kFusTileC);
     hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_net32_tiled), dim3(tblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, halo, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo));
-  } else if (reg.size() <= 32 && !(e->opt.dbg_ray & 1024)) {  // the same from L2
-    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_net32), dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
-                       int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
-                       lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
-  } else if (int(reg.size()) <= kFusionWaveMax && !(e->opt.dbg_post & 16)) {  // one wavefront per cell, the samples sorted in LDS
+  } else if (int(reg.size()) <= kFusionWaveMax) {  // one wavefront per cell, the samples sorted in LDS
     unsigned n_pad = 64u;
     while (n_pad < reg.size()) n_pad <<= 1;
     const unsigned lds = fusion_wave_lds_bytes(n_pad);
@@ -237,22 +224,6 @@ int fdm_engine_apply_uncertainty_fusion(fdm_engine* e, const fdm_fusion_config* 
     const unsigned wblocks = unsigned(std::min<size_t>((e->ncell + 1) / 2, 8192));
     hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion_wave), dim3(wblocks), dim3(kFusionWaveThreads), lds, e->stream, e->G, e->d_state,
                        int(e->scan_no & 3), e->d_region, F, n_pad, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
-                       lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
-  } else if (int(reg.size()) <= kFusionLdsEntries) {  // sample lists in LDS
-    const size_t lds = size_t(4) * reg.size() * kFusionThreads * sizeof(float);
-    static bool raised = false;
-    if (!raised) {
-      HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fusion<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(size_t(4) * kFusionLdsEntries * kFusionThreads * sizeof(float))));
-      raised = true;
-    }
-    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion<true>), dim3(fblocks), dim3(kFusionThreads), lds, e->stream, e->G, e->d_state,
-                       int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
-                       lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
-  } else if (reg.size() <= size_t(kMaxRegion)) {
-    hipLaunchKernelGGL(FDM_POST_KERNEL(k_fusion<false>), dim3(fblocks), dim3(kFusionThreads), 0, e->stream, e->G, e->d_state,
-                       int(e->scan_no & 3), e->d_region, F, e->d_tmp, e->d_tmp2, lptr(e, *up), lstride(e, *up),
                        lptr(e, *lo), lstride(e, *lo), unsigned(e->ncell));
   } else {  // any radius the reference accepts (config/postprocess.hpp:35)
     unsigned blocks = 0;
@@ -327,12 +298,12 @@ int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_val
   const float* elev_p = lptr(e, *elev);
   int elev_s = lstride(e, *elev);
   // (the LDS-tiled kernel stages its tile straight from the records: every cell is fetched ~3.4 times, from the L2, behind
-  //  other blocks' arithmetic — the copy was 17 of the call's 127 us at configs[3]; dbg_post 256: copy first, as before)
-  const bool tiled_ok = pct_ok && need_lo <= 16 && need_hi <= 16 && !tab.empty() && !(e->opt.dbg_post & 1);
+  //  other blocks' arithmetic — the copy was 17 of the call's 127 us at configs[3])
+  const bool tiled_ok = pct_ok && need_lo <= 16 && need_hi <= 16 && !tab.empty();
   // (the tiled kernel reads its own table only: the plain region — which the fusion stage of the same publish cycle keeps
   //  on the device with its weights — is left alone, and neither stage uploads anything from the second cycle on)
   if (!tiled_ok && (rc = upload_region(e, reg))) return rc;
-  if (elev_s != 1 && (!tiled_ok || (e->opt.dbg_post & 256))) {
+  if (elev_s != 1 && !tiled_ok) {
     if ((rc = ensure_tmp(e))) return rc;
     if ((rc = copy_strided(e, e->d_tmp, 1, elev_p, elev_s))) return rc;
     elev_p = e->d_tmp;
@@ -350,25 +321,25 @@ int fdm_engine_apply_feature_extraction(fdm_engine* e, float radius, int min_val
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(kFeatThreads), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                          e->d_feat_tab, F, halo, elev_p, elev_s, O);
     };
-    if (e->opt.dbg_post & 64) {  // (measurement: the two-instruction insertion chains of round 2)
-      if (need_lo <= 8 && need_hi <= 8) launch_tiled(FDM_POST_KERNEL(k_features_tiled<8, 8, false>));
-      else launch_tiled(FDM_POST_KERNEL(k_features_tiled<16, 16, false>));
-    } else if (need_lo <= 2 && need_hi <= 3) launch_tiled(FDM_POST_KERNEL(k_features_tiled<2, 3>));  // the defaults on a 29-cell disc (0.3 m on a 0.1 m map)
+    if (need_lo <= 2 && need_hi <= 3) launch_tiled(FDM_POST_KERNEL(k_features_tiled<2, 3>));  // the defaults on a 29-cell disc (0.3 m on a 0.1 m map)
     else if (need_lo <= 4 && need_hi <= 4) launch_tiled(FDM_POST_KERNEL(k_features_tiled<4, 4>));
     else if (need_lo <= 6 && need_hi <= 7) launch_tiled(FDM_POST_KERNEL(k_features_tiled<6, 7>));  // the defaults on a 113-cell disc: 6 from the bottom, 7 from the top
     else if (need_lo <= 8 && need_hi <= 8) launch_tiled(FDM_POST_KERNEL(k_features_tiled<8>));
     else launch_tiled(FDM_POST_KERNEL(k_features_tiled<16>));
   } else if (pct_ok && need_lo <= 8 && need_hi <= 8) launch_feat(FDM_POST_KERNEL(k_features<8>));
   else if (pct_ok && need_lo <= 16 && need_hi <= 16) launch_feat(FDM_POST_KERNEL(k_features<16>));
-  else if (reg.size() <= size_t(kMaxRegion) && (e->opt.dbg_post & 8)) launch_feat(FDM_POST_KERNEL(k_features<0>));
-  else if (features_sel_lds_bytes(halo, int(reg.size())) <= 160u * 1024u && !(e->opt.dbg_post & 8)) {
-    // any disc, any percentile pair: order statistics by bisection on an LDS tile (fdm_post.hpp k_features_sel)
+  else if (features_sel_lds_bytes(halo, int(reg.size())) <= 160u * 1024u) {
+    // any disc, any percentile pair: order statistics by bisection on an LDS tile (fdm_post.hpp k_features_sel).
+    // Every region of at most kMaxRegion entries comes here, so the pooled kernel below only ever sees larger ones: a
+    // disc that reaches h cells holds every offset with dr^2 + dc^2 <= h^2, among them the square of side
+    // 2 * floor(h / sqrt(2)) + 1; with at most 256 entries that side is at most 15, so h <= 11 (12 gives side 17).
+    static_assert(kMaxRegion < 17 * 17 && 160u * 1024u >= features_sel_lds_bytes(11, kMaxRegion),
+                  "a region of <= kMaxRegion entries fits the LDS of k_features_sel");
     const unsigned lds = features_sel_lds_bytes(halo, int(reg.size()));
     if ((rc = allow_lds(k_features_sel, lds))) return rc;
     hipLaunchKernelGGL(FDM_POST_KERNEL(k_features_sel), dim3(tile3_blocks(e)), dim3(256), lds, e->stream, e->G, e->d_state, int(e->scan_no & 3),
                        e->d_region, F, halo, elev_p, O);
-  } else if (reg.size() <= size_t(kMaxRegion)) launch_feat(FDM_POST_KERNEL(k_features<0>));
-  else {  // any radius the reference accepts (config/postprocess.hpp:45): the sorted heights in the global pool
+  } else {  // any radius the reference accepts (config/postprocess.hpp:45): the sorted heights in the global pool
     unsigned blocks = 0;
     if ((rc = ensure_pool(e, reg.size(), 256u, &blocks, reg.size()))) return rc;
     hipLaunchKernelGGL(FDM_POST_KERNEL(k_features_big), dim3(blocks), dim3(256), 0, e->stream, e->G, e->d_state, int(e->scan_no & 3),

@@ -457,8 +457,7 @@ int enqueue_ray_walk(fdm_engine* e, const RayLane& lane, const RayParams& Q_in, 
     const unsigned sectors = kRaySectors;
     // (a camera's 60-degree field of view puts its rays into 43 of the 256 sectors; four workgroups per sector for
     // scans of that size measured 22 us against 18: every one initialises and flushes a window of its own)
-    const unsigned parts = e->opt.ray_wedge_parts > 0 ? unsigned(e->opt.ray_wedge_parts)
-                                                  : std::max(1u, std::min(8u, Q.n / (sectors * 8u * kRwThreads)));
+    const unsigned parts = std::max(1u, std::min(8u, Q.n / (sectors * 8u * kRwThreads)));
     const uint32_t* bin_start = b.ray_bins + kRayBins;
     auto launch_wedge = [&](auto kern) -> int {
       if (int rc_lds = allow_lds(kern, lds)) return rc_lds;

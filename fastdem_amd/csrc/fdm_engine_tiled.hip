@@ -11,17 +11,15 @@ TileWork tile_work(const fdm_engine* e, unsigned blocks) {
   TileWork K{};
   K.W = blocks * 4u;
   K.T = (e->TG.n_tiles + K.W - 1u) / K.W;
-  K.prio = e->opt.upd_prio ? 1u : 0u;
-  K.stagger = unsigned(e->opt.bin_stagger);
-  K.delay = unsigned(e->opt.bin_delay);
-  K.delay_blocks = unsigned(e->opt.bin_delay_blocks);
   return K;
 }
 // update blocks of a launch: alone, enough to fill the chip; beside a bin half (fused launch), few — the bin blocks are
-// the arithmetic, the update wavefronts are chains of round trips that run beside them (option "upd_blocks")
+// the arithmetic, the update wavefronts are chains of round trips that run beside them (configs[3]: 384 / 512 / 768 /
+// 1 024 blocks 31.8 / 31.0 / 31.0 / 31.1 us, LABNOTES.md)
+constexpr unsigned kUpdBlocksFused = 768u, kUpdBlocksAlone = 2048u;
 unsigned update_blocks(const fdm_engine* e, bool fused) {
   const unsigned most = (e->TG.n_tiles + 3u) / 4u;  // one tile per wavefront
-  const unsigned want = fused ? unsigned(e->opt.upd_blocks) : unsigned(e->opt.upd_blocks_alone);
+  const unsigned want = fused ? kUpdBlocksFused : kUpdBlocksAlone;
   return std::max(1u, std::min(most, want));
 }
 
@@ -78,9 +76,8 @@ int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks) {
     }
     if (grow_desc && (rc = re(q.desc, size_t(e->TG.n_tiles) * e->desc_stride * 8))) return rc;  // (only entries below a tile's counter are ever read)
     if (!q.cnt) {
-      q.cnt_shift = unsigned(e->opt.cnt_shift);
-      HIPCK(hipMalloc(reinterpret_cast<void**>(&q.cnt), (size_t(e->TG.n_tiles) << q.cnt_shift) * sizeof(unsigned)));
-      HIPCK(hipMemsetAsync(q.cnt, 0, (size_t(e->TG.n_tiles) << q.cnt_shift) * sizeof(unsigned), e->stream));
+      HIPCK(hipMalloc(reinterpret_cast<void**>(&q.cnt), (size_t(e->TG.n_tiles) << kCntShift) * sizeof(unsigned)));
+      HIPCK(hipMemsetAsync(q.cnt, 0, (size_t(e->TG.n_tiles) << kCntShift) * sizeof(unsigned), e->stream));
     }
     q.stride = e->desc_stride;
   }
@@ -88,14 +85,15 @@ int ensure_tile_pool(fdm_engine* e, size_t records, unsigned blocks) {
 }
 
 // dynamic LDS of a large-scan launch that needs `lds` bytes: padded so that six blocks share a CU's 160 KB, not seven
-unsigned tiled_lds_padded(const fdm_engine* e, unsigned lds) {
-  if (e->opt.tiled_lds_pad >= 0) return lds + unsigned(e->opt.tiled_lds_pad);
+// (seven: configs[3] 32.3 -> 31.8 us at six; five — what a fixed 4 KB came to for a scan with an intensity channel,
+// 29.7 KB per block — 31.4 -> 30.3 us at six, profiles/r06/probe_l.json)
+unsigned tiled_lds_padded(unsigned lds) {
   constexpr unsigned kSeven = 163840u / 7u;  // at most this much: seven blocks fit
   return lds <= kSeven ? kSeven + 16u : lds;
 }
 int launch_tbin(fdm_engine* e, const ScanParams& P, const ScanInputs& in, const TilePool& Q, int32_t* ids,
                 unsigned bin_blocks, fdm_engine::BinVariant bv) {
-  const unsigned lds = tiled_lds_padded(e, tbin_lds_bytes(bv.has_int, bv.has_col, bv.threads));
+  const unsigned lds = tiled_lds_padded(tbin_lds_bytes(bv.has_int, bv.has_col, bv.threads));
   int rc = FDM_OK;
   auto go = [&](auto kern) {
     if ((rc = allow_lds(kern, lds))) return;
@@ -144,7 +142,7 @@ int launch_tiled_update_fused(fdm_engine* e, const fdm_engine::PendingUpdate& u,
       if constexpr (kRec) {
         const unsigned ub = update_blocks(e, true);
         const TileWork K = tile_work(e, ub);
-        const unsigned lds = tiled_lds_padded(e, std::max(tile_lds_bytes(bv.has_int, bv.has_col), tbin_lds_bytes(bv.has_int, bv.has_col, bv.threads)));
+        const unsigned lds = tiled_lds_padded(std::max(tile_lds_bytes(bv.has_int, bv.has_col), tbin_lds_bytes(bv.has_int, bv.has_col, bv.threads)));
         int rc = FDM_OK;
         auto go = [&](auto kern) {
           if ((rc = allow_lds(kern, lds))) return;

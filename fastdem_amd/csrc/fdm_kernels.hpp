@@ -258,7 +258,6 @@ __device__ __forceinline__ void bin4_body(const ScanParams& P, const GeomConst& 
   float* const cap_var = LEAN ? nullptr : S.cap_var;
   float* const wt_x = LEAN == 1 ? nullptr : S.wt_x;
   int32_t* const ids = LEAN ? nullptr : cell_ids;
-  const int dbg_na = LEAN ? 0 : P.dbg_no_atomics;
   const bool drop_nf = LEAN ? false : P.drop_nonfinite != 0;
   constexpr int kHashSlots = THREADS * 4;  // == points per block: room for every point in its own cell
   __shared__ unsigned long long h_key[kHashSlots];
@@ -320,10 +319,6 @@ __device__ __forceinline__ void bin4_body(const ScanParams& P, const GeomConst& 
   bool any_glob = false;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    if (dbg_na >= 3) {  // measurement only: loads without the arithmetic
-      cells[j] = (xs[j] + ys[j] + zs[j] == 12345.f) ? 0 : -1;
-      continue;
-    }
     const bool live = i0 + j < P.n;
     float cvar = 0.f;
     if (cap_var && live && P.integrate_mode) cvar = sigma_z2(P, xs[j], ys[j], zs[j]);
@@ -352,7 +347,7 @@ __device__ __forceinline__ void bin4_body(const ScanParams& P, const GeomConst& 
   unsigned long long run_key = kEmptyKey;
   uint32_t run_zmx = 0, run_imx = 0, run_fst = kNoIdx, run_lst = 0;
   auto fold_run = [&]() {
-    if (run_cell < 0 || dbg_na >= 2) return;
+    if (run_cell < 0) return;
     uint32_t h = uint32_t(run_cell) & (kHashSlots - 1);
     while (true) {
       const uint32_t seen = h_cell[h];
@@ -405,16 +400,14 @@ __device__ __forceinline__ void bin4_body(const ScanParams& P, const GeomConst& 
   __syncthreads();  // every run of the block is in the table
 
   // phase 3: one global atomic set per unique cell of the block
-  if (!dbg_na) {
 #pragma unroll
-    for (int q = 0; q < kHashSlots / THREADS; ++q) {
-      const int k = threadIdx.x + q * THREADS;
-      const uint32_t cell = h_cell[k];
-      if (cell == kEmptyCell) continue;
-      scratch_merge<HAS_INT, HAS_COL>(S, P.scan_no, cell, h_key[k], h_zmax[k],
-                                      HAS_INT ? h_imax[k] : 0u, HAS_INT ? h_first[k] : 0u,
-                                      HAS_COL ? h_last[k] : 0u);
-    }
+  for (int q = 0; q < kHashSlots / THREADS; ++q) {
+    const int k = threadIdx.x + q * THREADS;
+    const uint32_t cell = h_cell[k];
+    if (cell == kEmptyCell) continue;
+    scratch_merge<HAS_INT, HAS_COL>(S, P.scan_no, cell, h_key[k], h_zmax[k],
+                                    HAS_INT ? h_imax[k] : 0u, HAS_INT ? h_first[k] : 0u,
+                                    HAS_COL ? h_last[k] : 0u);
   }
   if (threadIdx.x == 0) {
     unsigned np = 0, ni = 0;
@@ -456,22 +449,20 @@ __device__ __forceinline__ void bin_body(const ScanParams& P, const GeomConst& G
   float* const cap_var = LEAN ? nullptr : S.cap_var;
   float* const wt_x = LEAN == 1 ? nullptr : S.wt_x;
   int32_t* const ids = LEAN ? nullptr : cell_ids;
-  const int dbg_na = LEAN ? 0 : P.dbg_no_atomics;
   const bool drop_nf = LEAN ? false : P.drop_nonfinite != 0;
   const bool has_int = CH < 0 ? P.has_intensity != 0 : (CH & 1) != 0;
   const bool has_col = CH < 0 ? P.has_color != 0 : (CH & 2) != 0;
   __shared__ DevCand s_cand;
   __shared__ unsigned s_pass[4], s_in[4];
-  // per-block table of the cells this block's 256 points fall into (P.bin_table): the run tails of
+  // per-block table of the cells this block's 256 points fall into: the run tails of
   // the wave merge fold into it with LDS atomics and only its occupied slots go to memory — a firing-
   // order scan puts the 16 samples a block holds of each beam into 2-3 cells, but 16 lanes apart
   __shared__ unsigned long long t_key[256];
   __shared__ uint32_t t_cell[256], t_zmx[256], t_imx[256], t_fst[256], t_lst[256];
-  if (P.bin_table) {
-    t_key[threadIdx.x] = kEmptyKey;
-    t_cell[threadIdx.x] = kEmptyCell;
-    t_zmx[threadIdx.x] = 0u; t_imx[threadIdx.x] = 0u; t_fst[threadIdx.x] = kNoIdx; t_lst[threadIdx.x] = 0u;
-  }  // (made visible by the barrier inside block_candidate)
+  t_key[threadIdx.x] = kEmptyKey;
+  t_cell[threadIdx.x] = kEmptyCell;
+  t_zmx[threadIdx.x] = 0u; t_imx[threadIdx.x] = 0u; t_fst[threadIdx.x] = kNoIdx; t_lst[threadIdx.x] = 0u;
+  // (made visible by the barrier inside block_candidate)
   // the point (and intensity) loads go out first: they are in flight while thread 0 reads the
   // geometry and works out the post-move candidate
   const unsigned i = bid * 256u + threadIdx.x;
@@ -555,7 +546,7 @@ __device__ __forceinline__ void bin_body(const ScanParams& P, const GeomConst& G
   }
   // a wave whose adjacent-lane merge already found long runs (ring-major scans: few tails) goes to
   // memory directly; one whose lanes are mostly their own tail (firing order) folds into the table
-  const bool use_table = P.bin_table && 2 * __popcll(__ballot(commit)) > __popcll(__ballot(inside));
+  const bool use_table = 2 * __popcll(__ballot(commit)) > __popcll(__ballot(inside));
   if (use_table) {
     if (commit) {
       uint32_t h = uint32_t(cell) & 255u;
@@ -576,7 +567,7 @@ __device__ __forceinline__ void bin_body(const ScanParams& P, const GeomConst& G
       }
       if (has_col) atomicMax(&t_lst[h], lst);
     }
-  } else if (commit && !dbg_na) {
+  } else if (commit) {
     if (has_int && has_col)
       scratch_merge<true, true>(S, P.scan_no, cell, key, zmx, imx, fst, lst);
     else if (has_int)
@@ -594,16 +585,14 @@ __device__ __forceinline__ void bin_body(const ScanParams& P, const GeomConst& G
     if (mg) st->flags[P.slot].any_inside = 1u;
   }
   __syncthreads();
-  if (P.bin_table && !dbg_na) {  // one slot per thread
-    const uint32_t tc = t_cell[threadIdx.x];
-    if (tc != kEmptyCell) {
-      const unsigned long long tk = t_key[threadIdx.x];
-      const uint32_t a = t_zmx[threadIdx.x], b2 = t_imx[threadIdx.x], c2 = t_fst[threadIdx.x], d2 = t_lst[threadIdx.x];
-      if (has_int && has_col) scratch_merge<true, true>(S, P.scan_no, tc, tk, a, b2, c2, d2);
-      else if (has_int) scratch_merge<true, false>(S, P.scan_no, tc, tk, a, b2, c2, d2);
-      else if (has_col) scratch_merge<false, true>(S, P.scan_no, tc, tk, a, b2, c2, d2);
-      else scratch_merge<false, false>(S, P.scan_no, tc, tk, a, b2, c2, d2);
-    }
+  const uint32_t tc = t_cell[threadIdx.x];  // one slot per thread
+  if (tc != kEmptyCell) {
+    const unsigned long long tk = t_key[threadIdx.x];
+    const uint32_t a = t_zmx[threadIdx.x], b2 = t_imx[threadIdx.x], c2 = t_fst[threadIdx.x], d2 = t_lst[threadIdx.x];
+    if (has_int && has_col) scratch_merge<true, true>(S, P.scan_no, tc, tk, a, b2, c2, d2);
+    else if (has_int) scratch_merge<true, false>(S, P.scan_no, tc, tk, a, b2, c2, d2);
+    else if (has_col) scratch_merge<false, true>(S, P.scan_no, tc, tk, a, b2, c2, d2);
+    else scratch_merge<false, false>(S, P.scan_no, tc, tk, a, b2, c2, d2);
   }
   if (threadIdx.x == 0) {
     const unsigned np = s_pass[0] + s_pass[1] + s_pass[2] + s_pass[3];
@@ -931,7 +920,7 @@ __device__ __forceinline__ void update_body(
   UpdateCtx u;
   make_ctx(P, st, S, u, tile, lt, tile * 256u < ncell);
   bool touched = false;
-  if (valid && (u.cur || u.obst_tile || u.strips) && P.dbg_upd != 1) {
+  if (valid && (u.cur || u.obst_tile || u.strips)) {
     if (!S.dense && u.cur) key = S.key[o];
     bool in_strip = false;
     // (a move of >= the map's size on an axis is clearAll() in either reading of move())
@@ -957,7 +946,7 @@ __device__ __forceinline__ void update_body(
         POLICY::clear_cell(L, o);  // record layout: the packed estimator state
       }
     }
-    touched = u.cur && key != kEmptyKey && P.dbg_upd != 3;  // dbg_upd: measurement-only switches
+    touched = u.cur && key != kEmptyKey;
     if (!touched) {
       // map_.clear(obstacle) (elevation_mapping.cpp:144-146) for the cells it can matter for
       if (u.obst_tile && (!in_strip || basic)) L.obstacle[o] = nanv;
@@ -1164,7 +1153,7 @@ inline __global__ __launch_bounds__(256) void k_collect_stats(const unsigned lon
   }
 }
 
-// One launch for two scans: blocks [0, upd_blocks) finish scan t (its update), the rest start scan
+// One launch for two scans: blocks [0, n_upd_blocks) finish scan t (its update), the rest start scan
 // t+1 (its bin).  The two halves share nothing — the scratch is double-buffered by scan parity and
 // the chained bin derives its base geometry from slot t (ScanParams::chain_prev) — so a stream of
 // small scans costs one launch and max(bin, update) per scan instead of two launches and their sum.
@@ -1181,14 +1170,14 @@ template <typename POLICY, bool HAS_INT, bool HAS_COL, int THREADS, bool STAMPED
 __global__ __launch_bounds__(THREADS) void k_update_bin4(
     const ScanParams Pu, const GeomConst G, DevState* __restrict__ st, const typename POLICY::Layers L,
     float* const* __restrict__ all_layers, int n_layers, const Scratch Su, const ScanInputs Iu, unsigned ncell,
-    unsigned upd_blocks, const ScanParams Pb, const Scratch Sb, const ScanInputs Ib,
+    unsigned n_upd_blocks, const ScanParams Pb, const Scratch Sb, const ScanInputs Ib,
     int32_t* __restrict__ cell_ids) {
   // the two kinds of block are interleaved in proportion over the grid, so that the bandwidth-bound
   // update half and the atomic/latency-bound bin half are resident together for the whole launch
   // (update blocks first, then bin blocks, only overlapped where one kind ran out)
   const unsigned long long total = gridDim.x;
-  const unsigned u0 = unsigned((blockIdx.x * (unsigned long long)upd_blocks) / total);
-  const unsigned u1 = unsigned(((blockIdx.x + 1ull) * (unsigned long long)upd_blocks) / total);
+  const unsigned u0 = unsigned((blockIdx.x * (unsigned long long)n_upd_blocks) / total);
+  const unsigned u1 = unsigned(((blockIdx.x + 1ull) * (unsigned long long)n_upd_blocks) / total);
   if (u1 > u0) {
     if (!STAMPED)
       update_body<POLICY, THREADS>(Pu, G, st, L, all_layers, n_layers, Su, Iu.x, Iu.y, Iu.z, Iu.rgb, Iu.var, ncell, u0);
@@ -1205,9 +1194,9 @@ template <typename POLICY, bool WAVE_MERGE, bool STAMPED = false, int CH = -1, i
 __global__ __launch_bounds__(256) void k_update_bin(
     const ScanParams Pu, const GeomConst G, DevState* __restrict__ st, const typename POLICY::Layers L,
     float* const* __restrict__ all_layers, int n_layers, const Scratch Su, const ScanInputs Iu, unsigned ncell,
-    unsigned upd_blocks, const ScanParams Pb, const Scratch Sb, const ScanInputs Ib,
+    unsigned n_upd_blocks, const ScanParams Pb, const Scratch Sb, const ScanInputs Ib,
     int32_t* __restrict__ cell_ids) {
-  if (blockIdx.x < upd_blocks) {
+  if (blockIdx.x < n_upd_blocks) {
     if (!STAMPED)
       update_body<POLICY>(Pu, G, st, L, all_layers, n_layers, Su, Iu.x, Iu.y, Iu.z, Iu.rgb, Iu.var, ncell,
                           blockIdx.x);
@@ -1215,7 +1204,7 @@ __global__ __launch_bounds__(256) void k_update_bin(
       update_stamped_body<POLICY, 256>(Pu, G, st, L, all_layers, n_layers, Su, Iu.x, Iu.y, Iu.z, Iu.rgb, Iu.var,
                                        ncell, blockIdx.x);
   } else {
-    bin_body<WAVE_MERGE, CH, LEAN>(Pb, G, st, Ib.x, Ib.y, Ib.z, Ib.intensity, Sb, cell_ids, blockIdx.x - upd_blocks);
+    bin_body<WAVE_MERGE, CH, LEAN>(Pb, G, st, Ib.x, Ib.y, Ib.z, Ib.intensity, Sb, cell_ids, blockIdx.x - n_upd_blocks);
   }
 }
 

@@ -100,7 +100,9 @@ struct MCommon {  // what all scans of a batch share
   float min_sq, max_sq, z_min, z_max;
   float sp[4];
   float Tbs[16];  // T_base_sensor (one sensor per batch: a scan with another extrinsic closes the batch)
-  int sensor_type, integrate_mode, do_move, gate_on_filter, has_var, bin_table;
+  int sensor_type, integrate_mode, do_move, gate_on_filter, has_var;
+  int pad0;  // (no kernel reads it.  It keeps the words behind it in the groups k_mbatch's scalar loads fetch them in: without it
+             //  every instantiation is allocated differently and configs[1] measured 2.4 % slower, profiles/r14/retire)
   int dbg, walk;                 // walk: 1 = the chain of moves is walked one launch ahead (mwalk_body).  dbg, measurement only: 1 = no scratch atomics, 2 = no chain walk (both: wrong results); 3 = every move by the reference's divide (tests)
   int walk_from, pad;            // with walk: scans k >= walk_from take the pre-walked chain, the bin blocks of earlier scans walk their own
   unsigned long long* timeline;  // measurement only (nullable): {start, end} of every block in 100 MHz ticks
@@ -1406,7 +1408,7 @@ __global__ __launch_bounds__(256, MBatchWaves<POLICY>::value) void k_mbatch(cons
                                                 const GeomConst G, DevState* __restrict__ st,
                                                 const typename POLICY::Layers L,
                                                 float* const* __restrict__ all_layers, int n_layers,
-                                                unsigned ncell, unsigned upd_blocks, unsigned upd_rows) {
+                                                unsigned ncell, unsigned n_upd_blocks, unsigned upd_rows) {
   __shared__ __align__(16) unsigned char lds[kMLdsBytes<(CH & 2) != 0, RAY>];
   const unsigned long long t0 = K.timeline ? wall_clock64() : 0ull;
 #if FDM_MB_PHASES
@@ -1415,7 +1417,7 @@ __global__ __launch_bounds__(256, MBatchWaves<POLICY>::value) void k_mbatch(cons
   const unsigned row = blockIdx.y, x = blockIdx.x;
   if (row < upd_rows) {
     const unsigned ub = row * gridDim.x + x;
-    if (ub < upd_blocks)
+    if (ub < n_upd_blocks)
       mupdate_body<POLICY, CH, RAY>(U, G, st, L, all_layers, n_layers, ncell, ub,
                                     *reinterpret_cast<MUpdLds<(CH & 2) != 0, RAY>*>(lds));
   } else if (row < upd_rows + B.count) {

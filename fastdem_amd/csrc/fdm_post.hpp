@@ -49,37 +49,6 @@ __device__ __forceinline__ bool post_inside(const PostGeom& p, int lr, int lc) {
   return unsigned(lr) < unsigned(p.rows) && unsigned(lc) < unsigned(p.cols);
 }
 
-// ---- inpainting: one pass (inpainting.cpp:41-64); the caller ping-pongs two buffers ----
-inline __global__ __launch_bounds__(256) void k_inpaint_pass(const GeomConst G, const DevState* __restrict__ st, int slot,
-                                                      const float* __restrict__ in, int in_stride,
-                                                      float* __restrict__ out, int out_stride,
-                                                      int min_valid, unsigned ncell) {
-  const unsigned t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= ncell) return;
-  const PostGeom p = post_geom(st, slot, G);
-  const int lc = int(t / unsigned(p.rows)), lr = int(t - unsigned(lc) * unsigned(p.rows));
-  const size_t ci = post_index(p, lr, lc);
-  float v = in[ci * in_stride];
-  if (isnan(v)) {
-    float sum = 0.0f;
-    int count = 0;
-#pragma unroll
-    for (int dr = -1; dr <= 1; ++dr)
-#pragma unroll
-      for (int dc = -1; dc <= 1; ++dc) {
-        if (dr == 0 && dc == 0) continue;
-        if (!post_inside(p, lr + dr, lc + dc)) continue;
-        const float n = in[post_index(p, lr + dr, lc + dc) * in_stride];
-        if (isfinite(n)) {
-          sum += n;
-          ++count;
-        }
-      }
-    if (count >= min_valid) v = sum / float(count);
-  }
-  out[ci * out_stride] = v;
-}
-
 // ---- spatial median smoothing (spatial_smoothing.hpp:52-66); `in` is a private copy ----
 inline __global__ __launch_bounds__(256) void k_median(const GeomConst G, const DevState* __restrict__ st, int slot,
                                                 const float* __restrict__ in, float* __restrict__ out,
@@ -197,41 +166,8 @@ inline __global__ __launch_bounds__(256) void k_median_sel(const GeomConst G, co
   out[post_index(p, lr, lc) * size_t(out_stride)] = post_unkey(key);
 }
 
-// 3x3 window (the default kernel): the nine values are named registers, missing / non-finite
-// neighbours are +inf, a 25-step sorting network (verified on all 512 0-1 inputs) orders them and
-// element n/2 of the n finite ones is the median — no window in scratch memory, no dependent loop.
-inline __global__ __launch_bounds__(256) void k_median3(const GeomConst G, const DevState* __restrict__ st, int slot,
-                                                 const float* __restrict__ in, float* __restrict__ out,
-                                                 int out_stride, int min_valid, unsigned ncell) {
-  const unsigned t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= ncell) return;
-  const PostGeom p = post_geom(st, slot, G);
-  const int lc = int(t / unsigned(p.rows)), lr = int(t - unsigned(lc) * unsigned(p.rows));
-  const size_t ci = post_index(p, lr, lc);
-  if (!isfinite(in[ci])) return;
-  constexpr float kInf = __builtin_huge_valf();
-  int n = 0;
-#define FDM_W(k, dr, dc)                                                        \
-  float w##k = kInf;                                                            \
-  if (post_inside(p, lr + (dr), lc + (dc))) {                                   \
-    const float v = in[post_index(p, lr + (dr), lc + (dc))];                    \
-    if (isfinite(v)) { w##k = v; ++n; }                                         \
-  }
-  FDM_W(0, -1, -1) FDM_W(1, -1, 0) FDM_W(2, -1, 1) FDM_W(3, 0, -1) FDM_W(4, 0, 0) FDM_W(5, 0, 1)
-  FDM_W(6, 1, -1) FDM_W(7, 1, 0) FDM_W(8, 1, 1)
-#undef FDM_W
-  if (n < min_valid) return;
-#define FDM_CE(i, j) { const float lo_ = fminf(w##i, w##j); w##j = fmaxf(w##i, w##j); w##i = lo_; }
-  FDM_CE(0, 3) FDM_CE(1, 7) FDM_CE(2, 5) FDM_CE(4, 8) FDM_CE(0, 7) FDM_CE(2, 4) FDM_CE(3, 8) FDM_CE(5, 6)
-  FDM_CE(0, 2) FDM_CE(1, 3) FDM_CE(4, 5) FDM_CE(7, 8) FDM_CE(1, 4) FDM_CE(3, 6) FDM_CE(5, 7) FDM_CE(0, 1)
-  FDM_CE(2, 4) FDM_CE(3, 5) FDM_CE(6, 8) FDM_CE(2, 3) FDM_CE(4, 5) FDM_CE(6, 7) FDM_CE(1, 2) FDM_CE(3, 4)
-  FDM_CE(5, 6)
-#undef FDM_CE
-  const int m = n / 2;  // nth_element(size/2): 0..4
-  out[ci * out_stride] = m == 0 ? w0 : (m == 1 ? w1 : (m == 2 ? w2 : (m == 3 ? w3 : w4)));
-}
-
-// ---- the two 3x3 stencils with the neighbourhood staged in LDS: one block per 32 x 8 cells, a ring of one cell,
+// ---- the two 3x3 stencils — one inpainting pass (inpainting.cpp:41-64; the caller ping-pongs two buffers) and the 3x3
+// median (the default kernel) — with the neighbourhood staged in LDS: one block per 32 x 8 cells, a ring of one cell,
 // cells outside the stored window as NaN ("outside" and "no data" are one test), neighbours visited in the
 // reference's order ----
 constexpr int kS3R = 32, kS3C = 8, kS3Pitch = kS3R + 2, kS3Width = kS3C + 2;
@@ -276,6 +212,9 @@ inline __global__ __launch_bounds__(256) void k_inpaint_pass_tiled(const GeomCon
   }
   out[post_index(p, lr, lc) * size_t(out_stride)] = v;
 }
+// The nine values are named registers, missing / non-finite neighbours are +inf, a 25-step sorting network (verified on
+// all 512 0-1 inputs) orders them and element n/2 of the n finite ones is the median — no window in scratch memory, no
+// dependent loop.
 inline __global__ __launch_bounds__(256) void k_median3_tiled(const GeomConst G, const DevState* __restrict__ st, int slot,
                                                        const float* __restrict__ in, float* __restrict__ out,
                                                        int out_stride, int min_valid) {
@@ -342,19 +281,10 @@ struct FusionParams {
   float inv_2s2, q_lower, q_upper;
   int min_valid, n_entries;
 };
-// SimpleWeightedECDF::quantile over samples sorted by value (uncertainty_fusion.cpp:63-91): ecdf_quantile_t
-// Per-thread sample lists live in LDS when the disc is small enough (slot-major, thread-minor: the
-// lanes of a wave hit consecutive banks), in scratch otherwise.  The lists are kept sorted by
-// insertion, which is what makes the kernel O(n^2) per cell and is the price of summing the weights
-// in the reference's (sorted) order.
 constexpr int kFusionThreads = 128;
-constexpr int kFusionLdsEntries = 64;  // 4 lists x 64 entries x 128 threads x 4 B = 128 KB of the CU's 160 KB
-
-template <bool USE_LDS>
-struct SampleList {
-  float* base;  // LDS: list[slot * kFusionThreads]; scratch: list[slot]
-  __device__ __forceinline__ float& operator[](int k) const { return USE_LDS ? base[k * kFusionThreads] : base[k]; }
-};
+// SimpleWeightedECDF::quantile over samples sorted by value (uncertainty_fusion.cpp:63-91), for k_fusion_big's lists: they
+// are kept sorted by insertion, which is what makes that kernel O(n^2) per cell and is the price of summing the weights
+// in the reference's (sorted) order.
 template <class LIST>
 __device__ __forceinline__ float ecdf_quantile_l(const LIST& val, const LIST& wgt, int n, float p) {
   if (n == 0) return __uint_as_float(0x7FC00000u);
@@ -370,75 +300,8 @@ __device__ __forceinline__ float ecdf_quantile_l(const LIST& val, const LIST& wg
   }
   return val[n - 1];
 }
-template <bool USE_LDS>
-__device__ __forceinline__ float ecdf_quantile_t(const SampleList<USE_LDS>& val, const SampleList<USE_LDS>& wgt, int n,
-                                                 float p) {
-  if (n == 0) return __uint_as_float(0x7FC00000u);
-  if (n == 1) return val[0];
-  float total = 0.0f;
-  for (int k = 0; k < n; ++k) total += wgt[k];
-  if (total <= 0.0f) return __uint_as_float(0x7FC00000u);
-  const float target = p * total;
-  float cumulative = 0.0f;
-  for (int k = 0; k < n; ++k) {
-    cumulative += wgt[k];
-    if (cumulative >= target) return val[k];
-  }
-  return val[n - 1];
-}
-
-template <bool USE_LDS>
-__global__ __launch_bounds__(kFusionThreads) void k_fusion(const GeomConst G, const DevState* __restrict__ st,
-                                                           int slot, const RegionEntry* __restrict__ reg,
-                                                           const FusionParams F, const float* __restrict__ up_in,
-                                                           const float* __restrict__ lo_in,
-                                                           float* __restrict__ up_out, int up_stride,
-                                                           float* __restrict__ lo_out, int lo_stride,
-                                                           unsigned ncell) {
-  extern __shared__ float s_lists[];
-  float scratch[USE_LDS ? 1 : 4 * kMaxRegion];
-  const int cap = USE_LDS ? F.n_entries : kMaxRegion;  // LDS is sized for the region actually used
-  float* pool = USE_LDS ? s_lists + threadIdx.x : scratch;
-  const int pitch = USE_LDS ? cap * kFusionThreads : cap;
-  const SampleList<USE_LDS> lv{pool}, lw{pool + pitch}, uv{pool + 2 * pitch}, uw{pool + 3 * pitch};
-  const unsigned t = blockIdx.x * unsigned(kFusionThreads) + threadIdx.x;
-  if (t >= ncell) return;
-  const PostGeom p = post_geom(st, slot, G);
-  const int lc = int(t / unsigned(p.rows)), lr = int(t - unsigned(lc) * unsigned(p.rows));
-  const size_t ci = post_index(p, lr, lc);
-  if (!isfinite(up_in[ci]) || !isfinite(lo_in[ci])) return;
-  int nl = 0, nu = 0, valid = 0;
-  for (int e = 0; e < F.n_entries; ++e) {
-    const RegionEntry re = reg[e];
-    if (!post_inside(p, lr + re.dr, lc + re.dc)) continue;
-    const size_t ni = post_index(p, lr + re.dr, lc + re.dc);
-    const float nu_v = up_in[ni], nl_v = lo_in[ni];
-    if (!isfinite(nu_v) || !isfinite(nl_v)) continue;
-    const float w_spatial = re.w;  // std::exp(-dist_sq * inv_2sigma_sq): a property of the entry, from the host
-    const float range = nu_v - nl_v;
-    const float w_range = 1.0f / (range + 1e-4f);
-    const float weight = w_spatial * w_range;
-    if (weight > 1e-6f) {  // SimpleWeightedECDF::add; the values are finite here
-      int k = nl++;
-      while (k > 0 && lv[k - 1] > nl_v) { lv[k] = lv[k - 1]; lw[k] = lw[k - 1]; --k; }
-      lv[k] = nl_v; lw[k] = weight;
-      k = nu++;
-      while (k > 0 && uv[k - 1] > nu_v) { uv[k] = uv[k - 1]; uw[k] = uw[k - 1]; --k; }
-      uv[k] = nu_v; uw[k] = weight;
-    }
-    ++valid;
-  }
-  if (valid < F.min_valid) return;
-  const float lower = ecdf_quantile_t<USE_LDS>(lv, lw, nl, F.q_lower);
-  const float upper = ecdf_quantile_t<USE_LDS>(uv, uw, nu, F.q_upper);
-  if (isfinite(lower) && isfinite(upper)) {
-    up_out[ci * up_stride] = upper;
-    lo_out[ci * lo_stride] = lower;
-  }
-}
-
-// Discs of more than 32 cells: ONE WAVEFRONT per cell, the samples sorted in LDS.  The insertion sorts of k_fusion /
-// k_fusion_big keep a list per THREAD (O(n^2) moves through LDS, scratch or a global pool: 134 ms for a 317-cell disc on
+// Discs of more than 32 cells: ONE WAVEFRONT per cell, the samples sorted in LDS.  The insertion sort of
+// k_fusion_big keeps a list per THREAD (O(n^2) moves through a global pool: 134 ms for a 317-cell disc on
 // the 1200 x 1200 map); here a wavefront gathers the disc once (lane = entry), sorts 64-bit keys ord(value) << 32 | entry
 // — ties in entry order, which is what the reference's insertion into a sorted list leaves — with a bitonic network
 // in wave-private LDS, lays the weights out in sorted order and walks SimpleWeightedECDF::quantile's two sequential sums
@@ -608,18 +471,18 @@ inline __global__ __launch_bounds__(kFusionThreads) void k_fusion_big(const Geom
 // 64-bit register, ord(value) << 32 | entry index, so that ties keep the entry order the insertion
 // sort above gives them; a fixed 191-step merge-exchange network (fdm_sortnet32.inc) sorts the
 // lower and the upper samples in registers, and the weights — shared by both lists — sit in LDS by
-// entry index.  The list kernel holds one wave per SIMD (59 KB of LDS per 128 threads) and walks a
-// dependent chain of ~1900 LDS operations per cell; this one is straight-line ALU code.
+// entry index.  Straight-line ALU code, where a kernel of per-thread lists walks a dependent chain of ~1900 LDS
+// operations per cell.
 #include "fdm_sortnet32.inc"
 #define FDM_E32(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) \
   X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31)
 // One list (lower or upper bounds) of one cell: gather, sort, weighted quantile.  The two lists are
 // done one after the other so that only 32 samples are live (2 x 32 x 64 bit would hold the kernel
-// at one wave per SIMD); the second pass re-reads the neighbours from L2 and the weights from LDS.
-// TILED: up_in / lo_in are the block's LDS tiles (cells outside the stored window hold NaN), `lr` is the thread's
-// cell inside them and `lc` the tile pitch — a neighbour is one scalar multiply-add and two LDS reads.
-template <bool UPPER, bool TILED = false>
-__device__ __forceinline__ float fusion_list32(const PostGeom& p, int lr, int lc, const RegionEntry* __restrict__ reg,
+// at one wave per SIMD); the second pass re-reads the neighbours and the weights from LDS.
+// up_in / lo_in are the block's LDS tiles (cells outside the stored window hold NaN), `base` is the thread's
+// cell inside them and `pitch` the tile pitch — a neighbour is one scalar multiply-add and two LDS reads.
+template <bool UPPER>
+__device__ __forceinline__ float fusion_list32(int base, int pitch, const RegionEntry* __restrict__ reg,
                                                const FusionParams& F, const float* __restrict__ up_in,
                                                const float* __restrict__ lo_in, float (*s_w)[kFusionThreads],
                                                int& valid, uint32_t& taken) {
@@ -634,19 +497,17 @@ __device__ __forceinline__ float fusion_list32(const PostGeom& p, int lr, int lc
 #define FDM_GATHER(e)                                                                         \
   if (e < F.n_entries) {                                                                       \
     const RegionEntry re = reg[e];                                                             \
-    if (TILED || post_inside(p, lr + re.dr, lc + re.dc)) {                                     \
-      const size_t ni = TILED ? size_t(lr + re.dc * lc + re.dr) : post_index(p, lr + re.dr, lc + re.dc); \
-      const float nu_v = up_in[ni], nl_v = lo_in[ni];                                          \
-      if (isfinite(nu_v) && isfinite(nl_v)) {                                                  \
-        const float weight = re.w * (1.0f / ((nu_v - nl_v) + 1e-4f));                          \
-        if (weight > 1e-6f) {                                                                  \
-          s_w[e][threadIdx.x] = weight;                                                        \
-          a##e = ((unsigned long long)ord(nl_v == 0.0f ? 0.0f : nl_v) << 32) | unsigned(e);    \
-          taken |= 1u << e;                                                                    \
-          ++n;                                                                                 \
-        }                                                                                      \
-        ++valid;                                                                               \
+    const size_t ni = size_t(base + re.dc * pitch + re.dr);                                    \
+    const float nu_v = up_in[ni], nl_v = lo_in[ni];                                            \
+    if (isfinite(nu_v) && isfinite(nl_v)) {                                                    \
+      const float weight = re.w * (1.0f / ((nu_v - nl_v) + 1e-4f));                            \
+      if (weight > 1e-6f) {                                                                    \
+        s_w[e][threadIdx.x] = weight;                                                          \
+        a##e = ((unsigned long long)ord(nl_v == 0.0f ? 0.0f : nl_v) << 32) | unsigned(e);      \
+        taken |= 1u << e;                                                                      \
+        ++n;                                                                                   \
       }                                                                                        \
+      ++valid;                                                                                 \
     }                                                                                          \
   }
     FDM_E32(FDM_GATHER)
@@ -656,7 +517,7 @@ __device__ __forceinline__ float fusion_list32(const PostGeom& p, int lr, int lc
 #define FDM_GATHER_U(e)                                                                       \
   if ((taken >> e) & 1u) {                                                                     \
     const RegionEntry re = reg[e];                                                             \
-    const size_t ni = TILED ? size_t(lr + re.dc * lc + re.dr) : post_index(p, lr + re.dr, lc + re.dc); \
+    const size_t ni = size_t(base + re.dc * pitch + re.dr);                                    \
     const float nu_v = up_in[ni];                                                              \
     a##e = ((unsigned long long)ord(nu_v == 0.0f ? 0.0f : nu_v) << 32) | unsigned(e);          \
   }
@@ -688,33 +549,9 @@ __device__ __forceinline__ float fusion_list32(const PostGeom& p, int lr, int lc
   return q;
 }
 
-inline __global__ __launch_bounds__(kFusionThreads) void k_fusion_net32(const GeomConst G, const DevState* __restrict__ st,
-                                                                 int slot, const RegionEntry* __restrict__ reg,
-                                                                 const FusionParams F, const float* __restrict__ up_in,
-                                                                 const float* __restrict__ lo_in,
-                                                                 float* __restrict__ up_out, int up_stride,
-                                                                 float* __restrict__ lo_out, int lo_stride,
-                                                                 unsigned ncell) {
-  __shared__ float s_w[32][kFusionThreads];
-  const unsigned t = blockIdx.x * unsigned(kFusionThreads) + threadIdx.x;
-  if (t >= ncell) return;
-  const PostGeom p = post_geom(st, slot, G);
-  const int lc = int(t / unsigned(p.rows)), lr = int(t - unsigned(lc) * unsigned(p.rows));
-  const size_t ci = post_index(p, lr, lc);
-  if (!isfinite(up_in[ci]) || !isfinite(lo_in[ci])) return;
-  int valid = 0;
-  uint32_t taken = 0u;
-  const float lower = fusion_list32<false>(p, lr, lc, reg, F, up_in, lo_in, s_w, valid, taken);
-  if (valid < F.min_valid) return;
-  const float upper = fusion_list32<true>(p, lr, lc, reg, F, up_in, lo_in, s_w, valid, taken);
-  if (isfinite(lower) && isfinite(upper)) {
-    up_out[ci * up_stride] = upper;
-    lo_out[ci * lo_stride] = lower;
-  }
-}
-// The same with the neighbourhood staged in LDS: one block per 32 x 4 cells, both layers' tiles with a ring of
-// `halo` cells (NaN outside the stored window, so "outside" and "no data" are one test).  The two passes (lower
-// list, then upper) re-read LDS instead of L2, and a neighbour costs no 64-bit index arithmetic.
+// The neighbourhood is staged in LDS: one block per 32 x 4 cells, both layers' tiles with a ring of `halo` cells (NaN
+// outside the stored window, so "outside" and "no data" are one test).  The two passes (lower list, then upper)
+// read LDS, not L2, and a neighbour costs no 64-bit index arithmetic.
 constexpr int kFusTileR = 32, kFusTileC = kFusionThreads / kFusTileR, kFusHaloMax = 8;
 inline __global__ __launch_bounds__(kFusionThreads) void k_fusion_net32_tiled(const GeomConst G, const DevState* __restrict__ st,
                                                                        int slot, const RegionEntry* __restrict__ reg,
@@ -748,9 +585,9 @@ inline __global__ __launch_bounds__(kFusionThreads) void k_fusion_net32_tiled(co
   const size_t ci = post_index(p, lr, lc);
   int valid = 0;
   uint32_t taken = 0u;
-  const float lower = fusion_list32<false, true>(p, base, pitch, reg, F, s_up, s_lo, s_w, valid, taken);
+  const float lower = fusion_list32<false>(base, pitch, reg, F, s_up, s_lo, s_w, valid, taken);
   if (valid < F.min_valid) return;
-  const float upper = fusion_list32<true, true>(p, base, pitch, reg, F, s_up, s_lo, s_w, valid, taken);
+  const float upper = fusion_list32<true>(base, pitch, reg, F, s_up, s_lo, s_w, valid, taken);
   if (isfinite(lower) && isfinite(upper)) {
     up_out[ci * up_stride] = upper;
     lo_out[ci * lo_stride] = lower;
@@ -1132,10 +969,9 @@ __device__ __forceinline__ void features_store(const FeatureOut& O, size_t ci, c
   O.nz[ci] = normal[2];
 }
 
-// `step` needs two order statistics of the neighbourhood's heights (feature_extraction.cpp:100-103).
-// TOPK > 0: they are among the TOPK smallest / TOPK largest values, which are kept in registers by
-// unrolled compare-exchange chains (the host checks the percentiles make that true for the region);
-// TOPK == 0: any percentile pair, full insertion sort in scratch.
+// `step` needs two order statistics of the neighbourhood's heights (feature_extraction.cpp:100-103): they are among
+// the TOPK smallest / TOPK largest values, which are kept in registers by unrolled compare-exchange chains (the host
+// checks the percentiles make that true for the region; any other percentile pair: k_features_sel, k_features_big).
 template <int TOPK>
 __global__ __launch_bounds__(256) void k_features(const GeomConst G, const DevState* __restrict__ st, int slot,
                                                   const RegionEntry* __restrict__ reg, const FeatureParams F,
@@ -1150,12 +986,10 @@ __global__ __launch_bounds__(256) void k_features(const GeomConst G, const DevSt
   if (!isfinite(center_z)) return;
   float sum[3] = {0.f, 0.f, 0.f};
   float sq[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float zs[TOPK > 0 ? 1 : kMaxRegion];
-  float small[TOPK > 0 ? TOPK : 1], large[TOPK > 0 ? TOPK : 1];
-  if (TOPK > 0) {
+  static_assert(TOPK > 0, "the order statistics are kept in registers");
+  float small[TOPK], large[TOPK];
 #pragma unroll
-    for (int j = 0; j < TOPK; ++j) { small[j] = 3.402823466e+38f; large[j] = -3.402823466e+38f; }
-  }
+  for (int j = 0; j < TOPK; ++j) { small[j] = 3.402823466e+38f; large[j] = -3.402823466e+38f; }
   int count = 0;
   for (int e = 0; e < F.n_entries; ++e) {
     const RegionEntry re = reg[e];
@@ -1169,22 +1003,16 @@ __global__ __launch_bounds__(256) void k_features(const GeomConst G, const DevSt
     for (int c = 0; c < 3; ++c)
 #pragma unroll
       for (int r = 0; r < 3; ++r) sq[c * 3 + r] += d[r] * d[c];
-    if (TOPK > 0) {
-      float a = nz, b = nz;
+    float a = nz, b = nz;
 #pragma unroll
-      for (int j = 0; j < TOPK; ++j) {  // small[] ascending, large[] descending
-        const float lo_j = small[j], hi_j = large[j];
-        small[j] = a < lo_j ? a : lo_j;
-        a = a < lo_j ? lo_j : a;
-        large[j] = b > hi_j ? b : hi_j;
-        b = b > hi_j ? hi_j : b;
-      }
-      ++count;
-    } else {
-      int k = count++;  // z_vals kept sorted (std::sort at feature_extraction.cpp:100)
-      while (k > 0 && zs[k - 1] > nz) { zs[k] = zs[k - 1]; --k; }
-      zs[k] = nz;
+    for (int j = 0; j < TOPK; ++j) {  // small[] ascending, large[] descending
+      const float lo_j = small[j], hi_j = large[j];
+      small[j] = a < lo_j ? a : lo_j;
+      a = a < lo_j ? lo_j : a;
+      large[j] = b > hi_j ? b : hi_j;
+      b = b > hi_j ? hi_j : b;
     }
+    ++count;
   }
   if (count < F.min_valid) return;
   float cov[9], trace;
@@ -1194,19 +1022,12 @@ __global__ __launch_bounds__(256) void k_features(const GeomConst G, const DevSt
   if (val[1] < 1e-8f) return;  // kMinEigenvalue
   const int lo = static_cast<int>(F.lo_pct * float(count - 1));
   const int hi = static_cast<int>(F.hi_pct * float(count - 1));
-  float z_lo, z_hi;
-  if (TOPK > 0) {
-    const int from_top = count - 1 - hi;
-    z_lo = small[0];
-    z_hi = large[0];
+  const int from_top = count - 1 - hi;
+  float z_lo = small[0], z_hi = large[0];
 #pragma unroll
-    for (int j = 1; j < TOPK; ++j) {
-      z_lo = lo == j ? small[j] : z_lo;
-      z_hi = from_top == j ? large[j] : z_hi;
-    }
-  } else {
-    z_lo = zs[lo];
-    z_hi = zs[hi];
+  for (int j = 1; j < TOPK; ++j) {
+    z_lo = lo == j ? small[j] : z_lo;
+    z_hi = from_top == j ? large[j] : z_hi;
   }
   features_store(O, ci, val, normal, trace, z_lo, z_hi);
 }
@@ -1352,7 +1173,7 @@ __device__ __forceinline__ float vmax_f32(float a, float b) {
 }
 // Inserting a into an ascending list s that keeps its K smallest: new s[j] = max(s[j-1], min(a, s[j])) = the MEDIAN of
 // {s[j-1], a, s[j]} because s[j-1] <= s[j] — one v_med3_f32 per slot, every slot from the OLD list (no chain of
-// dependent min / max pairs: round 6, half the instructions of the two-instruction step).
+// dependent min / max pairs: half the instructions of a min / max step per slot).
 __device__ __forceinline__ float vmed3_f32(float a, float b, float c) {
   float r;
   asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -1374,7 +1195,7 @@ __device__ __forceinline__ void pin_sgpr(const FeatEntry& f) {
   asm volatile("" ::"s"(f.off), "s"(f.d0), "s"(f.d1), "s"(f.p00), "s"(f.p01), "s"(f.p11), "s"(f.one));
 }
 
-template <int KLO, int KHI = KLO, bool MED3 = true>
+template <int KLO, int KHI = KLO>
 __global__ __launch_bounds__(kFeatThreads) void k_features_tiled(const GeomConst G, const DevState* __restrict__ st, int slot,
                                                         const FeatEntry* __restrict__ tab, const FeatureParams F,
                                                         int halo, const float* __restrict__ elev, int elev_stride,
@@ -1421,28 +1242,13 @@ __global__ __launch_bounds__(kFeatThreads) void k_features_tiled(const GeomConst
     c11 += feat_v2f{fe.p11, fe.one};
     m02 += feat_v2f{fe.d0, fe.d1} * feat_v2f{d2, d2};
     z22 += feat_v2f{d2, d2 * d2};
-    if (MED3) {  // small[] ascending, large[] descending; slot j from the old slots j - 1 and j
+    // small[] ascending, large[] descending; slot j from the old slots j - 1 and j
 #pragma unroll
-      for (int j = KLO - 1; j > 0; --j) small[j] = vmed3_f32(small[j - 1], nz, small[j]);
-      small[0] = vmin_f32(nz, small[0]);
+    for (int j = KLO - 1; j > 0; --j) small[j] = vmed3_f32(small[j - 1], nz, small[j]);
+    small[0] = vmin_f32(nz, small[0]);
 #pragma unroll
-      for (int j = KHI - 1; j > 0; --j) large[j] = vmed3_f32(large[j - 1], nz, large[j]);
-      large[0] = vmax_f32(nz, large[0]);
-    } else {
-      float a = nz, b = nz;
-#pragma unroll
-      for (int j = 0; j < KLO; ++j) {
-        const float lo_j = small[j];
-        small[j] = vmin_f32(a, lo_j);
-        a = vmax_f32(a, lo_j);
-      }
-#pragma unroll
-      for (int j = 0; j < KHI; ++j) {
-        const float hi_j = large[j];
-        large[j] = vmax_f32(b, hi_j);
-        b = vmin_f32(b, hi_j);
-      }
-    }
+    for (int j = KHI - 1; j > 0; --j) large[j] = vmed3_f32(large[j - 1], nz, large[j]);
+    large[0] = vmax_f32(nz, large[0]);
   };
   int e = 0;
 #if FDM_FEAT_UNROLL == 8

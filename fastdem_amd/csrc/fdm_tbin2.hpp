@@ -187,7 +187,7 @@ __device__ __forceinline__ void tbin2_flush(const PT& P0, const GeomConst& G, co
       if (p0 == 0u) {
         t0_tile = tile; t0_n = n; t0_off = off;
       } else if (k < n_tile) {
-        const unsigned slot = atomicAdd(Q.cnt + (size_t(tile) << Q.cnt_shift), 1u);
+        const unsigned slot = atomicAdd(Q.cnt + (size_t(tile) << kCntShift), 1u);
         Q.desc[size_t(tile) * Q.stride + slot] = (unsigned long long)(b0 + off) | ((unsigned long long)n << 32);
       }
       base += uni(unsigned(__builtin_amdgcn_readlane(int(inc), 63)));
@@ -196,7 +196,7 @@ __device__ __forceinline__ void tbin2_flush(const PT& P0, const GeomConst& G, co
   __syncthreads();
   unsigned t0_slot = 0u;
 #ifndef FDM_X_NOATOM
-  if (wave == 0u && t0_n) t0_slot = atomicAdd(Q.cnt + (size_t(t0_tile) << Q.cnt_shift), 1u);
+  if (wave == 0u && t0_n) t0_slot = atomicAdd(Q.cnt + (size_t(t0_tile) << kCntShift), 1u);
 #endif
   // (e) the records, grouped by tile, into the block's own region of the pool
 #pragma unroll
@@ -295,15 +295,12 @@ __device__ __forceinline__ void tbin2_body(const PT& P, const GeomConst& G, cons
   const DevCand cand = H.finish(G, &s_cand, bid, n_pass);  // contains the __syncthreads
   const bool rare_block = uni(s_rare[0] | s_rare[1] | s_rare[2] | s_rare[3]) != 0u;  // block-uniform
   FDM_PHASE(0);  // table initialised, points transformed and cropped, candidate known
-  const int dbg = LEAN ? 0 : P.dbg_no_atomics;  // measurement only: leave the kernel after a stage (results are wrong)
-  if (dbg == 1) { bin_part[bid] = (zs[0] + zs[1] + zs[2] + zs[3] == 12345.f) ? 1ull : 0x100000001ull; return; }
   {
     const unsigned lz = opaque_zero();
     tbin_points<HAS_INT, THREADS, LEAN, true>(late<4>(P, lz), late<4>(G, lz), late<4>(TG, lz), cell_ids, cand, bid, xm, ym, pass, cells, n_in,
                                               any_glob);
   }
   FDM_PHASE(1);  // index done
-  if (dbg == 2) { bin_part[bid] = (cells[0] + cells[1] + cells[2] + cells[3] == 0x7FFFFFF1) ? 1ull : 0x100000001ull; return; }
   {  // statistics of this wavefront: surviving points / points in the owned window (ballots: no shuffles)
     unsigned np = 0u, ni = 0u;
 #pragma unroll
@@ -387,7 +384,6 @@ __device__ __forceinline__ void tbin2_body(const PT& P, const GeomConst& G, cons
     bin_part[bid] = (unsigned long long)np | ((unsigned long long)ni << 32);
   }
   FDM_PHASE(2);  // LDS fold done
-  if (dbg == 5) return;
   const unsigned n_rec = uni(s_nrec);
   if (n_rec <= 256u)
     tbin2_flush<HAS_INT, HAS_COL, LEAN, 1>(P, G, TG, I, Q, cand, rare_block, b0, n_rec, h_cell, h_key, h_zmax, h_imax, h_last,

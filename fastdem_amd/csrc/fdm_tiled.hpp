@@ -51,7 +51,7 @@ constexpr uint32_t kCitMask = (1u << kCitBits) - 1u;
 constexpr uint32_t kNoWinner = 0xFFFFFFFFu;
 constexpr uint32_t kOrdZero = 0x80000000u;  // ord(+0.0f)
 #ifndef FDM_UPD_WAVES
-#define FDM_UPD_WAVES 6  // min waves per SIMD the large-scan kernels are compiled for (<= 80 VGPRs): six blocks per CU are what the launch runs with (tiled_lds_pad)
+#define FDM_UPD_WAVES 6  // min waves per SIMD the large-scan kernels are compiled for (<= 80 VGPRs): six blocks per CU are what the launch runs with (tiled_lds_padded, fdm_engine_tiled.hip)
 #endif
 
 // flags beside the cell-in-tile number (8 bits) of a record
@@ -75,14 +75,14 @@ struct __align__(8) RecCold {
   float var;       // sigma_z^2 of the min-z point
   uint32_t rgb;    // colour of the block's last point in the cell
 };
+constexpr unsigned kCntShift = 5;  // one tile counter per 128 bytes (TilePool::cnt)
 // The record pool of one scan parity (bin of scan t+1 runs beside the update of scan t).
 struct TilePool {
   RecHot* hot;                // [cap]
   RecCold* cold;              // [cap]
-  unsigned* cnt;              // [n_tiles << cnt_shift] chunks of the tile (put back to 0 by the update); one counter per
-                              // 2^cnt_shift words: neighbouring tiles are hit by the same blocks at the same time, and
+  unsigned* cnt;              // [n_tiles << kCntShift] chunks of the tile (put back to 0 by the update); one counter per
+                              // 2^kCntShift words: neighbouring tiles are hit by the same blocks at the same time, and
                               // memory-side atomics on one line queue up
-  unsigned cnt_shift;
   unsigned long long* desc;   // [n_tiles][stride] one word per chunk: first record | count << 32
   unsigned stride;            // >= bin blocks of the scan: a block appends at most one chunk per tile
   uint32_t* rare;             // [update wavefronts][3][256] scratch of the update's rare path (first-occurrence words)
@@ -105,13 +105,12 @@ struct TileAux {           // what the update kernel keeps per tile between scan
 // of a million): strided, they spread over all wavefronts.  (Runs of 8 consecutive tiles per wavefront on such a map —
 // the tile counters lie one per 128 B, a run coalesces nothing — put configs[4]'s 5 600 live tiles on 700 of the 3 072
 // wavefronts: 176 us per launch against 37.)
-struct TileWork {
+// (alignas(16): the kernel arguments behind it — the fused launch's second ScanParams, Scratch, ScanInputs — stay on the
+// 16-byte boundaries their scalar loads are grouped by; as a bare 8 bytes it moved them, and the update kernels, which
+// sit at their 80-VGPR cap, spilled 4-8 bytes per lane more)
+struct alignas(16) TileWork {
   unsigned W;          // update wavefronts of the launch
   unsigned T;          // tiles per wavefront
-  unsigned prio;       // 1: the update wavefronts raise their issue priority (option "upd_prio")
-  unsigned stagger;    // fused launch: start delay of the first-round bin blocks, in units of 512 cycles per resident slot (option "bin_stagger")
-  unsigned delay;      // fused launch: the first `delay_blocks` bin blocks wait this many units of 512 cycles before their first load
-  unsigned delay_blocks;  //            (option "bin_delay": the update wavefronts' first round trip goes ahead of 12 MB of point loads)
 };
 
 // value of a canonicalised ord word; `neg`: the first zero seen was -0 (only looked at for a zero)
@@ -586,7 +585,7 @@ __device__ __forceinline__ void tupdate_tile(
         POLICY::set_nan(stt);
       } else {
         POLICY::load(L, o, stt);
-        if (has_int && !(P.dbg_upd & 2)) sint = L.intensity[size_t(o) * L.istride];
+        if (has_int) sint = L.intensity[size_t(o) * L.istride];
         if (strip) POLICY::set_nan_basic(stt);
       }
       const float min_z = wl != kNoWinner ? signed_value(uint32_t(key >> 32), wl & 1u) : kFltMax;
@@ -594,7 +593,7 @@ __device__ __forceinline__ void tupdate_tile(
       if (A.ras_z) A.ras_z[o] = min_z;
       POLICY::update(L, o, stt, min_z, var, max_z);
       s_obst[lc] = (max_z > min_z) ? max_z : nanv;  // (stored with the tile's other cells below)
-      if (has_int && !(P.dbg_upd & 2)) {
+      if (has_int) {
         const float obs = (fst & 1u) ? nanv  // first point NaN -> stays NaN (elevation_mapping.cpp:73-79)
                                      : signed_value(im, izw & 1u);
         if (isnan(sint) || obs > sint) L.intensity[size_t(o) * L.istride] = obs;
@@ -605,7 +604,7 @@ __device__ __forceinline__ void tupdate_tile(
   // The obstacle layer of the whole tile, four 64-byte column segments per store: map_.clear(obstacle)
   // (elevation_mapping.cpp:144-146) for the untouched cells and the touched cells' values in ONE dense pass — as 163 K
   // scattered 4-byte stores the touched cells were a third of the launch's write requests.
-  if (obst_tile && !(P.dbg_upd & 1)) {  // (dbg_upd: measurement only — results are wrong)
+  if (obst_tile) {
     wave_sync();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -620,7 +619,7 @@ __device__ __forceinline__ void tupdate_tile(
   if (lane == 0u) {
     A.upd_part[tile] = n_touched;
     if (n_chunks) {
-      Q.cnt[size_t(tile) << Q.cnt_shift] = 0u;
+      Q.cnt[size_t(tile) << kCntShift] = 0u;
       if (u.do_update) A.stamp[tile] = P.scan_no;
     }
   }
@@ -638,7 +637,7 @@ __device__ __forceinline__ void tupdate_wave(
   // An update wavefront is a chain of dependent round trips with a few hundred instructions between them; beside
   // six arithmetic-bound bin wavefronts per SIMD every one of those instructions waits its turn.  Priority 3: its
   // instructions issue first (it is idle most of the time, the bin wavefronts lose next to nothing).
-  if (K.prio) __builtin_amdgcn_s_setprio(3);
+  __builtin_amdgcn_s_setprio(3);
   TileCtx u;
   make_tile_ctx(P, st, u, w == 0u && lane == 0u);
   if (w >= K.W) return;  // (a surplus wavefront of the grid owns nothing)
@@ -654,7 +653,7 @@ __device__ __forceinline__ void tupdate_wave(
     const unsigned tile = k * K.W + w;
     const bool valid = k < K.T && tile < TGp.n_tiles;
     unsigned nch = 0u, stamp = 0xFFFFFFFFu;
-    if (valid) { nch = Qp.cnt[size_t(tile) << Qp.cnt_shift]; stamp = Ap.stamp[tile]; }
+    if (valid) { nch = Qp.cnt[size_t(tile) << kCntShift]; stamp = Ap.stamp[tile]; }
     // (the tile's row / column in the tile grid: one division per lane and pass instead of one per tile)
     const unsigned tr = tile % unsigned(TGp.tiles_r), tc = tile / unsigned(TGp.tiles_r);
     const bool hits = valid && u.strips &&
@@ -696,7 +695,7 @@ template <typename POLICY, bool HAS_INT, bool HAS_COL, int THREADS, bool LEAN>
 __global__ __launch_bounds__(THREADS, FDM_UPD_WAVES) void k_tupdate_tbin(
     const ScanParams Pu, const GeomConst G, const TileGrid TG, DevState* __restrict__ st,
     const typename POLICY::Layers L, float* const* __restrict__ all_layers, int n_layers,
-    const TilePool Qu, const TileAux A, const TileWork K, unsigned upd_blocks, const ScanParams Pb,
+    const TilePool Qu, const TileAux A, const TileWork K, unsigned n_upd_blocks, const ScanParams Pb,
     const ScanInputs Ib, const Scratch Sb, const TilePool Qb, int32_t* __restrict__ cell_ids) {
   static_assert(THREADS == 256, "256-thread blocks");
   extern __shared__ __align__(16) unsigned char dyn_lds[];
@@ -704,22 +703,12 @@ __global__ __launch_bounds__(THREADS, FDM_UPD_WAVES) void k_tupdate_tbin(
 #if FDM_MB_PHASES
   if (threadIdx.x == 0) { g_phase[0] = g_phase[1] = g_phase[2] = unsigned(t0); }
 #endif
-  if (blockIdx.x < upd_blocks) {
+  if (blockIdx.x < n_upd_blocks) {
     const unsigned wave = uni(threadIdx.x >> 6);  // (wave-uniform: everything derived from it lives in scalar registers)
     tupdate_wave<POLICY, HAS_INT, HAS_COL>(Pu, G, TG, st, L, all_layers, n_layers, Qu, A, K,
                                            dyn_lds + wave * tile_wave_lds_bytes(HAS_INT, HAS_COL), blockIdx.x * 4u + wave);
   } else {
-    const unsigned bb = blockIdx.x - upd_blocks;
-    // The first ~1 300 bin blocks start in the same microsecond and ask for most of the scan at once: for 6-7 us
-    // the chip waits for memory, then every SIMD's seven wavefronts compete for issue slots in the same phase.  A
-    // stagger (block k of a CU's first round waits k x `stagger` x 512 cycles) lets the early blocks' arithmetic run
-    // under the late blocks' loads.
-    if (K.stagger) {
-      const unsigned slot = (bb >> 8) & 7u;
-      for (unsigned i = 0; i < slot * K.stagger && bb < 2048u; ++i) __builtin_amdgcn_s_sleep(8);
-    }
-    if (K.delay && bb < K.delay_blocks)
-      for (unsigned i = 0; i < K.delay; ++i) __builtin_amdgcn_s_sleep(8);
+    const unsigned bb = blockIdx.x - n_upd_blocks;
     TbinRing H(Pb, st);
     tbin2_body<HAS_INT, HAS_COL, LEAN>(Pb, G, TG, H, Ib, Sb, Sb.bin_part, Qb, cell_ids, dyn_lds, bb);
   }

@@ -1017,15 +1017,10 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2);
  * csrc/fdm_engine_host.hpp carries the measurements behind each default); tests/test_option_table.py keeps the two alike.
  *  the scan path
  *   "wave_merge" 0/1        : k_bin merges same-cell runs inside the wavefront before the atomics (default 1)
- *   "bin_table" 0/1         : k_bin folds poorly merged waves into a per-block LDS cell table before the atomics (1)
  *   "bin_variant" 0/1/4     : bin kernel by scan size (0, default), one point per thread (1), LDS-staged (4)
  *   "overlap" 0/1           : hold the update of a small scan back and fuse it with the next scan's bin launch (1)
- *   "borrow_inputs" 0/1     : a held-back update gathers from the CALLER's device arrays, which then stay untouched until
- *                             the next-but-one scan is enqueued or a flush (default 0: the engine keeps a staging copy)
  *   "zero_copy" n           : host entry points read PINNED input arrays of up to n points in place (default 2^30;
  *                             0 = always copy)
- *   "sync_spin_us" n        : a synchronous call polls the pinned statistics block for up to n microseconds before it
- *                             falls back to a stream wait (default 150; 0 = wait at once)
  *   "records" 0/1           : estimator state packed into per-cell records (1, default) or one array per layer (0)
  *   "dense" 0/1             : update sweep visits every tile (1) or only stamped tiles (0); default: 1 on maps of up to
  *                             4 M cells
@@ -1035,18 +1030,6 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2);
  *   "tiled" 0/1             : on / off (default 1)
  *   "tiled_min" n           : ... for scans from n points up (default 2048, on maps with enough tiles; a value set by hand
  *                             lifts the map-size condition)
- *   "upd_blocks" n          : update blocks (four tile wavefronts each) of a fused large-scan launch (1 .. 65535, default 768)
- *   "upd_blocks_alone" n    : ... of an update launch of its own (default 2048)
- *   "upd_prio" 0/1          : the update wavefronts raise their issue priority (default 1)
- *   "tiled_lds_pad" n       : extra dynamic LDS per block of the large-scan launches, bytes (0 .. 122880); default -1 = as
- *                             much as makes it six blocks per CU instead of seven
- *   "cnt_shift" 0..5        : one tile counter per 2^n words of the counter array (default 5 = one per 128 bytes:
- *                             memory-side atomics on one line queue up); before the first large scan only
- *   "bin_delay" n           : measurement: the first bin blocks of a fused large-scan launch wait n x 512 cycles before
- *                             their first load (0 .. 65535, default 0)
- *   "bin_delay_blocks" n    : ... the first n of them (default 1024)
- *   "bin_stagger" n         : fused large-scan launch: start stagger of the first-round bin blocks, n x 512 cycles per
- *                             resident slot (0 .. 64, default 0)
  *  the batch pipeline (fdm_engine_integrate_device_batch)
  *   "batch" 0/1             : group small scans into batch launches (default 1)
  *   "batch_max" n           : scans per launch, 2 .. 32; default 0 = automatic: 32 with the quantile estimator or with
@@ -1058,7 +1041,6 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2);
  *   "batch_ray_seg" 1/4/8/16: lanes per ray of its walk on memory-side atomics (default 4)
  *   "batch_ray_lds" 0/1     : its walk on LDS images (1, default) or always on memory-side atomics (0)
  *   "batch_ray_parts" n     : workgroups per quadrant and scan of the LDS walk (0 .. 64; default 0 = fill the chip)
- *   "batch_ray_words" n     : LDS image words of that walk (default 0 = twice a centred sensor's quadrant)
  *  the raycasting stage
  *   "voxel_small" 0/1       : the voxel filter without a sort for small scans (default 1; fdm_raycast.hpp k_vs_*); 0 = every
  *                             scan through the stable radix sort
@@ -1069,21 +1051,16 @@ int fdm_engine_last_kernel_ms(fdm_engine* e, float* ms2);
  *                             While it is 1 the sort-free small-scan filter is not used, and batch calls with raycasting on
  *                             take the scan-by-scan path (batch launches without raycasting are unaffected).  A held-back
  *                             stage leaves before the value changes
- *   "ray_hold" 0/1          : a scan's raycasting stage is held back together with its map update and runs right behind it —
- *                             in the next scan's launch sequence (the update then shares a launch with that scan's bin half) or
- *                             at the next flush (default 1; 0 = update and stage at once, the round-1..4 order)
  *   "ray_large_min" n       : raycasting of scans from n points up takes the large-scan path (default 196608): ray queue
  *                             ordered by (angular sector, length class)
  *   "ray_wedge" 0/1         : ... and walks it with the sector's minimum-height window in LDS (fdm_raywedge.hpp, default 1;
  *                             0 = one lane per ray on memory-side atomics)
- *   "ray_wedge_parts" n     : workgroups per sector of that walk (0 = by the scan's size, the default; 1 .. 16: measurement)
  *   "ray_overlap" -1/0/1    : the stage's map-independent part (voxel filter, queue, walk) of a large scan leaves on a stream of its
  *                             own as soon as the scan's bin half has run, its resolve stays behind the scan's update (0, default:
  *                             never; 1 whenever possible; -1 for synchronous calls and scans of >= 1 M points).  Worth 10-14 % in a
  *                             process with few active streams, a loss in one with many
  *  measurement only (scripts/ab_kernels.py and the probes beside it; all default 0)
- *   "dbg_no_atomics" n      : results are wrong when set
- *   "dbg_upd" n, "dbg_batch" n, "dbg_ray" n, "dbg_post" n : bit switches of the update, batch, raycasting and stencil kernels
+ *   "dbg_batch" n, "dbg_ray" n : bit switches of the batch and raycasting kernels
  *   "dbg_timeline" 0/1      : block start / end ticks of the fused large-scan launches (fdm_engine_debug_timeline) */
 int fdm_engine_set_option(fdm_engine* e, const char* key, int value);
 

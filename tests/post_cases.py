@@ -76,7 +76,7 @@ def need_lo_hi(n_entries, lo_pct, hi_pct):
 
 
 def median_kernel(kernel):
-    """The dispatch of fdm_engine_apply_spatial_smoothing without a debug bit."""
+    """The dispatch of fdm_engine_apply_spatial_smoothing."""
     side = 2 * (kernel // 2) + 1
     if kernel == 3:
         return "k_median3_tiled"
@@ -93,18 +93,18 @@ def fusion_n_pad(n_entries):
 
 
 def fusion_kernel(radius, q_lower, q_upper, res=RES):
-    """The dispatch of fdm_engine_apply_uncertainty_fusion without a debug bit."""
+    """The dispatch of fdm_engine_apply_uncertainty_fusion."""
     n, halo = region_disc(radius, res)[0].size, reach(radius, res)
     q_ok = all(F32(1e-6) <= F32(q) <= F32(1.0) for q in (q_lower, q_upper))
     if n <= 29 and halo <= FUS_HALO_MAX and q_ok:
         return "k_fusion_f64_tiled<%d, true>" % n if n in (29, 25, 21, 13, 9, 5) else "k_fusion_f64_tiled<29, false>"
-    if n <= 32:
-        return "k_fusion_net32_tiled" if halo <= FUS_HALO_MAX else "k_fusion_net32"
-    return "k_fusion_wave" if n <= FUSION_WAVE_MAX else "k_fusion_big"   # (kFusionWaveMax >= kMaxRegion: k_fusion<> is behind it)
+    if n <= 32 and halo <= FUS_HALO_MAX:
+        return "k_fusion_net32_tiled"
+    return "k_fusion_wave" if n <= FUSION_WAVE_MAX else "k_fusion_big"
 
 
 def features_kernel(radius, lo_pct, hi_pct, res=RES):
-    """The dispatch of fdm_engine_apply_feature_extraction without a debug bit."""
+    """The dispatch of fdm_engine_apply_feature_extraction."""
     n, halo = region_disc(radius, res)[0].size, reach(radius, res)
     need_lo, need_hi = need_lo_hi(n, lo_pct, hi_pct)
     pct_ok = 0.0 <= F32(lo_pct) <= 1.0 and 0.0 <= F32(hi_pct) <= 1.0
@@ -116,9 +116,7 @@ def features_kernel(radius, lo_pct, hi_pct, res=RES):
         return "k_features_tiled<16>"
     if near:
         return "k_features<8>" if need_lo <= 8 and need_hi <= 8 else "k_features<16>"
-    if features_sel_lds_bytes(halo, n) <= LDS_CAP:
-        return "k_features_sel"
-    return "k_features<0>" if n <= K_MAX_REGION else "k_features_big"
+    return "k_features_sel" if features_sel_lds_bytes(halo, n) <= LDS_CAP else "k_features_big"
 
 
 def cells(c):

@@ -75,12 +75,58 @@ def _names_passed(text):
     return set(re.findall(r'set_option\(\s*(?:[^,"()]+(?:\([^()]*\))?\s*,\s*)?"(\w+)"', text))
 
 
-def test_every_name_the_callers_pass_is_in_the_table():
+def _caller_files(scripts=False):
     files = [os.path.join(ROOT, "bench.py")]
     files += glob.glob(os.path.join(ROOT, "tests", "*.py"))
     files += glob.glob(os.path.join(ROOT, "fastdem_amd", "*.py"))
     for d, _, names in os.walk(os.path.join(ROOT, "fastdem_amd", "cpp")):
         files += [os.path.join(d, n) for n in names if n.endswith((".hpp", ".h", ".cpp", ".py", ".txt"))]
+    if scripts:
+        files += glob.glob(os.path.join(ROOT, "scripts", "*.py"))
+    return files
+
+
+# Retired with the code only they reached (LABNOTES.md, "Retired: the stencil debug bits and sixteen unset options").
+RETIRED = ("dbg_post", "bin_table", "borrow_inputs", "sync_spin_us", "upd_blocks", "upd_blocks_alone", "upd_prio",
+           "tiled_lds_pad", "cnt_shift", "bin_delay", "bin_delay_blocks", "bin_stagger", "batch_ray_words", "ray_hold",
+           "ray_wedge_parts", "dbg_no_atomics", "dbg_upd")
+
+
+def _names_set(text):
+    """Names a file sets: a literal handed to set_option, `key=value` inside a string (the `--set` switch of bench.py and
+    the scripts), or — in a file that hands set_option a variable key — a quoted dictionary key with an integer value."""
+    names = _names_passed(text)
+    names |= set(re.findall(r'''["',](\w+)=-?\d''', text))
+    if re.search(r"set_option\(\s*[A-Za-z_]\w*\s*,", text):
+        names |= set(re.findall(r'"(\w+)":\s*-?\d', text))
+    return names
+
+
+def test_every_option_of_the_table_is_set_by_some_caller():
+    """A row nobody sets is code nobody runs: the benchmark, a test, the package, the C++ mirror or a script under
+    scripts/ sets every option of the table at least once."""
+    this = os.path.abspath(__file__)
+    used = set()
+    for f in _caller_files(scripts=True):
+        if os.path.abspath(f) != this:
+            used |= _names_set(_read(f))
+    unset = [n for n, _ in table_rows() if n not in used]
+    assert not unset, unset
+    assert not set(RETIRED) & {n for n, _ in table_rows()}
+
+
+def test_retired_names_are_gone_from_the_sources():
+    assert len(set(RETIRED)) == 17
+    files = glob.glob(os.path.join(CSRC, "*")) + glob.glob(os.path.join(ROOT, "include", "*"))
+    assert len(files) > 40
+    word = re.compile(r"\b(%s)\b" % "|".join(RETIRED))
+    found = {os.path.relpath(f, ROOT): sorted(set(word.findall(_read(f)))) for f in files if os.path.isfile(f)}
+    found = {f: names for f, names in found.items() if names}
+    assert not found, found
+
+
+def test_every_name_the_callers_pass_is_in_the_table():
+    files = _caller_files()
     known = {n for n, _ in table_rows()}
     passed = {}
     for f in files:

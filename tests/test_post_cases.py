@@ -1,6 +1,5 @@
 """tests/post_cases.py on the CPU: the cases do what they are meant to (on the oracle alone), the kernel names they expect
-are the launch sites of fdm_engine_post.inl — all of them but the ones only a debug bit reaches — and the thresholds
-restated there are the source's."""
+are the launch sites of fdm_engine_post.inl, every one of them, and the thresholds restated there are the source's."""
 import os
 import re
 
@@ -12,20 +11,6 @@ import post_cases as PC
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fastdem_amd", "csrc")
 IDS = [c.id for c in PC.CASES]
-
-# Launch sites no plain call reaches: each needs a `dbg_post` / `dbg_ray` bit (engine options kept for measurements).
-DEBUG_ONLY = {
-    "k_inpaint_pass": "dbg_post 4: the inpainting pass without the LDS tile",
-    "k_median3": "dbg_post 4: the 3 x 3 median without the LDS tile",
-    "k_fusion_net32": "dbg_ray 1024 / dbg_post 2: no disc of <= 32 cells reaches farther than kFusHaloMax",
-    "k_fusion<true>": "dbg_post 16: kFusionWaveMax >= kMaxRegion, k_fusion_wave takes every disc this one would",
-    "k_fusion<false>": "dbg_post 16: the same",
-    "k_features<0>": "dbg_post 8: a region of <= kMaxRegion entries never exceeds the LDS of k_features_sel",
-    "k_features_tiled<8, 8, false>": "dbg_post 64: the two-instruction insertion chains",
-    "k_features_tiled<16, 16, false>": "dbg_post 64: the same",
-}
-# (k_fusion_f64_tiled<29, false> is NOT here: dbg_post 128 forces it, but a disc of one cell — a radius below the
-#  resolution — takes it without any bit, and tests/test_post_gpu.py asserts that)
 
 
 def source(name):
@@ -60,8 +45,6 @@ def test_restated_constants_are_the_sources():
     assert "static_cast<int>(lo_pct * float(nmax - 1)) + 1" in inl
     assert "(nmax - 1) - static_cast<int>(hi_pct * float(nmax - 1)) + 1" in inl
     assert "if (d2 <= r2 * (1.0f + 1e-5f)) reg.push_back" in inl and "std::floor(radius / res + 1e-4f)" in inl
-    # k_fusion<> sits behind k_fusion_wave: only a debug bit reaches it
-    assert PC.FUSION_WAVE_MAX >= PC.K_MAX_REGION
 
 
 def test_thresholds():
@@ -86,6 +69,24 @@ def test_thresholds():
     assert 9 <= lo <= 16 and 9 <= hi <= 16
 
 
+def test_no_region_within_kmaxregion_exceeds_the_lds_of_features_sel():
+    """The feature dispatch has no arm between k_features_sel and k_features_big: every disc of at most kMaxRegion cells
+    fits the LDS of k_features_sel (the static_assert beside the dispatch states the same with its bound of 11 cells)."""
+    seen = set()
+    for hundredths in range(0, 1301):             # radii of 0 .. 13 cells: the disc of 9.06 cells is the first beyond 256
+        radius = PC.cells(hundredths / 100.0)
+        n, halo = PC.region_disc(radius)[0].size, PC.reach(radius)
+        if n <= PC.K_MAX_REGION:
+            seen.add((halo, n))
+            assert halo <= 11 and PC.features_sel_lds_bytes(halo, n) <= PC.LDS_CAP, (hundredths, halo, n)
+        else:
+            assert hundredths > 900, hundredths       # (the count only grows with the radius)
+    assert max(n for _, n in seen) == 253 and max(h for h, _ in seen) == 9
+    assert PC.features_sel_lds_bytes(11, PC.K_MAX_REGION) <= PC.LDS_CAP
+    inl = source("fdm_engine_post.inl")
+    assert "160u * 1024u >= features_sel_lds_bytes(11, kMaxRegion)" in inl and "kMaxRegion < 17 * 17" in inl
+
+
 def recorded_names():
     """Every name a launch site of the four stages records: the argument of FDM_POST_KERNEL(...)."""
     inl = source("fdm_engine_post.inl")
@@ -108,13 +109,11 @@ def asserted_in_test_post_gpu():
 
 
 def test_every_launch_site_is_expected_by_a_test():
-    """parsed launch sites - DEBUG_ONLY == names of the case table + names asserted in test_post_gpu.py: a launch site
-    added without a test fails here, and so does a test that expects a name no site records."""
+    """parsed launch sites == names of the case table + names asserted in test_post_gpu.py: a launch site added without
+    a test fails here, and so does a test that expects a name no site records."""
     sites = recorded_names()
-    assert set(DEBUG_ONLY) <= sites, set(DEBUG_ONLY) - sites
     expected = {c.kernel for c in PC.CASES if c.kernel} | asserted_in_test_post_gpu()
-    assert sites - set(DEBUG_ONLY) == expected, (sorted(sites - set(DEBUG_ONLY) - expected),
-                                                 sorted(expected - (sites - set(DEBUG_ONLY))))
+    assert sites == expected, (sorted(sites - expected), sorted(expected - sites))
     # and the table alone reaches what no test ran before it
     table = {c.kernel for c in PC.CASES}
     assert {"k_median_big", "k_fusion_big", "k_features_big", "k_features<8>", "k_features<16>", "k_fusion_wave",
