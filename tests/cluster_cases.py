@@ -6,7 +6,15 @@ file's); its rand() scenes are rebuilt with a seeded generator on the same latti
 ADMISSION (asserted by tests/test_cluster_restate.py): a case other than the dyadic ones is here only if every pair of it
 whose float64 squared distance lies within r_sq (1 +- 1e-5) gets the same decision under the three fp32 summation orders
 and with fused multiply-add.  The seeded scenes are therefore laid on the lattice of 2^-10: there every difference, every
-square and every sum of the squared distance is exact in fp32, whatever the order."""
+square and every sum of the squared distance is exact in fp32, whatever the order.
+
+Thresholds this table crosses, with the kernel and the constant each comes from (the long lists are in
+tests/cluster_cases_large.py, with theirs):
+  32 key bits     k_cluster_keys packs [z][y][x] over the voxels' bounding box (cluster::box, at most 21 bits a field) and
+                  k_cluster_ranges bisects the sorted keys: wide_33_bits has 11 + 11 + 11, wide_corners 21 + 21 + 21 = 63
+  voxel range     cluster_voxel_of accepts -2^20 + range .. 2^20 - 1 - range: wide_corners has blobs AT both ends (range
+                  1), errors() "voxel_at_edge" / "voxel_beyond" the first values refused
+  index check     k_seg_index_check's grid is capped at 2048 blocks of 256: errors() "index_last_of_524289"."""
 import functools
 
 import numpy as np
@@ -128,6 +136,48 @@ def mixed_scene(n=70000, seed=70000):
     return _xyz(pts[rng.permutation(n)])
 
 
+def wide_corners(seed=63):
+    """Blobs of 12 .. 20 points at the accepted corner voxels of tolerance 0.5 — -2^20 + 1 and 2^20 - 2 on every axis,
+    coordinates on the lattice of 2^-5, which is exact at that magnitude — and blobs near the origin: the voxels' box is
+    2^21 - 2 wide on every axis, the sort key 21 + 21 + 21 = 63 bits (k_cluster_keys, k_cluster_ranges' bisection over
+    them, eight radix passes).  One corner blob straddles the corner voxel and its inner neighbour."""
+    rng = np.random.default_rng(seed)
+    lo, hi = (-2.0 ** 20 + 1) * 0.5, (2.0 ** 20 - 2) * 0.5
+    parts = []
+    for k, corner in enumerate(((lo, lo, lo), (hi, hi, hi), (lo, hi, lo), (hi, lo, hi), (hi, hi, lo))):
+        parts.append(np.asarray(corner)[None, :] + rng.integers(0, 8, (12 + 2 * k, 3)) / 32.0)
+    parts.append(np.asarray((hi - 0.25, lo, lo))[None, :] + rng.integers(0, 17, (40, 3)) // np.asarray([1, 2, 2]) / 32.0)
+    parts.append(np.asarray((lo, lo, lo))[None, :] + np.asarray([[3.0, 0.0, 0.0], [0.0, 3.0, 0.0]]))  # two singletons
+    pts = np.concatenate(parts + [np.stack(blobs(6, 15, seed, centre=-2.0), axis=1).astype(np.float64)])
+    assert np.array_equal(pts.astype(F).astype(np.float64), pts)
+    return _xyz(pts[rng.permutation(pts.shape[0])])
+
+
+def wide_33_bits(seed=33):
+    """Blobs at the origin and 600 away on every axis (voxel 1200: 11 bits a field, a 33-bit key, five radix passes); the
+    blob at (0, 0, 600) and the one at (0, 0, 88) differ in bit 32 of the key and above only."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for k, c in enumerate(((0, 0, 0), (600, 600, 600), (0, 0, 600), (0, 0, 88), (600, 0, 0), (0, 600, 88), (300, 300, 300))):
+        parts.append(np.asarray(c, dtype=np.float64)[None, :] + rng.integers(-100, 101, (11 + 3 * k, 3)) / 1024.0)
+    pts = np.concatenate(parts)
+    return _xyz(pts[rng.permutation(pts.shape[0])])
+
+
+def sort_keys(cloud, tolerance=0.5, indices=None):
+    """(key_bits, the key of every list position): what fdm_cloud_cluster's first sort orders by — [z][y][x] over the
+    voxels' bounding box (cluster::box in fdm_cluster_host.hpp)."""
+    pts, _ = CR._points(*cloud, indices)
+    vox = CR.voxels(pts, CR.relation_constants(tolerance)[0])
+    u = vox - vox.min(axis=0)[None, :]
+    bits = [max(int(u[:, k].max()).bit_length(), 1) for k in range(3)]
+    keys = (u[:, 2] << (bits[0] + bits[1])) | (u[:, 1] << bits[0]) | u[:, 0]
+    return sum(bits), keys
+
+
+KEY_BITS = {"wide_corners": 63, "wide_33_bits": 33}
+
+
 @functools.lru_cache(maxsize=None)
 def cases():
     """name -> (cloud, keyword arguments of euclidean_cluster)."""
@@ -165,6 +215,9 @@ def cases():
         "subset_ascending": (mid, dict(tolerance=0.5, indices=ascending)),
         "subset_shuffled": (mid, dict(tolerance=0.5, indices=shuffled)),
         "subset_duplicate": (mid, dict(tolerance=0.5, indices=dup)),
+        "wide_corners": (wide_corners(), dict(tolerance=0.5, min_size=1)),
+        "wide_corners_min10": (wide_corners(), dict(tolerance=0.5)),
+        "wide_33_bits": (wide_33_bits(), dict(tolerance=0.5)),
     }
     for n in (63, 64, 65, 255, 256, 257, 4097):
         table[f"line{n}"] = (chain(n, 0.5, (1, 0, 0), n), dict(tolerance=0.5))
@@ -212,6 +265,16 @@ def components(name):
     return CR.components_brute(*cloud, kw.get("tolerance", 0.5), kw.get("indices"))
 
 
+INDEX_CHECK_SWEEP = 2048 * 256
+
+
+def index_check_stride(n):
+    """A list of INDEX_CHECK_SWEEP + 1 entries into a cloud of n points whose only bad entry is the last one."""
+    idx = (np.arange(INDEX_CHECK_SWEEP + 1, dtype=np.uint64) * 7919 % n).astype(np.uint32)
+    idx[-1] = n
+    return idx
+
+
 @functools.lru_cache(maxsize=None)
 def errors():
     """name -> (cloud, keyword arguments, a word of the message): what fdm_cloud_cluster refuses."""
@@ -233,4 +296,6 @@ def errors():
         "tol_nan": (base, dict(tolerance=np.nan), "tolerance"),
         "tol_infinite": (base, dict(tolerance=np.inf), "tolerance"),
         "index_beyond": (base, dict(indices=np.asarray([0, 5, base[0].size, 7], dtype=np.uint32)), "index"),
+        # k_seg_index_check's grid is capped at 2048 blocks of 256: entry 524 288 is read by its strided loop only
+        "index_last_of_524289": (base, dict(indices=index_check_stride(base[0].size)), "index"),
     }

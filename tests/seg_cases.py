@@ -1,7 +1,15 @@
 """The case table of the segmentation tests (tests/test_seg_restate.py on the CPU, tests/test_segment_gpu.py on the
 GPU): clouds, configurations, and the restatement's answers (tests/seg_restate.py), computed once per process and shared.
 The rand-free clouds are those of nanoPCL's tests/test_segmentation.cpp (line numbers: that file's); every other cloud is
-seeded, so neither test needs a reference file."""
+seeded, so neither test needs a reference file.
+
+Thresholds this table crosses, with the kernel and the constant each comes from (the long lists are in
+tests/seg_cases_large.py, with theirs):
+  32 key bits     k_seg_pack_keys packs [gy][gx] over the cells' bounding box and fdm_cloud_segment_ground's second sort
+                  takes bits_x + bits_y bits of it (seg_bits, eight per radix pass): wide_bits33 has 17 + 16, wide_bits64
+                  and wide_extremes 32 + 32 — bits_x = 32, where the shift is a whole word
+  int32 floors    seg_cell_of accepts floor(v / r) in [-2^31, 2^31): wide_extremes holds both ends, ground_errors()
+                  "floor_exactly_2_31" the first value refused"""
 import functools
 
 import numpy as np
@@ -181,6 +189,63 @@ def ground_large(n=70000):
     return x[p], y[p], z[p]
 
 
+def ground_wide(kind, n=300):
+    """A cloud of n points whose cell box (resolution 0.5) is too wide for a 32-bit cell key — k_seg_pack_keys packs
+    [gy][gx] over the box and the second sort takes bits_x + bits_y bits of it:
+      "bits33"    2^17 x 2^16 cells: 17 + 16 bits, five radix passes
+      "bits64"    groups near x, y = +-1.0e9 (cells near +-2.0e9): 32 + 32 bits, eight passes, a shift by a whole word
+      "extremes"  the same widths from the accepted extremes themselves: a floor of exactly -2^31 and the largest float
+                  below 2^31
+    Twenty groups of six points with exactly equal x, y and different z, so that runs and the percentile pick happen at
+    those magnitudes; the groups come in pairs (P, Q) in cells that differ in a key bit above 31 only: P's z is
+    0 .. 0.1, Q's 0.35 .. 0.45 — ground in a cell of its own, obstacles if Q were taken for a part of P's cell.  The other
+    points share a few hundred cells inside the box, one to a few each."""
+    rng = np.random.default_rng({"bits33": 33, "bits64": 64, "extremes": 31}[kind])
+    if kind == "bits33":   # coordinates k / 2 + 0.25: exact
+        px = np.concatenate([[0, 2 ** 17 - 1], rng.integers(0, 2 ** 17, 8)]) * 0.5 + 0.25
+        py = np.concatenate([[0, 2 ** 15 - 1], rng.integers(0, 2 ** 15, 8)]) * 0.5 + 0.25
+        qx, qy = px, py + 2.0 ** 14  # 2^15 cells on: bit 15 of gy, bit 32 of the key
+        fx = rng.integers(0, 2 ** 17, 20)[rng.integers(0, 20, n)] * 0.5 + 0.25
+        fy = rng.integers(0, 2 ** 16, 20)[rng.integers(0, 20, n)] * 0.5 + 0.25
+    else:                  # floats near 1e9 are 64 apart, those below 2^30 too
+        lo, hi = (-1.0e9, 1.0e9) if kind == "bits64" else (-2.0 ** 30, 2.0 ** 30 - 64.0)
+        step = 64.0 * rng.integers(0, 1000, 10)
+        px = np.where(np.arange(10) % 2 == 0, lo + step, hi - step)
+        px[:2] = lo, hi
+        py = np.full(10, lo) + 64.0 * np.arange(10)
+        qx, qy = px, np.full(10, hi) - 64.0 * np.arange(10)  # the same gx, the far end of gy
+        fx = np.where(rng.integers(0, 2, n) == 0, lo, hi) + 64.0 * rng.integers(-8, 9, n) * (1 if kind == "bits64" else 0)
+        fy = rng.integers(-2 ** 23, 2 ** 23, 30)[rng.integers(0, 30, n)] * 64.0
+    gx, gy = np.repeat(np.concatenate([px, qx]), 6), np.repeat(np.concatenate([py, qy]), 6)
+    gz = np.concatenate([rng.uniform(0.0, 0.1, 60), rng.uniform(0.35, 0.45, 60)])
+    k = n - 120
+    x, y = np.concatenate([gx, fx[:k]]), np.concatenate([gy, fy[:k]])
+    z = np.concatenate([gz, rng.uniform(0.0, 1.0, k)])
+    p = rng.permutation(n)
+    cloud = x[p].astype(F), y[p].astype(F), z[p].astype(F)
+    assert np.array_equal(cloud[0].astype(np.float64), x[p]) and np.array_equal(cloud[1].astype(np.float64), y[p])
+    return cloud
+
+
+def ground_key_bits(cloud, resolution=0.5):
+    """(bits_x, bits_y, the packed key of every point): what fdm_cloud_segment_ground sorts by."""
+    gx, gy = (SR.cell_coordinates(v, resolution).astype(np.int64) for v in cloud[:2])
+    ex, ey = int(gx.max() - gx.min()), int(gy.max() - gy.min())
+    bits_x, bits_y = max(ex.bit_length(), 1), max(ey.bit_length(), 1)
+    keys = [(int(b - gy.min()) << bits_x) | int(a - gx.min()) for a, b in zip(gx, gy)]
+    return bits_x, bits_y, keys
+
+
+def ground_with_32_bit_keys(cloud, **kw):
+    """The restatement's answer if only the low 32 bits of the packed cell key were sorted and compared (four radix
+    passes instead of bits / 8): points whose keys agree there share a cell."""
+    _, _, keys = ground_key_bits(cloud, kw.get("grid_resolution", 0.5))
+    low = np.array([k & 0xFFFFFFFF for k in keys], dtype=np.int64)
+    res = kw.get("grid_resolution", 0.5)
+    sx, sy = ((low % 65536) * res + res / 2).astype(F), ((low // 65536) * res + res / 2).astype(F)  # one cell per low key
+    return SR.segment_ground(sx, sy, cloud[2], **kw)
+
+
 @functools.lru_cache(maxsize=None)
 def ground_cases():
     """name -> (cloud, keyword arguments of segment_ground)."""
@@ -205,7 +270,13 @@ def ground_cases():
         "n70000": (large, {}),
         "n70000_p1": (large, dict(cell_percentile=1.0, max_ground_height=5.0, min_points_per_cell=1)),
     }
+    for kind in GROUND_WIDE:
+        cases["wide_" + kind] = (ground_wide(kind), {})
+        cases["wide_" + kind + "_min1"] = (ground_wide(kind), dict(min_points_per_cell=1, cell_percentile=0.5))
     return cases
+
+
+GROUND_WIDE = {"bits33": (17, 16), "bits64": (32, 32), "extremes": (32, 32)}  # kind -> (bits_x, bits_y)
 
 
 @functools.lru_cache(maxsize=None)
@@ -217,14 +288,16 @@ def ground_answer(name):
 def ground_errors():
     """name -> (cloud, keyword arguments): the inputs at which the reference is undefined."""
     x, y, z = ground_edges()
-    bad_nan, bad_inf, far = x.copy(), z.copy(), y.copy()
+    bad_nan, bad_inf, far, first = x.copy(), z.copy(), y.copy(), x.copy()
     bad_nan[100] = np.nan
     bad_inf[7] = np.inf
     far[200] = F(3.0e9)  # floor(3e9 / 0.5) is outside int32
+    first[31] = F(2.0 ** 30)  # floor(2^30 / 0.5) = 2^31 exactly: the first floor that is refused
     return {
         "nan_coordinate": ((bad_nan, y, z), {}),
         "inf_z": ((x, y, bad_inf), {}),
         "floor_outside_int32": ((x, far, z), {}),
+        "floor_exactly_2_31": ((first, y, z), {}),
         "resolution_zero": ((x, y, z), dict(grid_resolution=0.0)),
         "resolution_negative": ((x, y, z), dict(grid_resolution=-0.5)),
         "resolution_inf": ((x, y, z), dict(grid_resolution=float("inf"))),

@@ -205,43 +205,56 @@ def default_result():
             "unrefined": np.array([0, 0, 1, 0], dtype=F)}
 
 
-def segment_plane(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, min_inliers=3,
-                  refine_model=True, indices=None, order="forward", solver="eigh"):
-    """:241-334.  Besides the result: counts / valid of every loop pass made (what the engine's replay is fed), the
-    quotient log(1 - p) / log(1 - w^3) at every best-update, the refinement's moments, the unrefined model."""
+def ransac_loop(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, indices=None):
+    """The loop of :258-308 alone: what it leaves for finish_plane (the refinement is the only part of segment_plane
+    that depends on the summation order or the eigen-solver, so large cases run the loop once and finish it six times)."""
     x, y, z = (np.ascontiguousarray(v, dtype=F).reshape(-1) for v in (x, y, z))
     indices = np.arange(x.size, dtype=np.uint32) if indices is None else np.asarray(indices, dtype=np.uint32).reshape(-1)
     if indices.size and int(indices.max()) >= x.size:
         raise ValueError("an index of the list is not below the point count")
     n = indices.size
     thr = F(distance_threshold)
-    res = default_result()
+    loop = {"cloud": (x, y, z), "indices": indices, "threshold": thr, "counts": [], "valid": [], "quotients": [],
+            "best_model": np.array([0, 0, 1, 0], dtype=F), "best_count": 0, "loop_iterations": 0}
     if n < 3:  # :247
-        return res
+        return loop
     rng = XorShift64(42)
-    best_model, best_count, adaptive, it = np.array([0, 0, 1, 0], dtype=F), 0, max_iterations, 0
+    best_model, best_count, adaptive, it = loop["best_model"], 0, max_iterations, 0
     lx, ly, lz = x[indices], y[indices], z[indices]
     while it < max_iterations and it < adaptive:  # :258
         it += 1
         i1, i2, i3 = draw_triplet(rng, n)
         pts = [(lx[i], ly[i], lz[i]) for i in (i1, i2, i3)]
         model, valid = plane_from_points(*pts)
-        res["valid"].append(int(valid))
+        loop["valid"].append(int(valid))
         if not valid:  # :283
-            res["counts"].append(0)
+            loop["counts"].append(0)
             continue
         count = int(np.count_nonzero(plane_dist(model, lx, ly, lz) < thr))  # :290
-        res["counts"].append(count)
+        loop["counts"].append(count)
         if count > best_count:  # :296
             best_model, best_count = model, count
             ratio = float(count) / float(n)
             adaptive = adaptive_iterations(ratio, probability)
             q = adaptive_quotient(ratio, probability)
             if q is not None:
-                res["quotients"].append(q)
-    res["loop_iterations"] = it
-    if best_count < min_inliers:  # :310
+                loop["quotients"].append(q)
+    loop.update(best_model=best_model, best_count=best_count, loop_iterations=it)
+    return loop
+
+
+def finish_plane(loop, min_inliers=3, refine_model=True, order="forward", solver="eigh"):
+    """:310-334 over what ransac_loop left: the result of segment_plane."""
+    x, y, z = loop["cloud"]
+    indices, thr, n = loop["indices"], loop["threshold"], loop["indices"].size
+    res = default_result()
+    if n < 3:  # :247
         return res
+    res.update(counts=loop["counts"], valid=loop["valid"], quotients=loop["quotients"],
+               loop_iterations=loop["loop_iterations"])
+    if loop["best_count"] < min_inliers:  # :310
+        return res
+    best_model = loop["best_model"]
     res["unrefined"] = best_model
     model = best_model
     inl = collect(x, y, z, indices, model, thr)
@@ -251,9 +264,17 @@ def segment_plane(x, y, z, distance_threshold=0.1, max_iterations=1000, probabil
         if np.isfinite(refined[3]):  # :323
             model = refined
             inl = collect(x, y, z, indices, model, thr)
-    res.update(coefficients=model, inliers=inl, fitness=float(inl.size) / float(n), iterations=it,
+    res.update(coefficients=model, inliers=inl, fitness=float(inl.size) / float(n), iterations=loop["loop_iterations"],
                success=bool(np.isfinite(model[3]) and inl.size > 0))
     return res
+
+
+def segment_plane(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, min_inliers=3,
+                  refine_model=True, indices=None, order="forward", solver="eigh"):
+    """:241-334.  Besides the result: counts / valid of every loop pass made (what the engine's replay is fed), the
+    quotient log(1 - p) / log(1 - w^3) at every best-update, the refinement's moments, the unrefined model."""
+    loop = ransac_loop(x, y, z, distance_threshold, max_iterations, probability, indices)
+    return finish_plane(loop, min_inliers, refine_model, order, solver)
 
 
 def segment_multiple_planes(x, y, z, max_planes=5, min_fitness=0.1, **cfg):  # :366-405

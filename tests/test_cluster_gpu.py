@@ -5,13 +5,18 @@ brute-force one).
 
 For every case: n_clusters, offsets and cluster_indices equal the canonical form exactly; labels agree with them;
 noise_indices is the complement; the stats add up; a second call gives the same bytes.  The refused inputs return
-FDM_ERR_INVALID with poisoned outputs untouched."""
+FDM_ERR_INVALID with poisoned outputs untouched.
+
+The large cases (tests/cluster_cases_large.py: lists past the sort's tile switch, the scan's carry and the index
+check's grid; one component over a thousand blocks) are held to the same assertions against the canonical form their
+construction gives."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import cluster_cases as CC
+import cluster_cases_large as CL
 import cluster_restate as CR
 
 pytestmark = pytest.mark.gpu
@@ -41,18 +46,16 @@ def as_numpy(a):
 
 
 def run(fdm, name, where):
-    cloud, kw = CC.cases()[name]
+    cloud, kw = (CC.cases() if name in CC.cases() else CL.cases())[name][:2]
     dev, dev_idx = placed(cloud, where, kw.get("indices"))
     args = {k: v for k, v in kw.items() if k != "indices"}
     return fdm.euclidean_cluster(*dev, indices=dev_idx, **args)
 
 
-@pytest.mark.parametrize("where", WHERE)
-@pytest.mark.parametrize("name", sorted(CC.cases()))
-def test_clusters_are_the_canonical_form(fdm, name, where):
-    cloud, kw = CC.cases()[name]
-    want_ind, want_off, want_lab = CC.answer(name)
-    m = CC.list_length(name)
+def check_canonical_form(fdm, name, where, cloud, kw, answer, n_components):
+    want_ind, want_off, want_lab = answer
+    idx = kw.get("indices")
+    m = cloud[0].size if idx is None else idx.size
     r = run(fdm, name, where)
     st = fdm.cluster_last_stats()
     ind, off, lab = as_numpy(r.indices), as_numpy(r.offsets), as_numpy(r.labels)
@@ -62,7 +65,7 @@ def test_clusters_are_the_canonical_form(fdm, name, where):
     assert np.array_equal(ind, want_ind)
     assert lab.size == m and np.array_equal(lab, want_lab)
     # labels against the CSR itself, whatever the answer: position p of cluster k carries k + 1
-    entries = np.arange(cloud[0].size, dtype=np.uint32) if kw.get("indices") is None else kw["indices"]
+    entries = np.arange(cloud[0].size, dtype=np.uint32) if idx is None else idx
     pos = np.nonzero(lab)[0]
     order = np.argsort(lab[pos], kind="stable")
     assert np.array_equal(entries[pos[order]], ind)
@@ -78,10 +81,30 @@ def test_clusters_are_the_canonical_form(fdm, name, where):
     assert st["neighbour_pairs"] <= st["tests"] <= st["candidate_pairs"] <= m * (m - 1) // 2
     assert st["neighbour_pairs"] >= st["unions"]
     if m:
-        assert st["n_components"] == CC.n_components(name) and st["range"] == 1
+        assert st["n_components"] == n_components and st["range"] == 1
+    return st
 
 
-@pytest.mark.parametrize("name", ["mixed70k", "dense_voxel", "singletons_min1", "line4097", "subset_duplicate"])
+@pytest.mark.parametrize("where", WHERE)
+@pytest.mark.parametrize("name", sorted(CC.cases()))
+def test_clusters_are_the_canonical_form(fdm, name, where):
+    cloud, kw = CC.cases()[name]
+    st = check_canonical_form(fdm, name, where, cloud, kw, CC.answer(name), CC.n_components(name) if CC.list_length(name) else 0)
+    if name in CC.KEY_BITS:  # keys wider than 32 bits: k_cluster_keys, k_cluster_ranges' bisection, 5 .. 8 radix passes
+        assert st["key_bits"] == CC.KEY_BITS[name]
+
+
+@pytest.mark.parametrize("where", WHERE)
+@pytest.mark.parametrize("name", sorted(CL.cases()))
+def test_large_clusters_are_the_constructed_form(fdm, name, where):
+    cloud, kw, _ = CL.cases()[name]
+    *answer, n_components = CL.answer(name)
+    st = check_canonical_form(fdm, name, where, cloud, kw, tuple(answer), n_components)
+    assert st["candidate_pairs"] < 100_000_000  # far below the work bound of 1.5e11
+
+
+@pytest.mark.parametrize("name", ["mixed70k", "dense_voxel", "singletons_min1", "line4097", "subset_duplicate",
+                                  "blobs_688k_min10"])
 def test_two_calls_give_identical_bytes(fdm, name):
     a, b = run(fdm, name, "device"), run(fdm, name, "device")
     for u, v in ((a.indices, b.indices), (a.offsets, b.offsets), (a.labels, b.labels)):

@@ -2,7 +2,12 @@
 euclideanCluster (tests/test_segmentation.cpp:111-277, :504-509, :523-531, :555-584), its partition equals the
 brute-force connected components of the relation on every case of tests/cluster_cases.py, every cluster's first BFS
 element is its smallest position (the seed), every case is ADMITTED, and the canonical form — what tests/test_cluster_gpu.py
-compares the device with — is the stable-sort reading of the restatement's own order."""
+compares the device with — is the stable-sort reading of the restatement's own order.
+
+The large cases (tests/cluster_cases_large.py) take their answers from their construction; here the same constructors
+are run at a few thousand points against the BFS and the brute force, the cases are shown to be on the lattice (their
+admission) and to cross the thresholds they were built for, and each is shown to be SENSITIVE: the computation with the
+targeted branch skipped gives another answer."""
 import os
 import shutil
 import subprocess
@@ -11,7 +16,9 @@ import numpy as np
 import pytest
 
 import cluster_cases as CC
+import cluster_cases_large as CL
 import cluster_restate as CR
+import seg_cases_large as SL
 
 F = np.float32
 NAMES = sorted(CC.cases())
@@ -141,6 +148,98 @@ def test_canonical_form_is_the_stable_order(name):
     for k in range(1, len(clusters)):  # equal sizes by smallest position
         if len(clusters[k]) == len(clusters[k - 1]):
             assert firsts[k] > firsts[k - 1]
+
+
+# ------------------------------------------------------------------ wide keys, large lists ----
+@pytest.mark.parametrize("name", sorted(CC.KEY_BITS))
+def test_wide_cases_need_more_than_32_key_bits(name):
+    cloud, tol, lo, hi, idx = config(name)
+    bits, keys = CC.sort_keys(cloud, tol, idx)
+    assert bits == CC.KEY_BITS[name] > 32
+    # sensitivity: sorted by the low 32 bits alone (four radix passes) the keys are not in order — k_cluster_ranges
+    # bisects them — and two occupied voxels share their low 32 bits
+    by_low = np.argsort(keys & 0xFFFFFFFF, kind="stable")
+    assert (np.diff(keys[by_low]) < 0).any()
+    assert np.unique(keys & 0xFFFFFFFF).size < np.unique(keys).size
+    vox = CR.voxels(CR._points(*cloud, idx)[0], CR.relation_constants(tol)[0])
+    if name == "wide_corners":  # the accepted extremes, with clusters AT them
+        assert vox.min() == CR.COORD_MIN + 1 and vox.max() == CR.COORD_MAX - 1
+        assert (vox.min(axis=0) == CR.COORD_MIN + 1).all() and (vox.max(axis=0) == CR.COORD_MAX - 1).all()
+        ind, off, _ = CC.restated(name)
+        corner = {int(p) for p in np.nonzero((np.abs(vox) >= CR.COORD_MAX - 2).all(axis=1))[0]}
+        assert sum(1 for k in range(off.size - 1) if set(ind[off[k]:off[k + 1]].tolist()) <= corner) >= 5
+        assert 1 in sizes(off) and 40 in sizes(off)  # the singletons and the blob across two voxels
+
+
+def test_blob_constructor_is_the_restatement_at_a_few_thousand_points():
+    cloud, idx, blob = CL.blob_list(**CL.BLOBS_SMALL)
+    assert 4000 <= idx.size <= 10000 and np.unique(idx).size < idx.size < cloud[0].size + idx.size
+    assert CL.on_the_lattice(cloud, idx)
+    pts, entries = CR._points(*cloud, idx)
+    label = CR.components_brute(*cloud, CL.TOL, idx)
+    for lo in (1, 10):
+        clusters, comps = CR.cluster_core(pts, CL.TOL, lo, 100000)
+        want = CR.canonical(clusters, entries, entries.size)
+        got = CL.canonical_of_partition(blob, idx, lo, 100000)
+        for a, b in zip(want, got[:3]):
+            assert np.array_equal(a, b)
+        assert got[3] == len(comps) == np.unique(label).size
+        assert np.array_equal(CL.canonical_of_partition(label, idx, lo, 100000)[2], got[2])  # the brute force's partition
+    # and the chain's constructor: one component by the BFS and by the brute force
+    line = CL.chain_long(2049, 300)
+    clusters, comps = CR.cluster_core(np.stack(line, axis=1), CL.TOL, 10, 100000)
+    assert len(comps) == 1 and np.unique(CR.components_brute(*line, CL.TOL)).size == 1
+    want = CR.canonical(clusters, np.arange(2049, dtype=np.uint32), 2049)
+    got = CL.canonical_of_partition(np.zeros(2049), np.arange(2049, dtype=np.uint32), 10, 100000)
+    assert all(np.array_equal(a, b) for a, b in zip(want, got[:3]))
+
+
+def test_large_blob_cases_cross_what_they_were_built_for():
+    cloud, idx, blob = CL.blobs_688k()
+    m = idx.size
+    assert m >= 655361 and m > CL.RS_SMALL_MAX and m > CL.INDEX_SWEEP and cloud[0].size < m
+    assert np.unique(idx).size < m and int(idx.max()) < cloud[0].size and np.unique(idx).size < cloud[0].size
+    assert CL.on_the_lattice(cloud, idx)  # admission, by construction
+    # the partition is the construction's: blobs narrower than the tolerance, 1.6 or more apart
+    pts, _ = CR._points(*cloud, idx)
+    p64 = pts.astype(np.float64)
+    order = np.argsort(blob, kind="stable")
+    starts = np.nonzero(np.diff(blob[order], prepend=-1))[0]
+    lo, hi = np.minimum.reduceat(p64[order], starts), np.maximum.reduceat(p64[order], starts)
+    assert (np.linalg.norm(hi - lo, axis=1) < CL.TOL).all()
+    centre = np.round((lo + hi) / 4.0) * 2.0
+    assert np.unique(centre, axis=0).shape[0] == starts.size and (np.abs((lo + hi) / 2.0 - centre) < 0.2).all()
+    for name, kept_positions, clusters in (("blobs_688k_min1", m, 161000), ("blobs_688k_min10", 300000, 25000)):
+        ind, off, lab, comps = CL.answer(name)
+        assert (ind.size, off.size - 1, comps) == (kept_positions, clusters, 161000)
+        assert ind.size > CL.SCAN_CHUNK and clusters > 2 * 1024  # the ordered keys' run heads carry too
+        assert int((lab > 0).sum()) == ind.size and off[-1] == ind.size
+        # sensitivity: without the scan's carry the kept positions compact to another list, the run heads to other offsets
+        if name.endswith("min10"):
+            assert m - ind.size > CL.SCAN_CHUNK  # rejected by min_size
+            assert ind.size <= CL.RS_SMALL_MAX < m  # the ordering sort takes the small tile in a histogram sized for m
+        kept = np.nonzero(lab)[0].astype(np.uint32)
+        if kept.size < m:
+            assert not np.array_equal(SL.compact_without_carry(lab > 0), kept)
+        heads = np.zeros(ind.size, dtype=bool)
+        heads[off[:-1]] = True
+        assert not np.array_equal(SL.compact_without_carry(heads), off[:-1])
+
+
+def test_chain_case_is_one_component_over_a_thousand_blocks():
+    (x, y, z), kw, _ = CL.cases()["chain_300k"]
+    m = x.size
+    assert m == CL.CHAIN > CL.SCAN_CHUNK and not y.any() and not z.any() and kw["max_size"] >= m
+    sx = np.sort(x.astype(np.float64))
+    assert (np.diff(sx) == 0.4375).all()  # a neighbour 0.875 tol away, the next one 1.75 tol: exact in fp32, no band
+    a = np.stack([x[:2], y[:2], z[:2]], axis=1)
+    dec = CR.decisions(np.zeros((2, 3), dtype=F), np.asarray([[0.4375, 0, 0], [0.875, 0, 0]], dtype=F), F(0.25))
+    assert dec[:, 0].all() and not dec[:, 1].any() and a.shape == (2, 3)
+    assert (np.abs(np.diff(x.astype(np.float64))) > 1.0).mean() > 0.99  # shuffled: list neighbours are far apart
+    ind, off, lab, comps = CL.answer("chain_300k")
+    assert comps == 1 and off.tolist() == [0, m] and np.array_equal(ind, np.arange(m)) and (lab == 1).all()
+    # sensitivity: links that stay inside a block of 256 sorted points give ceil(m / 256) components, not one
+    assert -(-m // 256) > 1024
 
 
 # ------------------------------------------------------------------ the engine's host algebra, stand-alone and sanitized ----

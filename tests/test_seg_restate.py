@@ -6,7 +6,11 @@ The restatement is held to every assertion of nanoPCL's RANSAC, ground and bound
 :283-376, :382-498, :511-549; line numbers below are that file's) — on the rand-free clouds as they are, on seeded clouds
 of the same construction where the reference draws from rand().  ADMISSION: a plane case is in the table only if its
 refined coefficients and final inlier list are identical under the three summation orders and both eigen-solvers, and
-if log(1 - p) / log(1 - w^3) at every best-update is no closer than 1e-9 to an integer.  Every case must be admitted."""
+if log(1 - p) / log(1 - w^3) at every best-update is no closer than 1e-9 to an integer.  Every case must be admitted.
+
+The large cases (tests/seg_cases_large.py) and the wide ones of the small table are held to the same admission and to
+SENSITIVITY: each exists to reach one branch that only size reaches, and the restatement of the computation with that
+branch skipped must give another observable answer — else the case could not fail for it."""
 import os
 import shutil
 import subprocess
@@ -15,6 +19,7 @@ import numpy as np
 import pytest
 
 import seg_cases as SC
+import seg_cases_large as SL
 import seg_restate as SR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,7 +224,7 @@ def test_ground_case_partitions_the_cloud(name):
 
 
 def test_ground_cases_cover_what_the_table_promises():
-    assert sorted({c[0][0].size for c in SC.ground_cases().values()}) == [1, 2, 255, 257, 4097, 70000]
+    assert sorted({c[0][0].size for c in SC.ground_cases().values()}) == [1, 2, 255, 257, 300, 4097, 70000]
     # one point: a cell below min_points_per_cell is all obstacle; with min 1 / 0 the point is its own robust minimum
     assert SC.ground_answer("n1")[1].tolist() == [0]
     assert SC.ground_answer("n1_min1")[1].tolist() == [0]          # z = 3 is above max_ground_height
@@ -249,6 +254,133 @@ def test_ground_cases_cover_what_the_table_promises():
     for name, (cloud, kw) in SC.ground_errors().items():
         with pytest.raises(ValueError):
             SR.segment_ground(*cloud, **kw)
+
+
+# ---- the large cases, and the wide ones of the small table: admission and sensitivity ----
+def coefficient_bits(r):
+    return r["coefficients"].view(np.uint32).tolist()
+
+
+@pytest.mark.parametrize("name", sorted(SL.plane_cases()))
+def test_large_plane_case_is_admitted(name):
+    base = SL.plane_answer(name)
+    for order, solver in SL.ORDERS:  # (one loop, six refinements: the loop does not depend on either)
+        r = SL.plane_answer(name, order, solver)
+        assert coefficient_bits(r) == coefficient_bits(base), (order, solver)
+        assert np.array_equal(r["inliers"], base["inliers"]), (order, solver)
+    assert base["success"] and base["moments"] is not None and base["quotients"]
+    for q in base["quotients"]:
+        assert abs(q - round(q)) >= 1e-9, q
+    n_list = SL.plane_loop(name)["indices"].size
+    assert base["fitness"] == base["inliers"].size / float(n_list)
+
+
+def test_plane_sum_cases_give_the_fixed_tree_a_second_term():
+    counts = {}
+    for name in SL.sum_cases():
+        loop = SL.plane_loop(name)
+        inl = SL.first_collect(name)  # what k_plane_sum sums over
+        counts[name] = inl.size
+        # sensitivity: the sums of the first 65 536 inliers alone (the stride skipped) refine to other coefficients
+        full, _ = SR.refine(*loop["cloud"], inl, loop["best_model"])
+        cut, _ = SR.refine(*loop["cloud"], inl[:SL.PLANE_SUM_SWEEP], loop["best_model"])
+        assert full.view(np.uint32).tolist() != cut.view(np.uint32).tolist(), name
+        assert coefficient_bits(SL.plane_answer(name)) == full.view(np.uint32).tolist()
+        # the second collect is past the grid too (the engine refines once; both compactions cross 65 536)
+        assert SL.plane_answer(name)["inliers"].size > SL.PLANE_SUM_SWEEP
+    print(counts)
+    assert SL.PLANE_SUM_SWEEP < counts["sum_one_block"] <= SL.PLANE_SUM_SWEEP + 256  # block 0 alone strides
+    assert 95000 <= counts["sum_100k"] <= 105000
+
+
+def test_plane_count_cases_make_a_second_sweep_that_decides():
+    head = SL.count_loop("head")
+    n_base = SL.count_base()[0].size
+    assert head["indices"].size == SL.PLANE_COUNT_SWEEP and 200000 <= n_base <= 400000
+    for name, (cloud, kw) in SL.count_cases().items():
+        loop, r = SL.plane_loop(name), SL.plane_answer(name)
+        m = loop["indices"].size
+        assert m == SL.PLANE_COUNT_SWEEP + (1 if "_t1_" in name else SL.COUNT_TAIL)
+        assert (cloud[0].size == m) == name.endswith("_cloud")
+        if name.endswith("_list"):
+            assert np.unique(kw["indices"]).size < kw["indices"].size <= 10 * n_base  # duplicates, a few per point
+            assert np.array_equal(kw["indices"][:SL.PLANE_COUNT_SWEEP], head["indices"])
+        # run to the cap: one batch of 128, the j >= 64 half of k_plane_count included
+        assert r["iterations"] == loop["loop_iterations"] == kw["max_iterations"] == SC.BATCH
+        # sensitivity, as the issue states it: the restatement over the first 2 097 152 entries alone differs
+        assert (head["loop_iterations"], head["best_model"].view(np.uint32).tolist()) != \
+               (loop["loop_iterations"], loop["best_model"].view(np.uint32).tolist()), name
+    # ... and for the long tail with the loop's OWN 128 hypotheses, each scored against the first sweep alone (what
+    # k_plane_count without its stride counts): another pass wins, with another model
+    full, first_sweep = SL.first_sweep_winner("count_tail_list")
+    assert full != first_sweep and full >= 0 and first_sweep >= 0
+    # (the single entry of the T = 1 variant moves no count by more than one: it pins the lone live lane of block 0's
+    # second tile — a count past m or a fault if its neighbours were not masked — not the winner)
+    # plane B wins the whole list, plane A wins its first sweep
+    loop = SL.plane_loop("count_tail_list")
+    lx, ly, lz = (v[loop["indices"]] for v in loop["cloud"])
+    cut = SL.PLANE_COUNT_SWEEP
+    count = lambda model, upto: int(np.count_nonzero(SR.plane_dist(model, lx[:upto], ly[:upto], lz[:upto]) < loop["threshold"]))  # noqa: E731
+    winner, other = loop["best_model"], head["best_model"]
+    assert count(winner, None) == loop["best_count"] > count(other, None)
+    assert count(winner, cut) < count(other, cut)
+    # the cloud variant holds the list's points in the list's order: the two share their loop and their coefficients
+    for t in ("count_t1", "count_tail"):
+        a, b = SL.plane_answer(t + "_list"), SL.plane_answer(t + "_cloud")
+        assert coefficient_bits(a) == coefficient_bits(b)
+        assert np.array_equal(a["inliers"], SL.count_cases()[t + "_list"][1]["indices"][b["inliers"]])
+
+
+def test_index_check_stride_list_is_bad_at_its_last_entry_only():
+    cloud, _ = SC.INDEX_ERROR
+    idx = SL.index_check_stride(cloud[0].size)
+    assert idx.size == SL.INDEX_CHECK_SWEEP + 1 and int(idx[:-1].max()) < cloud[0].size == int(idx[-1])
+    with pytest.raises(ValueError):
+        SR.segment_plane(*cloud, distance_threshold=0.05, indices=idx, max_iterations=1)
+
+
+@pytest.mark.parametrize("name", sorted(SL.ground_cases()))
+def test_ground_600k_crosses_the_sort_tile_and_the_scan_carry(name):
+    cloud, kw = SL.ground_cases()[name]
+    n = cloud[0].size
+    g, o = SL.ground_answer(name)
+    assert np.array_equal(np.sort(np.concatenate([g, o])), np.arange(n))
+    assert (np.diff(g.astype(np.int64)) > 0).all() and (np.diff(o.astype(np.int64)) > 0).all()
+    assert n > SL.RS_SMALL_MAX  # rs_tile(n) = 4096 for both sorts
+    cells = np.stack([np.floor(cloud[0] / F(0.5)), np.floor(cloud[1] / F(0.5))], axis=1)
+    _, counts = np.unique(cells, axis=0, return_counts=True)
+    assert (counts >= 5000).sum() >= 3 and ((counts == 1) | (counts == 2)).sum() > SL.SCAN_CHUNK
+    assert counts.size > SL.SCAN_CHUNK  # the run heads' scan carries too
+    # sensitivity: without the scan's carry the compaction of either list is another list
+    for kept in (g, o):
+        keep = np.zeros(n, dtype=bool)
+        keep[kept] = True
+        assert kept.size > 4096 and not np.array_equal(SL.compact_without_carry(keep), kept)
+        assert np.array_equal(SL.compact_without_carry(keep[:SL.SCAN_CHUNK]), kept[kept < SL.SCAN_CHUNK])  # (the model)
+
+
+@pytest.mark.parametrize("kind", sorted(SC.GROUND_WIDE))
+def test_ground_wide_cases_need_more_than_32_key_bits(kind):
+    for name in ("wide_" + kind, "wide_" + kind + "_min1"):
+        cloud, kw = SC.ground_cases()[name]
+        bits_x, bits_y, keys = SC.ground_key_bits(cloud)
+        assert (bits_x, bits_y) == SC.GROUND_WIDE[kind] and bits_x + bits_y > 32
+        # several points share a cell at these magnitudes: equal x, y, different z
+        cells, counts = np.unique(np.array(keys, dtype=object), return_counts=True)
+        assert (counts >= 6).sum() >= 20
+        g, o = SC.ground_answer(name)
+        assert g.size and o.size
+        # sensitivity: sorted and compared by the low 32 bits of the key alone, the lists are others
+        tg, to = SC.ground_with_32_bit_keys(cloud, **kw)
+        assert not np.array_equal(tg, g) and not np.array_equal(to, o)
+    if kind == "extremes":  # the accepted extremes themselves
+        gx, gy = (SR.cell_coordinates(v, 0.5) for v in cloud[:2])
+        assert gx.min() == gy.min() == -2.0 ** 31 and gx.max() == gy.max() == float(np.nextafter(F(2.0 ** 31), F(0)))
+    if kind == "bits64":
+        assert np.abs(cloud[0]).min() > 0.999e9 and (cloud[0] > 0).any() and (cloud[0] < 0).any()
+    # the first refused floor is 2^31 itself
+    bad = SC.ground_errors()["floor_exactly_2_31"][0][0]
+    assert SR.cell_coordinates(bad, 0.5).max() == 2.0 ** 31
 
 
 # ---- the engine's host algebra, stand-alone and sanitized ----

@@ -6,13 +6,17 @@ coefficients and inliers do not depend on the summation order or the eigen-solve
 Ground: both lists bit for bit; the undefined inputs return FDM_ERR_INVALID with the lists untouched.  Plane: iterations,
 success and the inlier count; the unrefined model's bits (refine_model off); the refined coefficients' bits and the inlier
 list; independently of any admission, the returned inliers are what the restatement's collect gives for the engine's OWN
-coefficients; fitness = n_inliers / n_indices exactly; the batches launched."""
+coefficients; fitness = n_inliers / n_indices exactly; the batches launched.
+
+The large cases (tests/seg_cases_large.py: lists past the scoring kernel's grid, the refinement's summation grid, the
+index check's grid, the scan's carry and the sort's tile switch) are held to the same assertions."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import seg_cases as SC
+import seg_cases_large as SL
 import seg_restate as SR
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +56,18 @@ def bits(a):
 def test_ground_lists_are_the_restatements(fdm, name, where):
     cloud, kw = SC.ground_cases()[name]
     want_g, want_o = SC.ground_answer(name)
+    dev, _ = placed(cloud, where)
+    g, o = fdm.segment_ground(*dev, **kw)
+    g, o = as_numpy(g), as_numpy(o)
+    assert g.size == want_g.size and o.size == want_o.size, (g.size, want_g.size, o.size, want_o.size)
+    assert np.array_equal(g, want_g) and np.array_equal(o, want_o)
+
+
+@pytest.mark.parametrize("where", WHERE)
+@pytest.mark.parametrize("name", sorted(SL.ground_cases()))
+def test_ground_600k_lists_are_the_restatements(fdm, name, where):
+    cloud, kw = SL.ground_cases()[name]
+    want_g, want_o = SL.ground_answer(name)
     dev, _ = placed(cloud, where)
     g, o = fdm.segment_ground(*dev, **kw)
     g, o = as_numpy(g), as_numpy(o)
@@ -143,6 +159,38 @@ def test_plane_is_the_restatements(fdm, name, where):
         assert st["n_hypotheses"] == passes == kw.get("max_iterations", 1000)  # the last batch is cut to the cap
 
 
+@pytest.mark.parametrize("where", WHERE)
+@pytest.mark.parametrize("name", sorted(SL.plane_cases()))
+def test_large_plane_is_the_restatements(fdm, name, where):
+    cloud, kw = SL.plane_cases()[name]
+    want = SL.plane_answer(name)
+    idx = kw.get("indices")
+    n_list = cloud[0].size if idx is None else idx.size
+    dev, dev_idx = placed(cloud, where, idx)
+    r = fdm.segment_plane(*dev, indices=dev_idx, **{k: v for k, v in kw.items() if k != "indices"})
+    check_against_restatement(r, want, cloud, kw, n_list)
+    st = fdm.segment_last_stats()
+    passes = want["loop_iterations"]
+    assert st["batch"] == SC.BATCH and st["n_batches"] == 1 and st["n_invalid_samples"] == want["valid"].count(0)
+    assert st["n_hypotheses"] == (passes if name in SL.count_cases() else SC.BATCH)
+    if name in SL.count_cases():  # run to the cap: one batch of 128, both halves of k_plane_count
+        assert passes == kw["max_iterations"] == SC.BATCH and n_list > SL.PLANE_COUNT_SWEEP
+    else:
+        assert as_numpy(r.inliers).size > SL.PLANE_SUM_SWEEP
+
+
+@pytest.mark.parametrize("name", sorted(SL.sum_cases()))
+def test_plane_two_calls_give_identical_bits(fdm, name):
+    """The refinement's sums are a fixed tree over a grid that depends on the inlier count alone: past 65 536 inliers,
+    where a lane takes several terms, a repeated call still gives the same bits."""
+    cloud, kw = SL.sum_cases()[name]
+    dev, _ = placed(cloud, "device")
+    a, b = fdm.segment_plane(*dev, **kw), fdm.segment_plane(*dev, **kw)
+    assert bits(a.coefficients).tobytes() == bits(b.coefficients).tobytes()
+    assert as_numpy(a.inliers).tobytes() == as_numpy(b.inliers).tobytes()
+    assert (a.iterations, a.fitness, a.success) == (b.iterations, b.fitness, b.success)
+
+
 def test_plane_result_does_not_depend_on_the_batch(fdm):
     lib = fdm.capi.load()
     cloud, kw = SC.plane_cases()["scene20"]
@@ -169,6 +217,42 @@ def test_plane_index_out_of_range_is_refused(fdm, where):
     dev, dev_idx = placed(cloud, where, kw["indices"])
     with pytest.raises(fdm.EngineError, match="index"):
         fdm.segment_plane(*dev, distance_threshold=kw["distance_threshold"], indices=dev_idx)
+
+
+@pytest.mark.parametrize("where", WHERE)
+def test_plane_index_past_the_check_grid_is_refused(fdm, where):
+    """524 289 entries whose only bad one is the last: k_seg_index_check's grid is capped at 2048 blocks of 256, so that
+    entry is seen by the strided loop alone.  Refused, the inlier list and the result untouched."""
+    cloud, kw = SC.INDEX_ERROR
+    idx = SL.index_check_stride(cloud[0].size)
+    lib = fdm.capi.load()
+    cfg = fdm.capi.FdmRansacConfig(float(F(kw["distance_threshold"])), 1000, 0.99, 3, 1)
+    res = fdm.capi.FdmRansacResult()
+    if where == "host":
+        inl = np.full(idx.size, 0xDEADBEEF, dtype=np.uint32)
+        ptrs = [v.ctypes.data_as(C.c_void_p) for v in (*cloud, idx, inl)]
+    else:
+        import torch
+        dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in cloud]
+        d_idx = torch.from_numpy(idx.astype(np.int64)).to(torch.int32).cuda()
+        inl = torch.full((idx.size,), 0x5EADBEEF, dtype=torch.int32, device="cuda")
+        ptrs = [C.c_void_p(v.data_ptr()) for v in (*dev, d_idx, inl)]
+        torch.cuda.synchronize()
+    rc = lib.fdm_cloud_segment_plane(cloud[0].size, ptrs[0], ptrs[1], ptrs[2], int(where == "device"), ptrs[3], idx.size,
+                                     C.byref(cfg), 0, ptrs[4], C.byref(res))
+    assert rc == -1 and b"index" in lib.fdm_last_error(), (rc, lib.fdm_last_error())  # FDM_ERR_INVALID
+    host = inl.cpu().numpy() if where == "device" else inl
+    assert (host == host[0]).all() and int(host[0]) & 0xFFFF == 0xBEEF, "a refused call wrote to the inlier list"
+    assert (res.iterations, res.success, res.n_inliers, res.fitness) == (0, 0, 0, 0.0)
+    assert list(res.coefficients) == [0.0, 0.0, 1.0, 0.0]
+    dev, dev_idx = placed(cloud, where, idx)
+    with pytest.raises(fdm.EngineError, match="index"):
+        fdm.segment_plane(*dev, distance_threshold=kw["distance_threshold"], indices=dev_idx)
+    # the same list without its last entry is taken
+    dev, dev_idx = placed(cloud, where, idx[:-1])
+    r = fdm.segment_plane(*dev, distance_threshold=kw["distance_threshold"], indices=dev_idx, max_iterations=8)
+    want = SR.segment_plane(*cloud, distance_threshold=kw["distance_threshold"], indices=idx[:-1], max_iterations=8)
+    assert (r.iterations, r.success) == (want["iterations"], want["success"]) == (8, True)
 
 
 def test_plane_outliers_complete_the_inliers(fdm):
