@@ -220,12 +220,14 @@ int launch_rbatch(fdm_engine* e, const RBatch& R) {
 int launch_mbatch(fdm_engine* e, int ch, const MUpd& U, const MBin& B, const MCrop& Cn, const MCommon& K) {
   // (7.2 KB of kernel arguments with 32 scans per batch: the AQL kernarg segment has no 4 KB limit — scripts/ubench/
   // kernarg_big.hip passes 8 KB by value on this stack, checked on the box in round 6)
-  static_assert(sizeof(MUpd) + sizeof(MBin) + sizeof(MCrop) + sizeof(MCommon) + sizeof(GeomConst) + 160 <= 8192,
+  // (the head's eight scalars, the four structs, the geometry, st, the layers of the widest policy, all_layers, n_layers)
+  static_assert(48 + sizeof(MUpd) + sizeof(MBin) + sizeof(MCrop) + sizeof(MCommon) + sizeof(GeomConst) + 160 <= 8192,
                 "k_mbatch: kernel arguments beyond 8 KB");
+  static_assert(sizeof(MBinScan) == 144 && offsetof(MBinScan, first_block) + 4 <= 64, "a bin block's record: one 64-byte line + the transforms");
   const unsigned ub = U.count ? unsigned((e->ncell + upd_cells_per_block(U.count) - 1u) / upd_cells_per_block(U.count)) : 0u;
   // rows as wide as the widest scan; the update's blocks fill as many leading rows as they need
   unsigned gx = 0u;
-  for (unsigned k = 0; k < B.count; ++k) gx = std::max(gx, (B.n[k] + kMBlock - 1u) / kMBlock);
+  for (unsigned k = 0; k < B.count; ++k) gx = std::max(gx, (B.s[k].n + kMBlock - 1u) / kMBlock);
   if (gx == 0u) gx = std::min(std::max(ub, Cn.count * kMScout + 1u), 64u);
   if (gx == 0u) return FDM_OK;
   const unsigned crows = Cn.count ? (Cn.count * kMScout + 1u + gx - 1u) / gx : 0u;  // the scout blocks of the next batch + its walker block, in rows of their own
@@ -237,8 +239,10 @@ int launch_mbatch(fdm_engine* e, int ch, const MUpd& U, const MBin& B, const MCr
     using POLICY = decltype(tag);
     if constexpr (is_rec_policy<POLICY>) {
       return with_constants([&](auto chc, auto ray) -> int {  // (ray: the variant whose update resolves ray events)
-        hipLaunchKernelGGL((k_mbatch<POLICY, chc(), ray()>), dim3(gx, rows), dim3(256), 0, e->stream, U, B, Cn, Kt, e->G,
-                           e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs, unsigned(e->ncell), ub, urows);
+        hipLaunchKernelGGL((k_mbatch<POLICY, chc(), ray()>), dim3(gx, rows), dim3(256), 0, e->stream, urows, ub,
+                           unsigned(e->ncell), gx, U.count, B.count, Cn.count, Kt.timeline ? 1u : 0u, U.key, U.ms, U, B, Cn, Kt,
+                           e->G,
+                           e->d_state, layers, e->d_layer_ptrs, e->n_layer_ptrs);
         HIPCK(hipGetLastError());
         return FDM_OK;
       }, UpTo<4>{ch & 3}, U.ray.stamp != 0u || B.cap != nullptr);  // (a half with raycasting)
@@ -291,11 +295,11 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
     const fdm_device_scan& s = scans[k];
     fill_integrate_params(e, P, s.T_base_sensor, s.T_world_base);
     for (int c = 0; c < 4; ++c)
-      for (int r = 0; r < 3; ++r) B.t[k].Twb[c * 3 + r] = P.Twb[c * 4 + r];
-    std::memcpy(B.t[k].R, P.R, sizeof(P.R));
-    B.n[k] = uint32_t(s.n);
-    B.px[k] = s.x; B.py[k] = s.y; B.pz[k] = s.z; B.pint[k] = s.intensity; B.prgb[k] = s.rgb; B.pvar[k] = s.sigma_z2;
-    B.first_block[k] = blocks;
+      for (int r = 0; r < 3; ++r) B.s[k].t.Twb[c * 3 + r] = P.Twb[c * 4 + r];
+    std::memcpy(B.s[k].t.R, P.R, sizeof(P.R));
+    B.s[k].n = uint32_t(s.n);
+    B.s[k].px = s.x; B.s[k].py = s.y; B.s[k].pz = s.z; B.s[k].pint = s.intensity; B.s[k].prgb = s.rgb; B.s[k].pvar = s.sigma_z2;
+    B.s[k].first_block = blocks;
     B.robot_x[k] = P.robot_x;
     B.robot_y[k] = P.robot_y;
     blocks += unsigned((s.n + kMBlock - 1u) / kMBlock);
@@ -312,7 +316,6 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
       R.ox[k] = P.ray_ox; R.oy[k] = P.ray_oy; R.oz[k] = P.ray_oz;
     }
   }
-  for (uint32_t k = count; k <= uint32_t(kMaxBatch); ++k) B.first_block[k] = blocks;
   if ((rc = ensure_multi(e, max_n, blocks))) return rc;
   if (ray && (rc = ensure_rbatch(e))) return rc;
 
@@ -342,8 +345,10 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   B.scan_no0 = uint32_t(e->scan_no);
   B.ms = e->mstate + slot;
   const bool fuse = e->chain && e->pend.multi;  // (same channels: checked above)
-  B.prev = fuse ? e->pend.MU.ms : nullptr;
-  B.prev_count = fuse ? e->pend.MU.count : 0u;
+  // (always a readable state: with no previous batch the batch's own, unused — MBin::prev)
+  B.prev = fuse ? e->pend.MU.ms : B.ms;
+  B.prev_count = fuse ? e->pend.MU.count : 1u;
+  B.has_prev = fuse ? 1u : 0u;
   B.obs_stride = unsigned(e->mobs_stride);
   B.key = e->mkey[par];
   B.aux = e->maux[par];
@@ -360,13 +365,15 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   auto fill_scouts = [&](MCrop& C, uint32_t n, const fdm_device_scan* ss, MState* ms) {
     std::memset(&C, 0, sizeof(C));
     for (uint32_t k = 0; k < n; ++k) {
-      C.n[k] = uint32_t(ss[k].n);
-      C.px[k] = ss[k].x; C.py[k] = ss[k].y; C.pz[k] = ss[k].z;
+      C.s[k].n = uint32_t(ss[k].n);
+      C.s[k].px = ss[k].x; C.s[k].py = ss[k].y; C.s[k].pz = ss[k].z;
       C.robot_x[k] = ss[k].T_world_base[12];  // T_world_base.translation().head<2>() (fastdem.cpp:144), as MBin::robot_x
       C.robot_y[k] = ss[k].T_world_base[13];
     }
     C.count = n;
     C.ms = ms;
+    C.prev = ms;  // (readable and unused unless the caller names a previous batch: MCrop::prev)
+    C.prev_count = 1u;
   };
   const bool gated = K.do_move && K.gate_on_filter;
   if (gated && !pre) {
@@ -377,8 +384,7 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
     std::memset(&B0, 0, sizeof(B0));
     fill_scouts(C0, count, scans, e->mstate + slot);
     // (no batch is binned by this launch: the walker block starts the chain where this batch's bin blocks will)
-    C0.prev = fuse ? e->pend.MU.ms : nullptr;
-    C0.prev_count = fuse ? e->pend.MU.count : 0u;
+    if (fuse) { C0.prev = e->pend.MU.ms; C0.prev_count = e->pend.MU.count; C0.has_prev = 1u; }
     C0.scan_no0 = uint32_t(e->scan_no);
     if ((rc = launch_mbatch(e, ch, U0, B0, C0, K))) return rc;
   }
@@ -453,8 +459,8 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   // bookkeeping as enqueue_scan leaves it after the batch's last scan
   const fdm_device_scan& l = scans[count - 1u];
   e->last_kind = 0;
-  e->last_bin_blocks = blocks - B.first_block[count - 1u];
-  e->last_bin_part = B.bin_part + B.first_block[count - 1u];
+  e->last_bin_blocks = blocks - B.s[count - 1u].first_block;
+  e->last_bin_part = B.bin_part + B.s[count - 1u].first_block;
   e->last_upd_tiles = unsigned((e->ncell + upd_cells_per_block(count) - 1u) / upd_cells_per_block(count));
   e->last_upd_part = e->mupd_part;
   e->ray_timed = false;

@@ -57,7 +57,10 @@
 //   the chain    of moves has one arithmetic (lane_f64, mchain_nearest, mchain_shift), used by the walker (mwalk_batch)
 //                and by the bin blocks' own walk (mbin_body).
 //
-// All per-batch parameters travel as kernel arguments (< 4 KB): no copy command, no upload kernel.
+// All per-batch parameters travel as kernel arguments (7.2 KB with 32 scans per batch; the limit kept is 8 KB,
+// launch_mbatch's static_assert): no copy command, no upload kernel.  They are laid out by WHO reads them FIRST: a block
+// waits for one scalar round trip (the head, see k_mbatch) and a bin or scout block for a second (its scan's record,
+// MBinScan / MCropScan) before its vector loads leave.
 // Algorithmic bytes are per scan what they were: 12 B/point (+4 intensity, +4 colour), 72 / 124 B per
 // touched cell, 4 B per map cell per scan for the obstacle clear.
 #pragma once
@@ -75,6 +78,25 @@ constexpr int kScansPerThread = 4;   // update half: a thread looks after four s
 // the n lowest bits (n <= 32: a shift by 32 is not a shift)
 __host__ __device__ constexpr unsigned lowbits(unsigned n) { return n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u; }
 constexpr int kLineWords = 32;           // a 128-byte line of 32-bit words
+// "These values are in scalar registers HERE, all of them" (an input of an empty asm: a pointer that came OUT of one would
+// be a pointer of unknown kind — flat loads, which count on both wait counters): no instruction, but the compiler can no longer sink the
+// loads of kernel arguments that produce them behind a branch or behind each other's waits — loads that do not depend on
+// one another leave as one batch and the wavefront waits for them once (k_mbatch's head, a scan's record).
+// The other direction: a struct of the kernel arguments as seen from HERE on.  The compiler may not hoist a load of one of
+// its members above this point — into the block that dispatches the halves, where it would be one more round trip in
+// front of every block's first vector loads — and still knows the members are uniform constants (scalar loads): the
+// struct's address gains an offset the compiler cannot see is zero, nothing escapes.
+template <typename T>
+__device__ __forceinline__ const T& kernarg_from_here(const T& v) {
+  unsigned zero = 0u;
+  asm volatile("" : "+s"(zero));
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(&v) + zero);
+}
+#define FDM_SGPR_NOW4(a, b, c, d) asm volatile("" ::"s"(a), "s"(b), "s"(c), "s"(d))
+#define FDM_SGPR_NOW10(a, b, c, d, e, f, g, h, i, j) \
+  asm volatile("" ::"s"(a), "s"(b), "s"(c), "s"(d), "s"(e), "s"(f), "s"(g), "s"(h), "s"(i), "s"(j))
+#define FDM_SGPR_NOW11(a, b, c, d, e, f, g, h, i, j, k) \
+  asm volatile("" ::"s"(a), "s"(b), "s"(c), "s"(d), "s"(e), "s"(f), "s"(g), "s"(h), "s"(i), "s"(j), "s"(k))
 #ifndef FDM_MB_WAVES
 #define FDM_MB_WAVES 6  // waves per SIMD k_mbatch is compiled for (<= 80 VGPRs; the LDS allows 6 blocks per CU): every block of a 16-scan VLP-16 batch resident at once
 #endif
@@ -110,15 +132,30 @@ struct MCommon {  // what all scans of a batch share
 struct MScanT {   // per scan: T_world_base without its constant last row (0 0 0 1), column-major 3 x 4 | rotation of the product
   float Twb[12], R[9];
 };
+// One scan of the bin half.  A bin block knows its scan from the grid, and everything it needs of that scan before its
+// point loads can leave — the pointers and n — sits on one 64-byte line of the arguments, the transforms behind it: one
+// batch of scalar loads, one wait (parallel arrays n[], px[], py[] ... 256 bytes apart were a chain of dependent trips).
+struct MBinScan {
+  const float* px;
+  const float* py;
+  const float* pz;
+  const float* pint;
+  const uint32_t* prgb;
+  const float* pvar;
+  unsigned n, first_block;               // points of the scan | bin blocks before it
+  MScanT t;
+  unsigned pad;
+};
 struct MBin {     // bin half: batch b
   unsigned count, scan_no0;
-  unsigned first_block[kMaxBatch + 1];   // bin blocks before scan k
-  unsigned n[kMaxBatch];                 // points of scan k
   MState* ms;
-  const MState* prev;                    // the previous batch's state while its update shares this launch (else null)
-  unsigned prev_count;
+  // The previous batch's state while its update shares this launch.  Always readable: with no previous batch it is the
+  // batch's own state and has_prev is 0 (prev_count 1), so the loads through it leave unconditionally beside the
+  // geometry ring's and the choice is a select on the values (mbatch_start, mbin_body)
+  const MState* prev;
+  unsigned prev_count, has_prev;
   unsigned obs_stride;                   // points per scan slot of obs / cobs
-  unsigned pad[2];
+  unsigned pad;
   // per-scan scratch, slot k at + k * ncell (key, aux, zs as in Scratch)
   unsigned long long* key;
   uint4* aux;
@@ -127,14 +164,8 @@ struct MBin {     // bin half: batch b
   uint32_t* cobs;                        // [count][obs_stride] colour of block-local last points, by slot
   unsigned long long* bin_part;          // [bin blocks]
   float* cap;                            // raycasting: [3][count][obs_stride] map-frame x (NaN: dropped by the crops), y, z by point index (else null)
-  double robot_x[kMaxBatch], robot_y[kMaxBatch];  // T_world_base translation of every scan (the chain of moves)
-  const float* px[kMaxBatch];
-  const float* py[kMaxBatch];
-  const float* pz[kMaxBatch];
-  const float* pint[kMaxBatch];
-  const uint32_t* prgb[kMaxBatch];
-  const float* pvar[kMaxBatch];
-  MScanT t[kMaxBatch];
+  double robot_x[kMaxBatch], robot_y[kMaxBatch];  // T_world_base translation of every scan (the chain of moves; read by lane)
+  MBinScan s[kMaxBatch];
 };
 // Raycasting stage of the batch's scans (fastdem.cpp:152-159, once per scan BEHIND that scan's map update).  The ray
 // launches of fdm_rbatch.hpp leave, per scan, the two order-free images of processScan — observed-evidence counts and the
@@ -158,33 +189,37 @@ struct MRay {
   float l_obs, l_ghost, l_max, clear_thr, conflict_thr;
   float pad2;
 };
-struct MUpd {     // update half: batch b-1
+struct MUpd {     // update half: batch b-1 (the kernel's first struct argument: key and ms, which an update block's first
+                  // loads go through, lie directly behind the head's scalars and are fetched with them)
+  unsigned long long* key;
+  MState* ms;
   unsigned count, scan_no0, obs_stride;
   int do_move, gate_on_filter;
   unsigned pad;
   MRay ray;
-  MState* ms;
   MState* rearm;                         // the state of the batch after next: zeroed by the committing block
-  unsigned long long* key;
   uint4* aux;
   uint2* zs;
   const float2* obs;
   const uint32_t* cobs;
   uint32_t* upd_part;                    // [update blocks] cells touched by the batch's LAST scan
 };
+struct MCropScan {  // one scouted scan, as MBinScan: one batch of scalar loads
+  const float* px;
+  const float* py;
+  const float* pz;
+  unsigned n, pad;
+};
 struct MCrop {    // crop half: batch b+1 (count == 0: none)
   unsigned count, pad;
-  unsigned first_block[kMaxBatch + 1];
-  unsigned n[kMaxBatch];
   MState* ms;
   // the walker block: the scouted batch's poses, and — when no batch is binned by this launch (the scout-only launch in
   // front of a call's first batch) — where its chain starts: the previous batch's state (complete), or the geometry ring
-  double robot_x[kMaxBatch], robot_y[kMaxBatch];
+  // (has_prev 0: prev is then the scouted batch's own state, readable and unused, as MBin::prev)
   const MState* prev;
-  unsigned prev_count, scan_no0;
-  const float* px[kMaxBatch];
-  const float* py[kMaxBatch];
-  const float* pz[kMaxBatch];
+  unsigned prev_count, has_prev, scan_no0, pad1;
+  double robot_x[kMaxBatch], robot_y[kMaxBatch];
+  MCropScan s[kMaxBatch];
 };
 
 // The members the arithmetic reads, by name (pointers only: an array member copied in device code is spilled,
@@ -289,11 +324,15 @@ constexpr unsigned kMLdsBytes = sizeof(MUpdLds<COL, RAY>) > sizeof(MBinLds) ? si
 // traffic, for sixteen bits: configs[2] 10.5 us per scan, VERDICT r03 #6.)
 constexpr unsigned kMScout = 4u;
 __device__ __forceinline__ void mcrop_body(const MCrop& Cn, const MCommon& K, const unsigned k, const unsigned sb) {
+  unsigned n = Cn.s[k].n;
+  const float* px_ = Cn.s[k].px;
+  const float* py_ = Cn.s[k].py;
+  const float* pz_ = Cn.s[k].pz;
+  FDM_SGPR_NOW4(n, px_, py_, pz_);  // the scan's record: one batch, one wait (the crops' limits join it)
   const MView V = mview(K, nullptr, nullptr);
-  const unsigned n = Cn.n[k];
-  const float* __restrict__ const px = Cn.px[k];
-  const float* __restrict__ const py = Cn.py[k];
-  const float* __restrict__ const pz = Cn.pz[k];
+  const float* __restrict__ const px = px_;
+  const float* __restrict__ const py = py_;
+  const float* __restrict__ const pz = pz_;
 #pragma unroll 1
   for (unsigned i0 = sb * kMBlock; i0 < n; i0 += kMScout * kMBlock) {  // (block-uniform)
     bool pass = false;
@@ -335,16 +374,16 @@ __device__ __forceinline__ void mcrop_body(const MCrop& Cn, const MCommon& K, co
 // (it defers the index wrap of short moves, which yields the candidate's wrapped index).
 //
 // Geometry before the first scan of a batch, from the state of the batch before it (complete) or the geometry ring.
-__device__ __forceinline__ DevGeom mbatch_start(const MState* __restrict__ prev, unsigned prev_count, unsigned scan_no0,
-                                                const MCommon& K, const DevState* __restrict__ st) {
-  if (!prev) return st->geom[scan_no0 & 3u];
-  const unsigned pk = prev_count - 1u;
+// (prev is always readable — MBin::prev — so both sources are loaded together and the choice is a select)
+__device__ __forceinline__ DevGeom mbatch_start(const MState* __restrict__ prev, unsigned prev_count, bool has_prev,
+                                                unsigned scan_no0, const MCommon& K, const DevState* __restrict__ st) {
+  const unsigned pk = (prev_count - 1u) & unsigned(kMaxBatch - 1);  // (1 .. kMaxBatch: the mask only keeps a stray count inside the arrays)
+  const DevGeom ring = st->geom[scan_no0 & 3u];
   DevGeom g = prev->E[pk];
-  if (K.do_move && (!K.gate_on_filter || ((prev->flags[0] >> pk) & 1u) != 0u)) {
-    const DevCand c = prev->C[pk];
-    g.px = c.px; g.py = c.py; g.sr = c.sr; g.sc = c.sc;
-  }
-  return g;
+  const DevCand c = prev->C[pk];
+  const unsigned f = prev->flags[0];
+  if (K.do_move && (!K.gate_on_filter || ((f >> pk) & 1u) != 0u)) { g.px = c.px; g.py = c.py; g.sr = c.sr; g.sc = c.sc; }
+  return has_prev ? g : ring;
 }
 // The arithmetic of a chain of moves, shared by the walker (mwalk_batch) and the bin blocks' own walk (mbin_body): both
 // must produce the reference's numbers, so there is one copy.  move() snaps the position to the grid p0 + integer * res, so
@@ -414,49 +453,71 @@ __device__ __forceinline__ void mwalk_batch(DevGeom g, const unsigned count, con
 }
 // The walker block (first wavefront): chain of the scouted batch Cn into Cn.ms->PE / PC.
 __device__ __forceinline__ void mwalk_body(const MBin& B, const MCrop& Cn, const MCommon& K, const GeomConst& G,
-                                           const DevState* __restrict__ st) {
+                                           const DevState* __restrict__ st, const unsigned b_count, const unsigned c_count) {
   if (threadIdx.x >= 64u || !K.do_move || !K.walk || K.dbg == 2) return;
   const unsigned lane = threadIdx.x & 63u;
   DevGeom g;
-  if (B.count) {  // behind the batch this launch bins: its own chain as pre-walked if its scouts agreed, else walked here
+  if (b_count) {  // behind the batch this launch bins: its own chain as pre-walked if its scouts agreed, else walked here
     const unsigned act = K.gate_on_filter ? uni(B.ms->flags[0]) : 0xFFFFFFFFu, pre = uni(B.ms->flags[1]);
     const bool pre_valid = uni(B.ms->flags[2]) != 0u;
-    const unsigned last = B.count - 1u;
+    const unsigned last = b_count - 1u;
     DevGeom e_l;
     DevCand c_l;
     if (pre_valid && ((pre ^ act) & lowbits(last)) == 0u) {
       e_l = B.ms->PE[last];
       c_l = B.ms->PC[last];
     } else {
-      mwalk_batch(mbatch_start(B.prev, B.prev_count, B.scan_no0, K, st), B.count, B.robot_x, B.robot_y, act, K, G, nullptr,
-                  e_l, c_l);
+      mwalk_batch(mbatch_start(B.prev, B.prev_count, B.has_prev != 0u, B.scan_no0, K, st), b_count, B.robot_x, B.robot_y, act,
+                  K, G, nullptr, e_l, c_l);
     }
     g = e_l;
     if ((act >> last) & 1u) { g.px = c_l.px; g.py = c_l.py; g.sr = c_l.sr; g.sc = c_l.sc; }
   } else {
-    g = mbatch_start(Cn.prev, Cn.prev_count, Cn.scan_no0, K, st);
+    g = mbatch_start(Cn.prev, Cn.prev_count, Cn.has_prev != 0u, Cn.scan_no0, K, st);
   }
   DevGeom e_l;
   DevCand c_l;
-  mwalk_batch(g, Cn.count, Cn.robot_x, Cn.robot_y, 0xFFFFFFFFu, K, G, Cn.ms, e_l, c_l);
-  if (lane == 0u) { Cn.ms->flags[1] = lowbits(Cn.count); Cn.ms->flags[2] = 1u; }
+  mwalk_batch(g, c_count, Cn.robot_x, Cn.robot_y, 0xFFFFFFFFu, K, G, Cn.ms, e_l, c_l);
+  if (lane == 0u) { Cn.ms->flags[1] = lowbits(c_count); Cn.ms->flags[2] = 1u; }
 }
 
 // ---------------------------------------------------------------------------------------------
 // bin half: block `bid` of the batch's bin grid.  CH: bit 0 intensity, bit 1 colour (compile-time, as k_bin's).
 template <int CH, bool RAY>
-__device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const GeomConst& G,
+__device__ __forceinline__ void mbin_body(const MBin& B_, const MCommon& K_, const GeomConst& G_,
                                           DevState* __restrict__ st, const unsigned ncell, const unsigned k,
                                           const unsigned lb, MBinLds& S) {
   // (scan k of the batch and the block's number inside the scan come straight from the grid: nothing to look up
   // before the point loads can leave)
   constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
   const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  MState* const ms = B.ms;
-  const MView V = mview(K, B.t[k].Twb, B.t[k].R);
-  const float* __restrict__ const px = B.px[k];
-  const float* __restrict__ const py = B.py[k];
-  const float* __restrict__ const pz = B.pz[k];
+  // The block's ONE batch of scalar loads behind the head: scan k's record (MBinScan: one line) and what the first
+  // wavefront's geometry loads go through.  All of it is independent of everything but k, so it leaves together and the
+  // wavefront waits once; the surplus blocks of a short row leave behind that wait, not in front of the pointer loads.
+  // (prgb, pvar, first_block and the transforms are not needed before the point loads: they stay where they are used.)
+  const MBinScan& R = B_.s[k];
+  unsigned n_ = R.n;
+  const float* px_ = R.px;
+  const float* py_ = R.py;
+  const float* pz_ = R.pz;
+  const float* pint_ = has_int ? R.pint : nullptr;
+  MState* ms_ = B_.ms;
+  const MState* prev_ = B_.prev;
+  unsigned prev_count_ = B_.prev_count, has_prev_ = B_.has_prev, scan_no0_ = B_.scan_no0;
+  FDM_SGPR_NOW10(n_, px_, py_, pz_, pint_, ms_, prev_, prev_count_, has_prev_, scan_no0_);
+  const unsigned n = n_;
+  if (lb >= (n + kMBlock - 1u) / kMBlock) return;  // (block-uniform)
+  const MBin& B = kernarg_from_here(B_);  // (everything else of the arguments is read behind the point loads' issue)
+  const MCommon& K = kernarg_from_here(K_);
+  const GeomConst& G = kernarg_from_here(G_);
+  MState* const ms = ms_;
+  const MState* const prev = prev_;
+  const bool has_prev = has_prev_ != 0u;
+  const MView V = mview(K, R.t.Twb, R.t.R);
+  const float* __restrict__ const px = px_;
+  const float* __restrict__ const py = py_;
+  const float* __restrict__ const pz = pz_;
+  const float* __restrict__ const pint = pint_;
 
   // (the poses and the geometry the chain starts from leave before the point loads: loads return in order, and the
   // walk below waits for these; the previous batch's candidate is fetched whether or not it will apply — one round
@@ -476,16 +537,15 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     g_pre = ms->PE[k];
     c_pre = ms->PC[k];
     if (lane <= k) { pose_x = B.robot_x[lane]; pose_y = B.robot_y[lane]; }
-    if (B.prev) {
-      const unsigned pk = B.prev_count - 1u;
-      g_start = B.prev->E[pk];
-      c_prev = B.prev->C[pk];
-      f_prev = B.prev->flags[0];
-    } else {
-      g_start = st->geom[B.scan_no0 & 3u];
-    }
+    // (the chain's start: every address is known from the block's one batch of arguments — prev is always readable —
+    // so the loads leave unconditionally and together; which geometry applies is a select on two addresses, both
+    // valid, and costs no register and no wait in front of the point loads)
+    const unsigned pk = (prev_count_ - 1u) & unsigned(kMaxBatch - 1);
+    const DevGeom* const g_from = has_prev ? &prev->E[pk] : &st->geom[scan_no0_ & 3u];
+    g_start = *g_from;
+    c_prev = prev->C[pk];
+    f_prev = prev->flags[0];
   }
-  const unsigned n = B.n[k];
   const unsigned i0 = lb * kMBlock + threadIdx.x;  // the thread's points: i0, i0 + 256 (two coalesced sweeps)
   float xs[kMPts], ys[kMPts], zs[kMPts], vs[kMPts];
 #pragma unroll
@@ -496,7 +556,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
       xs[h] = px[i];
       ys[h] = py[i];
       zs[h] = pz[i];
-      if (has_int) vs[h] = B.pint[k][i];
+      if (has_int) vs[h] = pint[i];
     }
   }
 #if FDM_MB_PHASES == 2  // (variant: kernel arguments read + loads issued | loads back | chain walked)
@@ -527,8 +587,8 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
       return;
     }
     DevGeom g = g_start;
-    if (B.prev) {  // what the update of the previous batch (the other half of this launch) is about to commit
-      const unsigned pk = B.prev_count - 1u;
+    if (has_prev) {  // what the update of the previous batch (the other half of this launch) is about to commit
+      const unsigned pk = (prev_count_ - 1u) & unsigned(kMaxBatch - 1);
       if (K.do_move && (!K.gate_on_filter || ((f_prev >> pk) & 1u) != 0u)) {
         g.px = c_prev.px; g.py = c_prev.py; g.sr = c_prev.sr; g.sc = c_prev.sc;
       }
@@ -636,6 +696,9 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   uint32_t* const S_zs = reinterpret_cast<uint32_t*>(B.zs + size_t(k) * ncell);
   float2* const S_obs = B.obs + size_t(k) * B.obs_stride;
   uint32_t* const S_cobs = B.cobs + size_t(k) * B.obs_stride;
+  // (the rest of the scan's record, read once here and not per record of the flush)
+  const uint32_t* __restrict__ const prgb = has_col ? R.prgb : nullptr;
+  const float* __restrict__ const pvar = R.pvar;
 
   // one cell's reduction goes to the scan's scratch; the merging thread also leaves what the update needs of the
   // block-local winner / last point in the block's SLOT for the cell: slot = lb * kMBlock + j, j = the number the
@@ -662,12 +725,12 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
     }
     if (has_col) {
       atomicMax(a + 3, slot);
-      S_cobs[slot] = B.prgb[k][lst];
+      S_cobs[slot] = prgb[lst];
     }
     if (idx != kNoIdx) {
       const float4 p = S.s_pt[idx - lb * kMBlock];
       float var = 0.0f;  // CellObservation default (elevation_mapping.hpp:26-34)
-      if (K.has_var) var = B.pvar[k][idx];
+      if (K.has_var) var = pvar[idx];
       else if (K.integrate_mode) var = sigma_z2(V, p.x, p.y, p.z);
       S_obs[slot] = make_float2(p.w, var);
     }
@@ -827,7 +890,7 @@ __device__ __forceinline__ void mbin_body(const MBin& B, const MCommon& K, const
   }
   if (threadIdx.x == 0) {
     const unsigned ni = S.s_in[0] + S.s_in[1] + S.s_in[2] + S.s_in[3];
-    B.bin_part[B.first_block[k] + lb] = (unsigned long long)np | ((unsigned long long)ni << 32);
+    B.bin_part[R.first_block + lb] =(unsigned long long)np | ((unsigned long long)ni << 32);
   }
 }
 
@@ -861,11 +924,11 @@ struct MCell {
 // Block 0 behind round trip 1: thread 0 commits the geometry ring behind the batch (make_ctx does this per scan), threads
 // 64 .. 64 + kMaxBatch re-arm the state of the batch after next.
 template <int CH, bool RAY>
-__device__ __forceinline__ void mupd_commit(const MUpd& U, DevState* __restrict__ st, const unsigned bid,
-                                            const unsigned passbits, const unsigned umask, const unsigned runmask) {
+__device__ __forceinline__ void mupd_commit(const MUpd& U, DevState* __restrict__ st, const unsigned bid, const unsigned count,
+                                            MState* const ms, const unsigned passbits, const unsigned umask,
+                                            const unsigned runmask) {
   constexpr bool has_int = (CH & 1) != 0, has_col = (CH & 2) != 0;
-  const unsigned lt = threadIdx.x, count = U.count;
-  MState* const ms = U.ms;
+  const unsigned lt = threadIdx.x;
   if (bid == 0 && lt == 0) {
     const unsigned last = count - 1u;
     const unsigned slot_next = (U.scan_no0 + count) & 3u;
@@ -1272,19 +1335,23 @@ __device__ __forceinline__ void mupd_walk_ray(const MUpd& U, const typename POLI
 }
 
 template <typename POLICY, int CH, bool RAY>
-__device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, DevState* __restrict__ st,
-                                             const typename POLICY::Layers& L,
+__device__ __forceinline__ void mupdate_body(const MUpd& U_, const GeomConst& G_, DevState* __restrict__ st,
+                                             const typename POLICY::Layers& L_,
                                              float* const* __restrict__ all_layers, int n_layers,
-                                             const unsigned ncell, const unsigned bid,
+                                             const unsigned ncell, const unsigned bid, const unsigned count,
+                                             const unsigned long long* const u_key, MState* const u_ms,
                                              MUpdLds<(CH & 2) != 0, RAY>& S) {
+  // (count, U.key and U.ms arrive with the kernel's head: the key loads and the geometry loads wait for nothing else)
+  const MUpd& U = U_;
+  const GeomConst& G = G_;
+  const typename POLICY::Layers& L = L_;
   const unsigned lt = threadIdx.x, lane = lt & 63u, wave = lt >> 6;
-  const unsigned count = U.count;
   const unsigned tpc = upd_threads_per_cell(count), cpb = 256u / tpc;   // threads per cell, cells per block (block-uniform)
   const unsigned cl = lt & (cpb - 1u), cq = tpc == 8u ? lt >> 5 : lt >> 6;   // cell of the block, group of four scans
   const unsigned o = bid * cpb + cl;
   const bool valid = o < ncell;
   const bool owner = valid && cq == 0u;  // the thread that applies the cell's events: wavefront 0, lane = cell
-  MState* const ms = U.ms;
+  MState* const ms = u_ms;
 
   // ---- round trip 1: the thread's four keys, the per-scan geometry (lane j holds scan j's) ----
   unsigned long long kk[kScansPerThread];
@@ -1292,7 +1359,7 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
   for (int j = 0; j < kScansPerThread; ++j) {
     const unsigned k = cq * unsigned(kScansPerThread) + unsigned(j);
     kk[j] = kEmptyKey;
-    if (k < count && valid) kk[j] = U.key[size_t(k) * ncell + o];
+    if (k < count && valid) kk[j] = u_key[size_t(k) * ncell + o];
   }
   float* lay_p = nullptr;  // (wavefront 1, no owner in it: the layer pointers join round trip 1)
   if constexpr (!RAY) {
@@ -1339,7 +1406,7 @@ __device__ __forceinline__ void mupdate_body(const MUpd& U, const GeomConst& G, 
   const unsigned umask = uni(unsigned(__ballot(lane < count && v_in != 0u)));                     // scans that observed a cell
   const unsigned stripmask = uni(unsigned(__ballot(v_applied && (v_shr != 0 || v_shc != 0))));   // scans whose move vacated cells
 
-  mupd_commit<CH, RAY>(U, st, bid, passbits, umask, runmask);
+  mupd_commit<CH, RAY>(U, st, bid, count, ms, passbits, umask, runmask);
 
   unsigned nib = 0u;
 #pragma unroll
@@ -1403,33 +1470,43 @@ template <typename POLICY> struct MBatchWaves { static constexpr int value = FDM
 template <> struct MBatchWaves<P2RecPolicy> { static constexpr int value = FDM_MB_WAVES - 1; };
 template <> struct MBatchWaves<P2Policy> { static constexpr int value = FDM_MB_WAVES - 1; };
 
+// The HEAD: the eight leading scalars are everything that decides which half a block belongs to and which scan or cells
+// are its own — the launch geometry (with the grid's width, so the hidden gridDim.x is not read), the three halves' scan
+// counts (copies of U.count, B.count, Cn.count) and whether stamps are wanted — and directly behind them lie the two
+// pointers an update block's first loads go through (MUpd::key, MUpd::ms).  They are fetched in one batch and used
+// unconditionally: one scalar round trip, then a bin or scout block fetches its scan's record (a second one) and its
+// vector loads leave.  The parent's arguments were a chain of dependent reads 5-8 deep (timeline pointer -> upd_rows ->
+// B.count -> n[k] -> px[k] ... -> ms -> prev -> prev_count), about 0.2 us each under this launch
+// (scripts/ubench/kernarg_chain.hip).  t0 is taken without waiting for an argument.
 template <typename POLICY, int CH, bool RAY>
-__global__ __launch_bounds__(256, MBatchWaves<POLICY>::value) void k_mbatch(const MUpd U, const MBin B, const MCrop Cn, const MCommon K,
-                                                const GeomConst G, DevState* __restrict__ st,
+__global__ __launch_bounds__(256, MBatchWaves<POLICY>::value) void k_mbatch(unsigned upd_rows, unsigned n_upd_blocks, unsigned ncell,
+                                                unsigned width, unsigned u_count, unsigned b_count, unsigned c_count,
+                                                unsigned stamps, unsigned long long* u_key, MState* u_ms,
+                                                const MUpd U, const MBin B, const MCrop Cn,
+                                                const MCommon K, const GeomConst G, DevState* __restrict__ st,
                                                 const typename POLICY::Layers L,
-                                                float* const* __restrict__ all_layers, int n_layers,
-                                                unsigned ncell, unsigned n_upd_blocks, unsigned upd_rows) {
+                                                float* const* __restrict__ all_layers, int n_layers) {
   __shared__ __align__(16) unsigned char lds[kMLdsBytes<(CH & 2) != 0, RAY>];
-  const unsigned long long t0 = K.timeline ? wall_clock64() : 0ull;
+  const unsigned long long t0 = wall_clock64();
+  FDM_SGPR_NOW10(upd_rows, n_upd_blocks, ncell, width, u_count, b_count, c_count, stamps, u_key, u_ms);
 #if FDM_MB_PHASES
   if (threadIdx.x == 0) { g_phase[0] = g_phase[1] = g_phase[2] = unsigned(t0); }
 #endif
   const unsigned row = blockIdx.y, x = blockIdx.x;
   if (row < upd_rows) {
-    const unsigned ub = row * gridDim.x + x;
+    const unsigned ub = row * width + x;
     if (ub < n_upd_blocks)
-      mupdate_body<POLICY, CH, RAY>(U, G, st, L, all_layers, n_layers, ncell, ub,
+      mupdate_body<POLICY, CH, RAY>(U, G, st, L, all_layers, n_layers, ncell, ub, u_count, u_key, u_ms,
                                     *reinterpret_cast<MUpdLds<(CH & 2) != 0, RAY>*>(lds));
-  } else if (row < upd_rows + B.count) {
-    const unsigned k = row - upd_rows;
-    if (x < (B.n[k] + kMBlock - 1u) / kMBlock) mbin_body<CH, RAY>(B, K, G, st, ncell, k, x, *reinterpret_cast<MBinLds*>(lds));
-  } else {  // scout rows: block c of Cn.count * kMScout
-    const unsigned c = (row - upd_rows - B.count) * gridDim.x + x;
-    if (c < Cn.count * kMScout) mcrop_body(Cn, K, c / kMScout, c % kMScout);
-    else if (c == Cn.count * kMScout && Cn.count) mwalk_body(B, Cn, K, G, st);
+  } else if (row < upd_rows + b_count) {  // (a surplus block of a short row leaves inside, behind its record)
+    mbin_body<CH, RAY>(B, K, G, st, ncell, row - upd_rows, x, *reinterpret_cast<MBinLds*>(lds));
+  } else {  // scout rows: block c of c_count * kMScout
+    const unsigned c = (row - upd_rows - b_count) * width + x;
+    if (c < c_count * kMScout) mcrop_body(Cn, K, c / kMScout, c % kMScout);
+    else if (c == c_count * kMScout && c_count) mwalk_body(B, Cn, K, G, st, b_count, c_count);
   }
-  if (K.timeline && threadIdx.x == 0) {  // (thread 0's view of the block; scripts/timeline_batch.py)
-    const unsigned b = blockIdx.y * gridDim.x + x;
+  if (stamps && threadIdx.x == 0) {  // (thread 0's view of the block; scripts/timeline_batch.py)
+    const unsigned b = blockIdx.y * width + x;
     K.timeline[2u * b] = t0;
 #if FDM_MB_PHASES
     K.timeline[2u * b + 1u] = phase_word(t0);
