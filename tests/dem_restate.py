@@ -6,6 +6,9 @@ data, not product.
   restate_sor             nanopcl::filters::statisticalOutlierRemoval   outlier_removal_impl.hpp:83-142
   restate_ground_peak     findGroundPeak                                pcd_convert.cpp:194-220
   restate_floating        removeFloatingPoints                          pcd_convert.cpp:228-269
+  restate_floating_grouped  the same mask by NumPy grouping, for clouds of 10^5 points (proved equal to the loop above in
+                          tests/test_dem_restate.py); floating_cells / floating_bins: its cells and bin indices, which
+                          the proofs of tests/dem_cases.py read
   restate_build_dem       buildDEM                                      pcd_convert.cpp:275-323
 
 For tests/test_sor_edges_gpu.py (clouds built against the engine's column search, tests/sor_cases.py):
@@ -186,6 +189,70 @@ def restate_floating(grid, x, y, z, height_threshold, bin_size):
     return keep
 
 
+def floating_cells(grid, x, y, z):
+    """int64[n]: the key (row << 32 | col) of the oracle's cell of every point, -1 where removeFloatingPoints skips the
+    point (:236-241: a NaN z, no cell)."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    key = np.full(x.size, -1, dtype=np.int64)
+    for i in np.flatnonzero(~np.isnan(z)):
+        ok, (r, c) = grid.get_index(float(x[i]), float(y[i]))
+        if ok:
+            key[i] = (int(r) << 32) | int(c)
+    return key
+
+
+def floating_bins(key, z, bin_size):
+    """(live, group, z_min, bins): the indices of the points that have a cell, the number of each one's cell among the
+    distinct cells (ascending key), float32 z_min per cell, and int64 bin per live point — findGroundPeak's
+    min(int((z - z_min) / bin), n_bins - 1) with n_bins = max(1, int((z_max - z_min) / bin) + 1), every operation rounded
+    to fp32 as in restate_ground_peak; OverflowError where _int_cast raises."""
+    z = np.asarray(z, dtype=F32)
+    live = np.flatnonzero(key >= 0)
+    uniq, group = np.unique(key[live], return_inverse=True)
+    zl, b = z[live], F32(bin_size)
+    z_min, z_max = np.full(uniq.size, np.inf, dtype=F32), np.full(uniq.size, -np.inf, dtype=F32)
+    np.minimum.at(z_min, group, zl)
+    np.maximum.at(z_max, group, zl)
+    with np.errstate(all="ignore"):
+        span = (z_max - z_min) / b
+        at = (zl - z_min[group]) / b
+    assert span.dtype == F32 and at.dtype == F32
+    for v in (span, at):
+        if not ((v > -2147483649.0) & (v < 2147483648.0)).all():     # a NaN too
+            raise OverflowError("float does not fit an int")
+    n_bins = np.maximum(1, span.astype(np.int64) + 1)                # astype: truncation, as static_cast<int>
+    return live, group, z_min, np.minimum(at.astype(np.int64), n_bins[group] - 1)
+
+
+def restate_floating_grouped(grid, x, y, z, height_threshold, bin_size, key=None):
+    """restate_floating's mask, cell by cell in NumPy instead of point by point: the same fp32 operations in the same
+    order per value.  `key`: floating_cells(grid, x, y, z) where the caller has it already."""
+    x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
+    if key is None:
+        key = floating_cells(grid, x, y, z)
+    keep = np.zeros(x.size, dtype=bool)
+    live, group, z_min, bins = floating_bins(key, z, bin_size)
+    if live.size == 0:
+        return keep
+    # runs of equal (cell, bin); per cell the LOWEST bin among those with the largest count (:209-216, strict '>')
+    order = np.lexsort((bins, group))
+    g, b = group[order], bins[order]
+    head = np.flatnonzero(np.r_[True, (g[1:] != g[:-1]) | (b[1:] != b[:-1])])
+    count = np.diff(np.r_[head, g.size])
+    rg, rb = g[head], b[head]
+    pick = np.lexsort((rb, -count, rg))
+    first = pick[np.r_[True, rg[pick][1:] != rg[pick][:-1]]]
+    best = np.empty(z_min.size, dtype=np.int64)
+    best[rg[first]] = rb[first]
+    bs = F32(bin_size)
+    with np.errstate(all="ignore"):
+        ground = z_min + (best.astype(F32) + F32(0.5)) * bs          # :219
+        cutoff = ground + F32(height_threshold)                      # :257
+    assert ground.dtype == F32 and cutoff.dtype == F32
+    keep[live] = z[live] <= cutoff[group]
+    return keep
+
+
 class DEM:
     """What restate_build_dem returns: geometry tuple (restate_auto_geometry), grid, layers in order, the stage counts."""
 
@@ -203,12 +270,14 @@ class DEM:
 
 
 def restate_build_dem(R, x, y, z, intensity=None, rgb=None, resolution=0.1, method="max", sor_k=10, sor_std_mul=1.0,
-                      height_threshold=2.0, bin_size=0.0, inpaint_iterations=3):
-    """A DEM, or None where the reference returns an uninitialised map (:276, :282)."""
+                      height_threshold=2.0, bin_size=0.0, inpaint_iterations=3, sor=None, floating=restate_floating):
+    """A DEM, or None where the reference returns an uninitialised map (:276, :282).  `sor`: (keep, threshold) of the
+    outlier removal where the caller has shown what it is without the k-NN search (a cloud too large for every pair);
+    `floating`: restate_floating or restate_floating_grouped."""
     x, y, z = (np.asarray(v, dtype=F32) for v in (x, y, z))
     if x.size == 0:
         return None
-    keep, _, thr = restate_sor(x, y, z, sor_k, sor_std_mul)
+    keep, thr = sor if sor is not None else restate_sor(x, y, z, sor_k, sor_std_mul)[::2]
     if not keep.any():
         return None
     sel = lambda a: None if a is None else np.asarray(a)[keep]       # noqa: E731
@@ -222,7 +291,7 @@ def restate_build_dem(R, x, y, z, intensity=None, rgb=None, resolution=0.1, meth
     g = out.grid.geometry()
     assert (g.length_x, g.length_y, g.resolution, g.rows, g.cols) == (geo[0], geo[1], geo[2], geo[5], geo[6])
     b = F32(bin_size) if bin_size > 0 else res                       # :308-309
-    keep2 = restate_floating(out.grid, x, y, z, height_threshold, b)
+    keep2 = floating(out.grid, x, y, z, height_threshold, b)
     sel2 = lambda a: None if a is None else a[keep2]                 # noqa: E731
     x, y, z, intensity, rgb = x[keep2], y[keep2], z[keep2], sel2(intensity), sel2(rgb)
     out.n_after_height = int(x.size)

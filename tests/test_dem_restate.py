@@ -230,3 +230,197 @@ def test_brute_force_clouds_reach_the_queue_by_the_grid_rule():
     assert 15.0 * 15.0 > float(SC.lb2(4, 0.5, h))                    # the tie's 15 m are beyond the bound of ring 4
     mean = DR.knn_mean_distances_of(x, y, z, k, np.arange(3000, x.size))
     assert (mean[:16] == 0).all() and (mean[16:21] > 10).all() and mean[21] == 15.0
+
+
+# ---- the clouds of tests/dem_cases.py: which path of the filter and of the compaction each one reaches.  What is shown
+# here on the restatement alone, tests/test_dem_edges_gpu.py does not assert again ----
+import dem_cases as DC  # noqa: E402
+import test_build_dem_gpu as TB  # noqa: E402
+
+# passes of the bin sort (keys 0 .. the largest bin index) and of the cell sort (keys 0 .. ncell, the skip key)
+PASSES = {"bins_2": (2, 3), "bins_3": (3, 3), "bins_4": (4, 3), "cells_1": (1, 1), "cells_256": (2, 2), "cells_4": (1, 4),
+          "long_run": (2, 2), "tile_large": (3, 2), "moved": (1, 2)}
+
+
+def ncell_of(name):
+    g = DC.grid_of(DC.filter_case(name)).geometry()
+    return g.rows * g.cols
+
+
+def test_sort_passes_follow_rs_key_bits():
+    assert [DC.sort_passes(v) for v in (0, 1, 255, 256, 65535, 65536, (1 << 24) - 1, 1 << 24, (1 << 32) - 1, 1 << 40)] == \
+        [1, 1, 1, 2, 2, 3, 3, 4, 4, 4]
+
+
+@pytest.mark.parametrize("name", DC.FILTER_CASES)
+def test_filter_case_reaches_its_passes(R, name):
+    c, r = DC.filter_case(name), DC.restated_filter(name)
+    print(f"{name}: {c.x.size} points, {(r.key >= 0).sum()} with a cell, restated in {r.seconds:.2f} s")
+    assert (DC.sort_passes(DC.largest_bin(name)), DC.sort_passes(ncell_of(name))) == PASSES[name]
+    live = r.key >= 0
+    assert 0.05 < r.keep[live].mean() < 0.95 and not r.keep[~live].any()
+
+
+def test_cell_counts_at_the_edges_of_a_pass(R):
+    assert ncell_of("cells_1") == 255 and ncell_of("cells_256") == 256 and ncell_of("cells_4") == 4097 * 4096 >= 1 << 24
+    assert ncell_of("bins_2") == 260 * 260
+    assert DC.sort_passes(256 - 1) == 1                              # what a sort sized for the cells alone would take
+
+
+@pytest.mark.parametrize("name", DC.FILTER_CASES)
+def test_grouped_restatement_equals_the_loop_on_the_filter_cases(R, name):
+    c, r = DC.filter_case(name), DC.restated_filter(name)
+    loop = DR.restate_floating(DC.grid_of(c), c.x, c.y, c.z, c.height_threshold, DC.bin_of(c))
+    assert np.array_equal(loop, r.keep)
+
+
+@pytest.mark.parametrize("height_threshold,bin_size", [(2.0, 0.0), (2.0, 0.25), (0.5, 0.0), (0.5, 0.03), (np.nan, 0.0)])
+def test_grouped_restatement_equals_the_loop_on_the_first_filter_cloud(R, height_threshold, bin_size):
+    x, y, z = TB.filter_cloud()
+    grid = R.RefEngine(float(F32(TB.W)), float(F32(TB.H)), float(F32(TB.RES)))
+    b = F32(bin_size) if bin_size > 0 else F32(TB.RES)
+    assert np.array_equal(DR.restate_floating_grouped(grid, x, y, z, height_threshold, b),
+                          DR.restate_floating(grid, x, y, z, height_threshold, b))
+
+
+@pytest.mark.parametrize("name", DC.COMPARED)
+def test_grouped_restatement_equals_the_loop_in_the_pipelines(R, name):
+    a, b = DC.restated_pipeline(name)[0], DC.restated_pipeline(name, "loop")[0]
+    assert (a.n_after_sor, a.n_after_height, a.geometry, a.layers()) == (b.n_after_sor, b.n_after_height, b.geometry, b.layers())
+    for k in a.layers():
+        assert np.array_equal(a.layer(k).view(np.uint32), b.layer(k).view(np.uint32)), k
+
+
+def test_grouped_restatement_refuses_what_the_loop_refuses(R):
+    grid = R.RefEngine(4.0, 3.0, 0.1)
+    x = y = np.zeros(2, dtype=F32)
+    for f in (DR.restate_floating, DR.restate_floating_grouped):
+        with pytest.raises(OverflowError):
+            f(grid, x, y, np.array([0.0, 3e9], dtype=F32), 2.0, F32(1.0))
+        assert f(grid, x, y, np.array([0.0, 2e9], dtype=F32), 2.0, F32(1.0)).tolist() == [True, False]
+
+
+def test_bin_sizes_give_different_masks_and_the_hand_made_cells_their_answers(R):
+    masks = {n: DC.restated_filter(n).keep for n in DC.BIN_SIZES}
+    assert all((masks[a] != masks[b]).any() for a in masks for b in masks if a < b)
+    for name, keep in masks.items():
+        c = DC.filter_case(name)
+        m = c.marks
+        assert list(c.z[m["tie_low_first"]]) == [0.5, 0.5, 30.0, 30.0, 10.0]          # the input order is the designed one
+        assert list(c.z[m["tie_high_first"]]) == [30.0, 30.0, 0.5, 0.5, 10.0]
+        assert keep[m["tie_low_first"]].tolist() == [True, True, False, False, False]
+        assert keep[m["tie_high_first"]].tolist() == [False, False, True, True, False]
+        at = m["cutoff_" + name]
+        cut = DC.cutoff_of_zero(DC.BIN_SIZES[name], DC.BINS_HT)
+        assert c.z[at[3]] == cut and c.z[at[4]] == np.nextafter(cut, F32(9)) and c.z[at[4]].dtype == F32
+        assert keep[at].tolist() == [True, True, True, True, False]
+        assert keep[m["single"]].all() and keep[m["all_equal"]].all() and keep[m["peak_high"]].all()
+        assert keep[m["majority_low"]].sum() == 40 and keep[m["three_peaks"]].tolist() == [True, True] + [False] * 4
+        assert keep[m["negative"]].tolist() == [True, True, False, False]
+        assert keep[m["peak_inside"]].tolist() == [True] * 5 + [False]
+        for idx in m.values():                                       # every hand-made cell is a cell of its own
+            assert len(set(DC.restated_filter(name).key[idx])) == 1
+        assert np.isnan(c.z[-2:]).all() and (DC.restated_filter(name).key[-4:] == -1).all()
+
+
+def test_cells_256_puts_skipped_points_between_the_points_of_storage_cell_0(R):
+    c, r = DC.filter_case("cells_256"), DC.restated_filter("cells_256")
+    cell0 = np.flatnonzero(r.key == DC.cell_key(0, 0))
+    early, high = c.marks["cell0_early"], c.marks["cell0_high"]
+    assert np.array_equal(cell0, np.concatenate([early, high]))
+    between = np.arange(early[-1] + 1, high[0])
+    assert (r.key[between] == -1).sum() >= 50 and np.isin(c.marks["skipped"], between).all()
+    assert (r.key[c.marks["skipped"]] == -1).all()
+    assert np.isnan(c.z[between]).sum() == 30                        # half without a z, half outside the map
+    live, group, z_min, bins = DR.floating_bins(r.key, c.z, DC.bin_of(c))
+    b0 = bins[np.isin(live, cell0)]
+    assert np.unique(b0).size == 501 and np.bincount(b0).max() == 5 == (b0 == 0).sum()
+    assert r.keep[early].all() and not r.keep[high].any()            # the peak is bin 0: all thousand go
+    # the run of the thousand alone has its peak in bin 10: a cutoff of 1.55 m would keep the first dozen of them
+    assert np.bincount(b0[5:]).argmax() == 10 and (c.z[high] <= 1.55).sum() == 12
+
+
+def test_long_run_has_its_two_cells(R):
+    c, r = DC.filter_case("long_run"), DC.restated_filter("long_run")
+    a = np.flatnonzero(r.key == DC.cell_key(*DC.LONG_CELL))
+    b = np.flatnonzero(r.key == DC.cell_key(*DC.ONE_BIN_CELL))
+    assert a.size == 5000 and b.size == 1025
+    assert np.array_equal(a, c.marks["long"]) and np.array_equal(b, c.marks["one_bin"])
+    live, group, z_min, bins = DR.floating_bins(r.key, c.z, DC.bin_of(c))
+    count = np.bincount(bins[np.isin(live, a)])
+    assert (count > 0).sum() == 410 >= 300 and np.flatnonzero(count == count.max()).tolist() == [5, 350]
+    assert np.unique(bins[np.isin(live, b)]).size == 1
+    cut = F32(F32(F32(0.0) + F32(F32(5.5) * F32(0.01))) + F32(0.5))
+    assert np.array_equal(r.keep[a], c.z[a] <= cut) and 500 < r.keep[a].sum() < 1000   # the low peak is the ground
+    assert r.keep[b].all()
+    # in the input the two cells' points and the others' alternate: no stretch of 256 inputs is one cell's alone
+    other = r.key != DC.cell_key(*DC.LONG_CELL)
+    runs = np.diff(np.flatnonzero(np.r_[True, other, True]))
+    assert runs.max() < 64 and a[-1] - a[0] > 7000 and b[-1] - b[0] > 7000
+
+
+def test_tile_large_is_beyond_the_small_tile(R):
+    c, r = DC.filter_case("tile_large"), DC.restated_filter("tile_large")
+    assert c.x.size == 600_001 > 600_000 and (r.key >= 0).sum() == 20_000 == (~np.isnan(c.z)).sum()
+
+
+def test_moved_map_has_a_start_index(R):
+    c, r = DC.filter_case("moved"), DC.restated_filter("moved")
+    g = DC.grid_of(c).geometry()
+    assert g.start_row != 0 and g.start_col != 0 and (g.rows, g.cols) == (40, 30)
+    for name, idx in c.marks.items():
+        assert len(set(r.key[idx])) == 1 and r.keep[idx].tolist() == [True] * 46 + [False, False], name
+    assert {DC.cell_key(0, 0), DC.cell_key(39, 29), DC.cell_key(g.start_row, g.start_col)} <= set(r.key)
+    assert (r.key[-2:] == -1).all()
+
+
+def test_none_survives_and_the_reference_returns_the_bare_map(R):
+    for name in DC.NONE_SURVIVE:
+        dem = DC.restated_pipeline(name)[0]
+        assert dem is not None and dem.n_after_height == 0 < dem.n_after_sor
+        assert dem.layers() == ["elevation", "elevation_min", "elevation_max"]
+        assert all(np.isnan(dem.layer(k)).all() for k in dem.layers()) and dem.geometry[5:] == (31, 21)
+    few = DC.restated_pipeline("minus_one_metre")[0]
+    assert 0 < few.n_after_height < 64                               # less than one wavefront of survivors
+
+
+def test_odd_geometries(R):
+    assert DC.restated_pipeline("one_cell")[0].geometry[5:] == (1, 1)
+    assert DC.restated_pipeline("one_row")[0].geometry[5:] == (1, 41)
+    p, dem = DC.pipeline("utm"), DC.restated_pipeline("utm")[0]
+    assert dem.geometry[3:5] == (5.0e5, 4.9e6) and np.unique(p.cloud["y"]).size < 200   # fp32 steps of 0.5 m in y
+    keep = DR.restate_sor(p.cloud["x"], p.cloud["y"], p.cloud["z"], p.config["sor_k"], p.config["sor_std_mul"])[0]
+    key = DR.floating_cells(dem.grid, p.cloud["x"][keep], p.cloud["y"][keep], p.cloud["z"][keep])
+    print(f"utm: {(key < 0).sum()} of {key.size} survivors of the outlier removal have no cell")
+    for name in ("one_cell", "one_row", "utm"):
+        d = DC.restated_pipeline(name)[0]
+        assert 0 < d.n_after_height < d.n_after_sor < DC.pipeline(name).cloud["x"].size
+
+
+def test_scan_chunks_has_more_than_1024_blocks_in_both_compactions(R):
+    p = DC.pipeline("scan_chunks")
+    dem, seconds = DC.restated_pipeline("scan_chunks")
+    print(f"scan_chunks restated in {seconds:.1f} s")
+    n = p.cloud["x"].size
+    assert n == DC.N_SCAN_CHUNKS >= 262_145 + 256 and dem.n_after_sor == n
+    assert -(-n // 256) > 1024 and -(-dem.n_after_sor // 256) > 1024
+    gone = 1.0 - dem.n_after_height / dem.n_after_sor
+    assert 0.10 < gone < 0.40, gone
+    assert p.config["sor_std_mul"] == 1e9 and np.sqrt(n) < 1e9       # the docstring's argument: every point passes SOR
+
+
+def test_refused_late_is_refused_by_the_height_filter_and_not_before(R):
+    p = DC.pipeline("refused_late")
+    c = p.cloud
+    keep, _, thr = DR.restate_sor(c["x"], c["y"], c["z"], p.config["sor_k"], p.config["sor_std_mul"])
+    assert keep.all() and np.isfinite(thr) and c["z"][-1] == F32(3e9)
+    with pytest.raises(OverflowError):
+        DC.restated_pipeline("refused_late")
+
+
+def test_fallback_cloud_reaches_the_queue_by_the_grid_rule(R):
+    p = DC.pipeline("fallback")
+    n = p.cloud["x"].size
+    assert DC.sor_must_queue(p.cloud, p.config["sor_k"], np.arange(n - 6, n)) == 6
+    keep = DR.restate_sor(p.cloud["x"], p.cloud["y"], p.cloud["z"], p.config["sor_k"], p.config["sor_std_mul"])[0]
+    assert not keep[-6:].any() and DC.restated_pipeline("fallback")[0].geometry[5:] == (31, 21)
