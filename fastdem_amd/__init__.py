@@ -10,8 +10,8 @@ Layout (only what the path needs):
   cpp/         C++17 host mirror of fastdem::FastDEM / ElevationMap over the C ABI
 """
 from . import capi, synth  # noqa: F401
-from .engine import (ClusterResult, DEMConfig, Engine, EngineError, HostArray, RansacResult, RegistrationResult, align_gicp,  # noqa: F401
-                     align_icp, align_plane_icp, align_settings, apply_cluster_labels, build_dem, cluster_last_stats, estimate_normals, euclidean_cluster,
+from .engine import (ClusterResult, DEMConfig, Engine, EngineError, HostArray, RansacResult, RegistrationResult, VoxelMap, align_gicp,  # noqa: F401
+                     align_icp, align_plane_icp, align_settings, align_vgicp, linearize_vgicp, apply_cluster_labels, build_dem, cluster_last_stats, estimate_normals, euclidean_cluster,
                      from_point_cloud,
                      grid_max_z, host_array, linearize, normals_last_stats, register_last_stats, segment_ground,
                      segment_last_stats, segment_multiple_planes, segment_plane, sor_last_stats,
@@ -21,6 +21,7 @@ from . import pcd  # noqa: F401,E402
 __all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud", "DEMConfig", "build_dem",
            "statistical_outlier_removal", "sor_last_stats", "voxel_grid", "grid_max_z", "estimate_normals",
            "normals_last_stats", "align_icp", "align_plane_icp", "align_gicp", "linearize", "align_settings",
+           "VoxelMap", "align_vgicp", "linearize_vgicp",
            "register_last_stats", "RegistrationResult", "segment_ground", "segment_plane", "segment_multiple_planes",
            "segment_last_stats", "RansacResult", "euclidean_cluster", "apply_cluster_labels",
            "cluster_last_stats", "ClusterResult", "capi", "synth", "pcd"]

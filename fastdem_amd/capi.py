@@ -145,6 +145,13 @@ class FdmRegisterStats(C.Structure):  # fdm_register_stats
                 ("voxel", C.c_float), ("ring_limit", C.c_int32), ("linearizations", C.c_int32), ("ms", C.c_float * 3)]
 
 
+class FdmVoxelMapInfo(C.Structure):  # fdm_voxel_map_info
+    _fields_ = [("resolution", C.c_float), ("inv_resolution", C.c_float), ("covariance_epsilon", C.c_double),
+                ("device", C.c_int32), ("reserved", C.c_int32), ("n_points", C.c_uint64), ("n_skipped", C.c_uint64),
+                ("num_voxels", C.c_uint64), ("n_sparse", C.c_uint64), ("table_slots", C.c_uint64),
+                ("max_count", C.c_uint32), ("max_probe", C.c_uint32), ("ms", C.c_float * 3), ("reserved2", C.c_float)]
+
+
 class FdmGroundSegConfig(C.Structure):
     """fdm_ground_seg_config == nanopcl::segmentation::GroundSegConfig (segmentation/ground_seg.hpp:34-40)."""
 
@@ -371,6 +378,15 @@ PROTOTYPES = {
     "fdm_cloud_register_linearize": (C.c_int, [C.c_int, C.POINTER(FdmRegisterClouds), _P, C.POINTER(FdmAlignSettings),
                                                C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), _P]),
     "fdm_register_last_stats": (C.c_int, [C.POINTER(FdmRegisterStats)]),
+    "fdm_voxel_map_create": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.c_float, C.c_double, C.c_int, C.POINTER(_P)]),
+    "fdm_voxel_map_destroy": (None, [_P]),
+    "fdm_voxel_map_get_info": (C.c_int, [_P, C.POINTER(FdmVoxelMapInfo)]),
+    "fdm_voxel_map_records": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    "fdm_cloud_register_vgicp": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, C.c_int, _P, C.POINTER(FdmAlignSettings),
+                                           C.POINTER(FdmRegistrationResult)]),
+    "fdm_cloud_register_vgicp_linearize": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, C.c_int, _P,
+                                                     C.POINTER(FdmAlignSettings), _P, _P, C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_uint64), _P]),
     "fdm_cloud_segment_ground": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.POINTER(FdmGroundSegConfig), C.c_int, _P, _P,
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fdm_cloud_segment_plane": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, _P, C.c_uint64, C.POINTER(FdmRansacConfig),

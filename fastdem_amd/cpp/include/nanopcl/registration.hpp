@@ -7,8 +7,9 @@
 // channels are looked at, as there.
 //
 // Not mirrored: IterativeSolver, the factors, linearizers and correspondence classes as types of their own (one
-// linearization is fdm_cloud_register_linearize), and alignVGICP — the voxel distribution map is a data structure this
-// library does not have.  Both overloads are declared deleted so that a call fails at compile time with their name.
+// linearization is fdm_cloud_register_linearize).  alignVGICP and the voxel distribution map are OPT-IN: they live in
+// nanopcl/registration/vgicp.hpp, which defines NANOPCL_VGICP and includes this header.  Without that macro both
+// overloads are declared deleted here, so that a call fails at compile time with their name.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -123,7 +124,9 @@ inline RegistrationResult empty_result(const Eigen::Isometry3d& initial_guess) {
   return detail::align(FDM_REGISTER_GICP, source, target, initial_guess, settings, "alignGICP");
 }
 
-// the reference's voxelized GICP (align.hpp:276-353): not provided — there is no voxel distribution map here
+#ifndef NANOPCL_VGICP
+#define NANOPCL_REGISTRATION_VGICP_DELETED
+// the reference's voxelized GICP (align.hpp:276-353): provided by nanopcl/registration/vgicp.hpp, not by this header alone
 class VoxelCorrespondence;
 RegistrationResult alignVGICP(const PointCloud& source, const VoxelCorrespondence& correspondence,
                               const Eigen::Isometry3d& initial_guess = Eigen::Isometry3d::Identity(),
@@ -131,6 +134,7 @@ RegistrationResult alignVGICP(const PointCloud& source, const VoxelCorrespondenc
 RegistrationResult alignVGICP(const PointCloud& source, const PointCloud& target, float voxel_resolution = 1.0f,
                               const Eigen::Isometry3d& initial_guess = Eigen::Isometry3d::Identity(),
                               const AlignSettings& settings = {}) = delete;
+#endif
 
 }  // namespace registration
 }  // namespace nanopcl

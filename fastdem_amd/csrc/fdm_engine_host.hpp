@@ -48,6 +48,7 @@
 #include "fdm_normals.hpp"
 #include "fdm_register.hpp"
 #include "fdm_register_host.hpp"
+#include "fdm_vgicp.hpp"
 #include "fdm_segment.hpp"
 #include "fdm_segment_host.hpp"
 #include "fdm_cluster.hpp"

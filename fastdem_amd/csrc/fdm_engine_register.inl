@@ -3,6 +3,8 @@
 // fdm_default_align_settings.  Part of fdm_engine_post.hip, behind fdm_engine_normals.inl; the target's search grid is
 // fdm_engine_dem.inl's (knn_grid_build).  Engine-free like the other cloud calls: the call picks its device, works on the
 // null stream in scratch of its own and frees it on return.  Synchronous: the host reads 29 doubles per iteration.
+// RegCall's steps (the source's staging and finite check, its regularisation, the partials) and reg_solve also serve
+// voxelized GICP, whose target is a prebuilt voxel map (fdm_engine_vgicp.inl).
 
 namespace {
 thread_local fdm_register_stats g_register_stats = {};
@@ -30,6 +32,7 @@ struct RegCall {
   const float* src[3] = {};
   const float* tgt[6] = {};
   RegTarget Q{};
+  VgTable V{};  // kRegVGICP: the map's table and records (fdm_engine_vgicp.inl)
   Events E;
   bool clock = false;
   int32_t* d_corr = nullptr;
@@ -49,21 +52,18 @@ struct RegCall {
   }
   // both clouds non-empty and checked: staging, the refusal of a coordinate that is not finite, the target's grid, the
   // regularised covariances
-  int prepare(int method_, const fdm_register_clouds& c, const fdm_align_settings& st) {
+  // the source on the device, and the refusal of a coordinate that is not finite: it has no grid of its own, its
+  // coordinates are looked at by the bounds kernel alone
+  int stage_source(int method_, uint64_t n, const float* sx, const float* sy, const float* sz, bool dev,
+                   const fdm_align_settings& st) {
     method = method_;
     set = st;
-    n_src = unsigned(c.n_source);
-    n_tgt = unsigned(c.n_target);
-    const bool dev = c.on_device != 0;
+    n_src = unsigned(n);
     clock = cloud_profile_on();
     if (clock)
       if (int rc = E.init(6)) return rc;
-    const void* const h_src[3] = {c.sx, c.sy, c.sz};
-    if (int rc = stage_cloud(s, c.n_source, 3, h_src, dev, b_src, src)) return rc;
-    const void* const ht[6] = {c.tx, c.ty, c.tz, method == kRegPlane ? c.tnx : nullptr, method == kRegPlane ? c.tny : nullptr,
-                               method == kRegPlane ? c.tnz : nullptr};
-    if (int rc = stage_cloud(s, c.n_target, 6, ht, dev, b_tgt, tgt)) return rc;
-    // the source has no grid of its own: its coordinates are looked at by the bounds kernel alone
+    const void* const h_src[3] = {sx, sy, sz};
+    if (int rc = stage_cloud(s, n, 3, h_src, dev, b_src, src)) return rc;
     if (int rc = b_stat.alloc(sizeof(KnnStat))) return rc;
     hipLaunchKernelGGL(k_knn_init, dim3(1), dim3(64), 0, s, b_stat.as<KnnStat>());
     hipLaunchKernelGGL(k_knn_bounds, dim3(std::min((n_src + 255u) / 256u, 2048u)), dim3(256), 0, s, n_src, src[0], src[1],
@@ -73,6 +73,31 @@ struct RegCall {
     HIPCK(hipMemcpyAsync(&hs, b_stat.p, sizeof(hs), hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     if (hs.nonfinite) return fail(FDM_ERR_INVALID, "the source cloud has a coordinate that is not finite");
+    return FDM_OK;
+  }
+  // the source's regularised covariances
+  int regularize_source(const float* s_cov9, bool dev) {
+    const float* d_sc = nullptr;
+    if (int rc = stage_cov(s_cov9, n_src, dev, b_scov, &d_sc)) return rc;
+    if (int rc = b_screg.alloc(size_t(n_src) * 6 * sizeof(double))) return rc;
+    hipLaunchKernelGGL(k_reg_regularize, dim3((n_src + 255u) / 256u), dim3(256), 0, s, n_src, d_sc, set.covariance_epsilon,
+                       b_screg.as<double>());
+    HIPCK(hipGetLastError());
+    return FDM_OK;
+  }
+  // one partial per block of the linearization, and their sum
+  int alloc_sums() {
+    const unsigned blocks = (n_src + unsigned(kRegThreads) - 1u) / unsigned(kRegThreads);
+    if (int rc = b_partial.alloc(size_t(blocks) * kRegStride * sizeof(double))) return rc;
+    return b_out.alloc(kRegStride * sizeof(double));
+  }
+  int prepare(int method_, const fdm_register_clouds& c, const fdm_align_settings& st) {
+    const bool dev = c.on_device != 0;
+    if (int rc = stage_source(method_, c.n_source, c.sx, c.sy, c.sz, dev, st)) return rc;
+    n_tgt = unsigned(c.n_target);
+    const void* const ht[6] = {c.tx, c.ty, c.tz, method == kRegPlane ? c.tnx : nullptr, method == kRegPlane ? c.tny : nullptr,
+                               method == kRegPlane ? c.tnz : nullptr};
+    if (int rc = stage_cloud(s, c.n_target, 6, ht, dev, b_tgt, tgt)) return rc;
     if (int rc = mark(0)) return rc;
     if (int rc = knn_grid_build(s, n_tgt, tgt[0], tgt[1], tgt[2], 1u, I)) return rc;  // (refuses a target that is not finite)
     if (int rc = mark(1)) return rc;
@@ -93,23 +118,17 @@ struct RegCall {
     g_register_stats.ring_limit = Q.rings;
     if (int rc = mark(2)) return rc;
     if (method == kRegGICP) {
-      const float *d_sc = nullptr, *d_tc = nullptr;
-      if (int rc = stage_cov(c.s_cov9, c.n_source, dev, b_scov, &d_sc)) return rc;
+      const float* d_tc = nullptr;
+      if (int rc = regularize_source(c.s_cov9, dev)) return rc;
       if (int rc = stage_cov(c.t_cov9, c.n_target, dev, b_tcov, &d_tc)) return rc;
-      if (int rc = b_screg.alloc(size_t(n_src) * 6 * sizeof(double))) return rc;
       if (int rc = b_tcreg.alloc(size_t(n_tgt) * 6 * sizeof(double))) return rc;
-      hipLaunchKernelGGL(k_reg_regularize, dim3((n_src + 255u) / 256u), dim3(256), 0, s, n_src, d_sc, set.covariance_epsilon,
-                         b_screg.as<double>());
       hipLaunchKernelGGL(k_reg_regularize, dim3((n_tgt + 255u) / 256u), dim3(256), 0, s, n_tgt, d_tc, set.covariance_epsilon,
                          b_tcreg.as<double>());
       HIPCK(hipGetLastError());
       Q.creg = b_tcreg.as<double>();
     }
     if (int rc = mark(3)) return rc;
-    const unsigned blocks = (n_src + unsigned(kRegThreads) - 1u) / unsigned(kRegThreads);
-    if (int rc = b_partial.alloc(size_t(blocks) * kRegStride * sizeof(double))) return rc;
-    if (int rc = b_out.alloc(kRegStride * sizeof(double))) return rc;
-    return FDM_OK;
+    return alloc_sums();
   }
   // one linearization at T: the model, and the correspondences where d_corr is set
   int linearize(const reg::Rigid& T, reg::Model& M) {
@@ -132,6 +151,10 @@ struct RegCall {
         hipLaunchKernelGGL((k_reg_linearize<kRegPlane>), dim3(blocks), dim3(kRegThreads), 0, s, n_src, src[0], src[1], src[2],
                            static_cast<const double*>(nullptr), t, Q, kern, width, part, d_corr);
         break;
+      case kRegVGICP:
+        hipLaunchKernelGGL(k_vg_linearize, dim3(blocks), dim3(kRegThreads), 0, s, n_src, src[0], src[1], src[2],
+                           static_cast<const double*>(b_screg.as<double>()), t, V, kern, width, part, d_corr);
+        break;
       default:
         hipLaunchKernelGGL((k_reg_linearize<kRegGICP>), dim3(blocks), dim3(kRegThreads), 0, s, n_src, src[0], src[1], src[2],
                            static_cast<const double*>(b_screg.as<double>()), t, Q, kern, width, part, d_corr);
@@ -153,7 +176,7 @@ struct RegCall {
   }
   void finish() {
     if (!clock) return;
-    g_register_stats.ms[0] = E.ms(0, 1);
+    if (method != kRegVGICP) g_register_stats.ms[0] = E.ms(0, 1);  // (a voxel map was built elsewhere)
     g_register_stats.ms[1] = E.ms(2, 3);
   }
 };
@@ -185,6 +208,30 @@ fdm_align_settings reg_settings(const fdm_align_settings* st) {
   fdm_align_settings d;
   fdm_default_align_settings(&d);
   return st ? *st : d;
+}
+// the host loop over call.linearize, from `guess`
+int reg_solve(RegCall& call, uint64_t n_source, const reg::Rigid& guess, const fdm_align_settings& st, reg::Result* R) {
+  reg::Criteria crit;
+  crit.max_iterations = st.max_iterations;
+  crit.min_correspondences = st.min_correspondences;
+  crit.translation_eps = st.translation_eps;
+  crit.rotation_eps = st.rotation_eps;
+  crit.relative_error_eps = st.relative_error_eps;
+  int rc = FDM_OK;
+  *R = reg::solve(n_source, guess, crit, [&](const reg::Rigid& T, reg::Model& M) { return call.linearize(T, M); }, &rc);
+  if (rc) return rc;
+  call.finish();
+  return FDM_OK;
+}
+void reg_write_result(const reg::Result& R, fdm_registration_result* out) {
+  *out = fdm_registration_result{};
+  reg::rigid_to_colmajor(R.T, out->transform);
+  out->fitness = R.fitness;
+  out->rmse = R.rmse;
+  out->iterations = R.iterations;
+  out->converged = R.converged ? 1 : 0;
+  out->has_covariance = R.has_covariance ? 1 : 0;
+  if (R.has_covariance) std::memcpy(out->covariance, R.covariance, sizeof(out->covariance));
 }
 }  // namespace
 
@@ -224,25 +271,9 @@ int fdm_cloud_register(int method, const fdm_register_clouds* clouds, const doub
     if (int rc = pick_device(device)) return rc;
     RegCall call;
     if (int rc = call.prepare(method, *clouds, st)) return rc;
-    reg::Criteria crit;
-    crit.max_iterations = st.max_iterations;
-    crit.min_correspondences = st.min_correspondences;
-    crit.translation_eps = st.translation_eps;
-    crit.rotation_eps = st.rotation_eps;
-    crit.relative_error_eps = st.relative_error_eps;
-    int rc = FDM_OK;
-    R = reg::solve(clouds->n_source, guess, crit, [&](const reg::Rigid& T, reg::Model& M) { return call.linearize(T, M); }, &rc);
-    if (rc) return rc;
-    call.finish();
+    if (int rc = reg_solve(call, clouds->n_source, guess, st, &R)) return rc;
   }
-  *out = fdm_registration_result{};
-  reg::rigid_to_colmajor(R.T, out->transform);
-  out->fitness = R.fitness;
-  out->rmse = R.rmse;
-  out->iterations = R.iterations;
-  out->converged = R.converged ? 1 : 0;
-  out->has_covariance = R.has_covariance ? 1 : 0;
-  if (R.has_covariance) std::memcpy(out->covariance, R.covariance, sizeof(out->covariance));
+  reg_write_result(R, out);
   return FDM_OK;
 }
 

@@ -16,6 +16,8 @@
 //   k_reg_reduce       the partials in block order: eight contiguous runs of blocks summed side by side, then the eight
 //                      in order
 // The sums have a fixed shape for a given n: no floating-point atomics, two calls return the same bits.
+// The pieces a sibling kernel needs are device functions of their own — reg_regularize_one, reg_transform, the factors,
+// reg_block_sum — and voxelized GICP (fdm_vgicp.hpp: k_vg_linearize, the voxel map's C_reg) is built from them.
 //
 // The search is fdm_knn.hpp's walk over the TARGET's column grid, built once per call (the target does not move), with a
 // top-1 that keeps (d2 bits, target input index) as one 64-bit key — the lower index wins among equal distances, this
@@ -118,12 +120,9 @@ __device__ __forceinline__ void reg_jacobi3(double A[3][3], double V[3][3]) {
 // V diag(eps, 1, 1) VT = I - (1 - eps) v0 v0T.  Among equal smallest eigenvalues the lowest index is taken, which gives
 // diag(eps, 1, 1) for the identity (an invalid point of fdm_cloud_estimate_normals); any other coincidence is
 // unspecified (the reference's depends on Eigen's iteration).
-inline __global__ __launch_bounds__(256) void k_reg_regularize(unsigned n, const float* __restrict__ cov9, double eps,
-                                                               double* __restrict__ creg) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const float* c = cov9 + size_t(i) * 9;  // column-major: (r, c) at c * 3 + r; the lower triangle is r >= c
-  double* o = creg + size_t(i) * 6;
+// (one covariance: c = 9 floats column-major, (r, c) at c * 3 + r, the lower triangle is r >= c; o = six doubles.  Also
+// the voxel distribution map's, fdm_vgicp.hpp)
+__device__ __forceinline__ void reg_regularize_one(const float* c, double eps, double* o) {
   const float c00 = c[0];
   if (!(fabsf(c00) <= kFltMax)) {
     o[0] = eps; o[1] = 0.0; o[2] = 0.0; o[3] = eps; o[4] = 0.0; o[5] = eps;
@@ -150,6 +149,12 @@ inline __global__ __launch_bounds__(256) void k_reg_regularize(unsigned n, const
   o[3] = 1.0 - f * (v[1] * v[1]);
   o[4] = 0.0 - f * (v[1] * v[2]);
   o[5] = 1.0 - f * (v[2] * v[2]);
+}
+inline __global__ __launch_bounds__(256) void k_reg_regularize(unsigned n, const float* __restrict__ cov9, double eps,
+                                                               double* __restrict__ creg) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  reg_regularize_one(cov9 + size_t(i) * 9, eps, creg + size_t(i) * 6);
 }
 
 // ---- the factors: each adds one correspondence's 28 numbers to S[0 .. 27] (H row-major upper triangle, b, error) ----
@@ -232,6 +237,39 @@ __device__ __forceinline__ void reg_factor_gicp(double tx, double ty, double tz,
   S[27] = 0.5 * rw * mahal_sq;
 }
 
+// p = T * (x, y, z): ((r0 x + r1 y) + r2 z) + t per row in double, no contraction (ASSUMED order: DESIGN.md §6)
+__device__ __forceinline__ void reg_transform(const RegTransform& T, double x, double y, double z, double& px, double& py,
+                                              double& pz) {
+  px = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.r[0], x), __dmul_rn(T.r[1], y)), __dmul_rn(T.r[2], z)), T.t[0]);
+  py = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.r[3], x), __dmul_rn(T.r[4], y)), __dmul_rn(T.r[5], z)), T.t[1]);
+  pz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.r[6], x), __dmul_rn(T.r[7], y)), __dmul_rn(T.r[8], z)), T.t[2]);
+}
+
+// The block's sum of every lane's S[0 .. 28] into partial[blockIdx.x]: the wavefront's by a butterfly, the same tree in
+// every lane; then LDS across the four wavefronts in wavefront order.  Every thread of the block calls it.
+__device__ __forceinline__ void reg_block_sum(double* S, double* __restrict__ partial) {
+  __shared__ double s_sum[kRegThreads / 64][kRegStride];
+#pragma unroll
+  for (int a = 0; a < kRegSums; ++a) {
+    double v = S[a];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    S[a] = v;
+  }
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (lane == 0u) {
+#pragma unroll
+    for (int a = 0; a < kRegSums; ++a) s_sum[wave][a] = S[a];
+  }
+  __syncthreads();
+  if (threadIdx.x < unsigned(kRegSums)) {
+    double v = s_sum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kRegThreads / 64; ++w) v += s_sum[w][threadIdx.x];
+    partial[size_t(blockIdx.x) * kRegStride + threadIdx.x] = v;
+  }
+}
+
 // corr (nullable): corr[i] = the target index source point i corresponds to, -1 for none
 template <int FACTOR>
 __global__ __launch_bounds__(kRegThreads) void k_reg_linearize(unsigned n, const float* __restrict__ sx,
@@ -240,7 +278,6 @@ __global__ __launch_bounds__(kRegThreads) void k_reg_linearize(unsigned n, const
                                                                const double* __restrict__ s_creg, const RegTransform T,
                                                                const RegTarget Q, int kernel, double width,
                                                                double* __restrict__ partial, int32_t* __restrict__ corr) {
-  __shared__ double s_sum[kRegThreads / 64][kRegStride];
   const unsigned i = blockIdx.x * unsigned(kRegThreads) + threadIdx.x;
   double S[kRegSums];
 #pragma unroll
@@ -248,10 +285,8 @@ __global__ __launch_bounds__(kRegThreads) void k_reg_linearize(unsigned n, const
   if (i < n) {
     // p = T * source[i]: ((r0 x + r1 y) + r2 z) + t per row in double (ASSUMED order: DESIGN.md §6), rounded once to
     // float for the search; the factor takes the double
-    const double x = double(sx[i]), y = double(sy[i]), z = double(sz[i]);
-    const double px = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.r[0], x), __dmul_rn(T.r[1], y)), __dmul_rn(T.r[2], z)), T.t[0]);
-    const double py = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.r[3], x), __dmul_rn(T.r[4], y)), __dmul_rn(T.r[5], z)), T.t[1]);
-    const double pz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T.r[6], x), __dmul_rn(T.r[7], y)), __dmul_rn(T.r[8], z)), T.t[2]);
+    double px, py, pz;
+    reg_transform(T, double(sx[i]), double(sy[i]), double(sz[i]), px, py, pz);
     const float4 q = make_float4(float(px), float(py), float(pz), 0.0f);
     RegTop top;
     top.init();
@@ -279,26 +314,7 @@ __global__ __launch_bounds__(kRegThreads) void k_reg_linearize(unsigned n, const
       corr[i] = -1;
     }
   }
-  // the wavefront's sums: a butterfly, the same tree in every lane
-#pragma unroll
-  for (int a = 0; a < kRegSums; ++a) {
-    double v = S[a];
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    S[a] = v;
-  }
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (lane == 0u) {
-#pragma unroll
-    for (int a = 0; a < kRegSums; ++a) s_sum[wave][a] = S[a];
-  }
-  __syncthreads();
-  if (threadIdx.x < unsigned(kRegSums)) {
-    double v = s_sum[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kRegThreads / 64; ++w) v += s_sum[w][threadIdx.x];
-    partial[size_t(blockIdx.x) * kRegStride + threadIdx.x] = v;
-  }
+  reg_block_sum(S, partial);
 }
 
 // out[0 .. 28] = the nb partials summed: slice s takes blocks [s * per, min(nb, (s + 1) * per)) in order, the slices

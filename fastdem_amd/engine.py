@@ -1122,6 +1122,153 @@ def register_last_stats():
             "ms": tuple(float(v) for v in st.ms)}
 
 
+# ---- voxelized GICP (fdm_voxel_map_* / fdm_cloud_register_vgicp: include/fdm_engine.h) ----
+class VoxelMap:
+    """nanopcl::registration::VoxelDistributionMap on the device: per-voxel means and covariances of a target cloud, built
+    once and registered against any number of times (align_vgicp, linearize_vgicp).  x, y, z: NumPy arrays, or torch
+    device tensors (the map then lives on their device).  Owns device memory until close() (or the end of a `with`)."""
+
+    def __init__(self, x, y, z, resolution=1.0, covariance_epsilon=1e-3, device=0):
+        self._h = None
+        n, p, on_device, dev, keep, _ = _seg_cloud(x, y, z, device)
+        h = C.c_void_p()
+        _ck(capi.load().fdm_voxel_map_create(n, p[0], p[1], p[2], on_device, float(resolution),
+                                             float(covariance_epsilon), int(dev), C.byref(h)))
+        del keep
+        self._h = h
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            capi.load().fdm_voxel_map_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _handle(self):
+        if not self._h:
+            raise EngineError("the voxel map is closed")
+        return self._h
+
+    def info(self):
+        """dict: resolution, inv_resolution, covariance_epsilon, device, n_points, n_skipped (not finite), num_voxels,
+        n_sparse (fewer than 3 points), max_count, table_slots, max_probe, ms (keys + sort, reduce + regularise, hash:
+        zeros unless fdm_cloud_debug_profile was on)."""
+        st = capi.FdmVoxelMapInfo()
+        _ck(capi.load().fdm_voxel_map_get_info(self._handle(), C.byref(st)))
+        out = {k: getattr(st, k) for k in ("resolution", "inv_resolution", "covariance_epsilon", "device", "n_points",
+                                           "n_skipped", "num_voxels", "n_sparse", "max_count", "table_slots",
+                                           "max_probe")}
+        out["ms"] = tuple(float(v) for v in st.ms)
+        return out
+
+    def __len__(self):
+        return int(self.info()["num_voxels"])
+
+    def records(self):
+        """dict of NumPy arrays in ascending key order: key uint64[m], count uint32[m], mean float32[m, 3], cov
+        float32[m, 3, 3] and creg float64[m, 3, 3] (the regularised covariance), both indexed [row][column]."""
+        m = len(self)
+        key, count = np.empty(m, dtype=np.uint64), np.empty(m, dtype=np.uint32)
+        mean, cov9 = np.empty((m, 3), dtype=np.float32), np.empty((m, 9), dtype=np.float32)
+        c6 = np.empty((m, 6), dtype=np.float64)
+        _ck(capi.load().fdm_voxel_map_records(self._handle(), 0, _ptr(key), _ptr(mean), _ptr(cov9), _ptr(c6), _ptr(count)))
+        creg = c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(m, 3, 3)
+        return {"key": key, "count": count, "mean": mean,
+                "cov": np.ascontiguousarray(cov9.reshape(m, 3, 3).transpose(0, 2, 1)), "creg": np.ascontiguousarray(creg)}
+
+
+def _vgicp_source(sx, sy, sz, source_cov, device):
+    """(n, pointers of x y z cov9, on_device, the arrays kept alive) of a NumPy or torch device source cloud."""
+    n, p, on_device, _, keep, torch = _seg_cloud(sx, sy, sz, device)
+    cov = None
+    if source_cov is not None:
+        if torch is not None:
+            if not _is_torch(source_cov) or source_cov.device != keep[0].device:
+                raise TypeError("registration takes float32 tensors that all live on the source's device "
+                                "(or NumPy arrays throughout)")
+            cov = source_cov.float().reshape(n, 3, 3).transpose(1, 2).contiguous()
+        else:
+            cov = np.ascontiguousarray(_f32(source_cov).reshape(n, 3, 3).transpose(0, 2, 1))    # -> column-major
+    return n, p + [(_dptr if on_device else _ptr)(cov)], on_device, keep + (cov,)
+
+
+def _vgicp_map(voxel_map, target, voxel_resolution, st, device):
+    """(the map to use, whether it is this call's to close)."""
+    if (voxel_map is None) == (target is None):
+        raise TypeError("give exactly one of voxel_map and target")
+    if voxel_map is not None:
+        return voxel_map, False
+    tx, ty, tz = target
+    return VoxelMap(tx, ty, tz, voxel_resolution, st.covariance_epsilon, device), True
+
+
+def align_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_resolution=1.0, initial_guess=None, device=0,
+                **settings):
+    """nanopcl::registration::alignVGICP on the device.  Give a prebuilt VoxelMap (the fast path: one lookup per point
+    and iteration), or target=(tx, ty, tz), which builds a map of voxel_resolution with settings' covariance_epsilon for
+    this call alone.  source_cov: (n, 3, 3) indexed [row][column].  max_correspondence_dist is not used.  Otherwise as
+    align_icp."""
+    st = settings.pop("settings", None) or align_settings(**settings)
+    vmap, mine = _vgicp_map(voxel_map, target, voxel_resolution, st, device)
+    try:
+        n, p, on_device, keep = _vgicp_source(sx, sy, sz, source_cov, device)
+        res = capi.FdmRegistrationResult()
+        _ck(capi.load().fdm_cloud_register_vgicp(vmap._handle(), n, p[0], p[1], p[2], p[3], on_device,
+                                                 _guess16(initial_guess), C.byref(st), C.byref(res)))
+        del keep
+    finally:
+        if mine:
+            vmap.close()
+    T = np.array(res.transform, dtype=np.float64).reshape(4, 4).T.copy()
+    cov = np.array(res.covariance, dtype=np.float64).reshape(6, 6) if res.has_covariance else None
+    return RegistrationResult(T, float(res.fitness), float(res.rmse), int(res.iterations), bool(res.converged), cov)
+
+
+def linearize_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_resolution=1.0, transform=None, device=0,
+                    return_correspondences=False, **settings):
+    """One VGICP linearization at `transform`, shaped like linearize: H, H_upper, b, error, num_inliers, and with
+    return_correspondences "corr": every source point's voxel as its rank in ascending key order (-1 for none)."""
+    st = settings.pop("settings", None) or align_settings(**settings)
+    vmap, mine = _vgicp_map(voxel_map, target, voxel_resolution, st, device)
+    try:
+        n, p, on_device, keep = _vgicp_source(sx, sy, sz, source_cov, device)
+        H, b = (C.c_double * 21)(), (C.c_double * 6)()
+        err, cnt = C.c_double(0.0), C.c_uint64(0)
+        corr = None
+        if return_correspondences:
+            if on_device:
+                import torch
+                corr = torch.empty(n, dtype=torch.int32, device=keep[0].device)
+            else:
+                corr = np.empty(n, dtype=np.int32)
+        _ck(capi.load().fdm_cloud_register_vgicp_linearize(vmap._handle(), n, p[0], p[1], p[2], p[3], on_device,
+                                                           _guess16(transform), C.byref(st), H, b, C.byref(err),
+                                                           C.byref(cnt), (_dptr if on_device else _ptr)(corr)))
+        del keep
+    finally:
+        if mine:
+            vmap.close()
+    Hu = np.array(H, dtype=np.float64)
+    full = np.zeros((6, 6))
+    full[np.triu_indices(6)] = Hu
+    full = full + np.triu(full, 1).T
+    out = {"H": full, "H_upper": Hu, "b": np.array(b, dtype=np.float64), "error": float(err.value),
+           "num_inliers": int(cnt.value)}
+    if return_correspondences:
+        out["corr"] = corr
+    return out
+
+
 # ---- cloud segmentation (fdm_cloud_segment_ground / _plane / _planes: include/fdm_engine.h) ----
 def _seg_cloud(x, y, z, device):
     """(n, pointers of x y z, on_device, device, the arrays kept alive, torch module or None)."""

@@ -651,7 +651,8 @@ int fdm_normals_last_stats(fdm_normal_stats* out);
  * kdtree_correspondence.hpp:57-120, core/lie.hpp:39-148) ----
  * Engine-free and synchronous, on `device`; host arrays (on_device 0) or device arrays.  The per-iteration work — the
  * transform, the nearest target point within the radius, the factor and the sum of the factors — runs on the device; the
- * 6 x 6 algebra and the loop run on the host in double.  alignVGICP (the voxel distribution map) is not provided.
+ * 6 x 6 algebra and the loop run on the host in double.  alignVGICP registers against a voxel distribution map built once:
+ * fdm_voxel_map_create and fdm_cloud_register_vgicp, below.
  * LOOP.  T = initial_guess (16 doubles, column-major; NULL = the identity), prev_error = DBL_MAX, lambda = 1e-3 and never
  * adapted.  Per iteration: linearize every source point at T; fewer inliers than min_correspondences: failed (T, fitness
  * 0, rmse +inf, iterations = iter, not converged, no covariance); delta = (H + lambda I)^-1 (-b); new_T = se3Exp(delta) T;
@@ -738,6 +739,78 @@ typedef struct fdm_register_stats {  /* the calling thread's last fdm_cloud_regi
   float ms[3];
 } fdm_register_stats;
 int fdm_register_last_stats(fdm_register_stats* out);
+
+/* ---- voxelized GICP: nanopcl::registration::VoxelDistributionMap, VoxelCorrespondence and alignVGICP (registration/
+ * voxel_distribution_map.hpp:143-323, correspondence/voxel_correspondence.hpp:35-78, factors/vgicp_factor.hpp,
+ * align.hpp:276-353, core/voxel.hpp:28-42) ----
+ * The target is turned ONCE into a map of per-voxel means and covariances; every later scan is registered against it with
+ * one table lookup per source point and iteration, where GICP searches for a nearest neighbour.  A map owns device memory
+ * on one device, outlives the call that made it and may serve any number of register calls; it is not changed by them.
+ * BUILD.  inv = 1.0f / resolution.  A target point with a non-finite x, y or z is SKIPPED (counted in n_skipped), as in
+ * the reference; every other point gets the key fdm_cloud_voxel_grid documents (voxel::pack: the float product, floor, the
+ * x86 int conversion, the clamp to [-2^20, 2^20 - 1], [z:21][y:21][x:21]).  Per key, in INPUT ORDER and in double: sum of
+ * p and sum_outer of p_a * p_b (exact products of two floats), the first point of a voxel ASSIGNED and the others added —
+ * a voxel whose points all have x = -0.0f keeps a -0.0 sum — sequentially, without reassociation or atomics; count is a
+ * uint32.  mean = sum / double(count), stored as float.  count >= 3: cov(a, b) = sum_outer(a, b) / double(count) - mean_a *
+ * mean_b in double without contraction, stored as float.  count 1 or 2: cov = float(covariance_epsilon) * I.
+ * VOXEL ORDER (this project's definition).  Records, and the indices a correspondence names, are in ASCENDING KEY order;
+ * the reference's table order is not observable through its API.
+ * REGULARISED COVARIANCE.  C_reg of a voxel of count >= 3 is I - (1 - eps) v0 v0T computed in DOUBLE from the stored float
+ * covariance (lower triangle), v0 the unit eigenvector of its smallest eigenvalue, and kept in double: the arithmetic GICP
+ * applies to a point's covariance, above.  C_reg of a sparser voxel is exactly I.  DEVIATION: the reference reaches the
+ * same matrix through a float eigen-solver and float products and casts the result to double; the two differ at float
+ * rounding.  Where the two smallest eigenvalues of a voxel's covariance coincide (three collinear points, repeated
+ * points) v0 is unspecified there and here.
+ * LOOKUP.  The voxel of a point is the record of its key; a voxel that exists is always valid (count >= 1).  The table is
+ * open addressing over the distinct keys, a power of two of at least 2 * num_voxels slots, the first slot a mix of all 63
+ * key bits; a lookup probes at most max_probe slots, the longest sequence the build took.
+ * ALIGN.  As fdm_cloud_register with GICP's factor, loop, convergence, result and covariance rule, except: the
+ * correspondence of source point i is the voxel of p = T * source[i] cast to float — no voxel, no correspondence;
+ * max_correspondence_dist is NOT USED; q = double(mean), C_tgt = the voxel's C_reg, C_src = R C_reg_src RT with the
+ * source's covariances regularised once with settings->covariance_epsilon.  An empty source or an empty map returns the
+ * early result (the guess, 0, +inf, 0, not converged) before anything else is looked at; a source without covariances is
+ * refused ("alignVGICP: source must have covariances").  The convenience overload alignVGICP(source, target,
+ * voxel_resolution, ...) is a map built with settings->covariance_epsilon, one register call and the map's destruction.
+ * FDM_ERR_INVALID: a resolution or 1.0f / resolution that is not finite and > 0; a negative or NaN covariance_epsilon; a
+ * source coordinate that is not finite (undefined in the reference: the cast to int); n_target > 2^32 - 4097 (the sorts'
+ * limit); n_source >= 2^31; device source arrays that live on another device than the map; an entry of the transform that
+ * is not finite; an unknown robust kernel; a null argument.  The thread's current device is put back before every call
+ * returns.  The build's scratch is freed before fdm_voxel_map_create returns: a map keeps its records and its table. */
+typedef struct fdm_voxel_map fdm_voxel_map;   /* opaque; owns device memory on one device */
+typedef struct fdm_voxel_map_info {
+  float resolution, inv_resolution;
+  double covariance_epsilon;
+  int32_t device, reserved;
+  uint64_t n_points, n_skipped;      /* points given; ... of which not finite */
+  uint64_t num_voxels, n_sparse;     /* distinct keys; ... of which with fewer than 3 points */
+  uint64_t table_slots;              /* 0 for an empty map */
+  uint32_t max_count, max_probe;     /* the fullest voxel's points; slots the longest insertion looked at */
+  /* device ms while fdm_cloud_debug_profile (fdm_engine_debug.h) was on at the build, zeros otherwise: keys and sort;
+   * run heads, reduction and regularisation; the table */
+  float ms[3];
+  float reserved2;
+} fdm_voxel_map_info;
+/* x, y, z: host arrays (on_device 0) or device arrays on `device`.  n == 0 or no finite point: an empty map. */
+int fdm_voxel_map_create(uint64_t n, const float* x, const float* y, const float* z, int on_device, float resolution,
+                         double covariance_epsilon, int device, fdm_voxel_map** out);
+void fdm_voxel_map_destroy(fdm_voxel_map* map);   /* NULL is fine */
+int fdm_voxel_map_get_info(const fdm_voxel_map* map, fdm_voxel_map_info* out);
+/* The records in ascending key order, num_voxels entries each, into host arrays (on_device 0) or device arrays on the
+ * map's device; any may be NULL.  mean3: 3 floats; cov9: 9 floats, column-major; creg6: xx, xy, xz, yy, yz, zz. */
+int fdm_voxel_map_records(const fdm_voxel_map* map, int on_device, uint64_t* keys, float* mean3, float* cov9,
+                          double* creg6, uint32_t* count);
+/* alignVGICP(source, correspondence, initial_guess, settings) on the map's device.  fdm_register_last_stats afterwards:
+ * n_target = num_voxels, grid_x = grid_y = ring_limit = 0, voxel = the resolution, ms[0] = 0 (the map was built
+ * elsewhere), ms[1] the source's regularisation, ms[2] the linearizations. */
+int fdm_cloud_register_vgicp(const fdm_voxel_map* map, uint64_t n_source, const float* sx, const float* sy,
+                             const float* sz, const float* s_cov9, int on_device, const double* initial_guess,
+                             const fdm_align_settings* settings, fdm_registration_result* out);
+/* One linearization at `transform` (NULL = the identity), as fdm_cloud_register_linearize; corr[i] = the rank in
+ * ascending key order of the voxel source point i corresponds to, -1 for none.  An empty source or map gives zeros. */
+int fdm_cloud_register_vgicp_linearize(const fdm_voxel_map* map, uint64_t n_source, const float* sx, const float* sy,
+                                       const float* sz, const float* s_cov9, int on_device, const double* transform,
+                                       const fdm_align_settings* settings, double H[21], double b[6], double* error,
+                                       uint64_t* num_inliers, int32_t* corr);
 
 /* ---- cloud segmentation: nanopcl::segmentation::segmentGround (segmentation/impl/ground_seg_impl.hpp:27-123) and
  * segmentPlane / segmentMultiplePlanes (RANSAC; segmentation/impl/ransac_plane_impl.hpp:29-405) ----

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device cost of cloud registration, one JSON line per cloud and method: fdm_cloud_register (ICP,
-point-to-plane ICP, GICP) on device-resident clouds of the three sizes of BASELINE.json — the VLP-16 scan, the RGB-D
+point-to-plane ICP, GICP) and fdm_cloud_register_vgicp on device-resident clouds of the three sizes of BASELINE.json — the VLP-16 scan, the RGB-D
 frame and the 128-beam scan of fastdem_amd.synth in the world frame — prepared on the device as a user would: voxelGrid
 at --voxel metres, then normals and covariances at k = 20.  The target is that cloud; the source is the same cloud moved
 by a known small transform (0.15 m, 0.02 rad) and rounded to float, registered from the identity.
@@ -17,6 +17,11 @@ search, factor and the two sum kernels — the linearizations' total divided by 
 whole synchronous call: allocations, events, the host's 29-double read-back and 6 x 6 algebra per iteration included).
 fdm_cloud_debug_profile switches the events on.  Not separated: search against factor inside the linearize kernel (one
 kernel; the ICP line, whose factor is a dozen operations, is the closest to the search alone).
+
+The vgicp lines register the same sources against a voxel distribution map of the target (--vgicp-voxel metres, built
+ONCE per cloud and reused by every repeat, as scan-to-map registration does): map_ms is the map's build on the device
+(keys + sort, reduce + regularise, hash: map_stage_ms), map_wall_ms the whole synchronous create call, grid_ms is 0,
+regularize_ms the source's covariances alone; the other fields as for the other methods.
 
   python scripts/register_bench.py [--repeat 7] [--voxel 0.2] [--out profiles/register/register_bench.jsonl]
 """
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=7)
     ap.add_argument("--voxel", type=float, default=0.2)
     ap.add_argument("--max-dist", type=float, default=1.0)
+    ap.add_argument("--vgicp-voxel", type=float, default=1.0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--clouds", default="vlp16,rgbd,lidar128")
     args = ap.parse_args()
@@ -81,6 +87,20 @@ def main():
                  ("icp", "shuffled"): lambda **kw: F.align_icp(*shuf, *tgt, max_correspondence_dist=md, **kw),
                  ("plane", "shuffled"): lambda **kw: F.align_plane_icp(*shuf, *tgt, t_normals, max_correspondence_dist=md, **kw),
                  ("gicp", "shuffled"): lambda **kw: F.align_gicp(*shuf, *tgt, shuf_cov, t_cov, max_correspondence_dist=md, **kw)}
+        # voxelized GICP: the map built once (timed over --repeat builds), then reused by every call
+        F.VoxelMap(*tgt, resolution=args.vgicp_voxel).close()          # warm-up
+        map_wall, map_ms = [], []
+        for _ in range(args.repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            probe = F.VoxelMap(*tgt, resolution=args.vgicp_voxel)
+            map_wall.append((time.perf_counter() - t0) * 1e3)
+            map_ms.append(probe.info()["ms"])
+            probe.close()
+        vmap = F.VoxelMap(*tgt, resolution=args.vgicp_voxel)
+        info = vmap.info()
+        calls[("vgicp", "voxel")] = lambda **kw: F.align_vgicp(*src, s_cov, voxel_map=vmap, **kw)
+        calls[("vgicp", "shuffled")] = lambda **kw: F.align_vgicp(*shuf, shuf_cov, voxel_map=vmap, **kw)
         for (method, order), call in calls.items():
             call()                                                   # warm-up: code objects, the allocator
             ms, wall, wall1, first = [], [], [], []
@@ -109,8 +129,16 @@ def main():
                     "wall_ms": round(float(np.median(wall)), 3), "wall_one_iteration_ms": round(float(np.median(wall1)), 3),
                     "wall_per_iteration_ms": round(wall_iter, 4),
                     "wall_setup_ms": round(float(np.median(wall1)) - wall_iter, 3)}
+            if method == "vgicp":
+                stage = np.median(np.asarray(map_ms), axis=0)
+                line.update({"map_voxel": args.vgicp_voxel, "map_voxels": int(info["num_voxels"]),
+                             "map_sparse": int(info["n_sparse"]), "table_slots": int(info["table_slots"]),
+                             "max_probe": int(info["max_probe"]), "map_ms": round(float(stage.sum()), 4),
+                             "map_stage_ms": [round(float(v), 4) for v in stage],
+                             "map_wall_ms": round(float(np.median(map_wall)), 3)})
             lines.append(line)
             print(json.dumps(line), flush=True)
+        vmap.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
