@@ -56,11 +56,10 @@ struct RegistrationResult {
 };
 
 namespace detail {
-inline RegistrationResult align(int method, const PointCloud& source, const PointCloud& target,
-                                const Eigen::Isometry3d& initial_guess, const AlignSettings& settings, const char* who) {
+inline fdm_align_settings to_settings(const AlignSettings& settings) {
   fdm_align_settings st;
   fdm_default_align_settings(&st);
-  st.max_correspondence_dist = settings.max_correspondence_dist;
+  st.max_correspondence_dist = settings.max_correspondence_dist;  // (carried by every method; VGICP does not use it)
   st.max_iterations = settings.max_iterations;
   st.translation_eps = settings.translation_eps;
   st.rotation_eps = settings.rotation_eps;
@@ -69,6 +68,22 @@ inline RegistrationResult align(int method, const PointCloud& source, const Poin
   st.robust_kernel = int(settings.robust_kernel);
   st.robust_kernel_width = settings.robust_kernel_width;
   st.covariance_epsilon = settings.covariance_epsilon;
+  return st;
+}
+inline RegistrationResult to_result(const fdm_registration_result& r) {
+  RegistrationResult out{Eigen::Isometry3d::Identity(), r.fitness, r.rmse, size_t(r.iterations), r.converged != 0, std::nullopt};
+  std::memcpy(out.transform.data(), r.transform, sizeof(r.transform));  // both column-major 4 x 4
+  if (r.has_covariance) {
+    Matrix6d cov;
+    for (int row = 0; row < 6; ++row)
+      for (int col = 0; col < 6; ++col) cov(row, col) = r.covariance[row * 6 + col];
+    out.covariance = cov;
+  }
+  return out;
+}
+inline RegistrationResult align(int method, const PointCloud& source, const PointCloud& target,
+                                const Eigen::Isometry3d& initial_guess, const AlignSettings& settings, const char* who) {
+  const fdm_align_settings st = to_settings(settings);
   fdm_register_clouds c{};
   c.n_source = source.size();
   c.sx = source.xData(); c.sy = source.yData(); c.sz = source.zData();
@@ -82,15 +97,7 @@ inline RegistrationResult align(int method, const PointCloud& source, const Poin
   fdm_registration_result r;
   const int rc = fdm_cloud_register(method, &c, initial_guess.matrix().data(), &st, device, &r);
   if (rc < 0) throw std::runtime_error(std::string(who) + ": " + fdm_last_error());
-  RegistrationResult out{Eigen::Isometry3d::Identity(), r.fitness, r.rmse, size_t(r.iterations), r.converged != 0, std::nullopt};
-  std::memcpy(out.transform.data(), r.transform, sizeof(r.transform));  // both column-major 4 x 4
-  if (r.has_covariance) {
-    Matrix6d cov;
-    for (int row = 0; row < 6; ++row)
-      for (int col = 0; col < 6; ++col) cov(row, col) = r.covariance[row * 6 + col];
-    out.covariance = cov;
-  }
-  return out;
+  return to_result(r);
 }
 inline RegistrationResult empty_result(const Eigen::Isometry3d& initial_guess) {  // align.hpp:76-78
   return {initial_guess, 0.0, std::numeric_limits<double>::infinity(), 0, false, std::nullopt};

@@ -147,30 +147,12 @@ class VoxelCorrespondence {
   if (source.empty() || correspondence.empty()) return detail::empty_result(initial_guess);
   if (!source.hasCovariance())
     throw std::runtime_error("alignVGICP: source must have covariances. Call geometry::estimateCovariances() first.");
-  fdm_align_settings st;
-  fdm_default_align_settings(&st);
-  st.max_correspondence_dist = settings.max_correspondence_dist;  // (carried; VGICP does not use it)
-  st.max_iterations = settings.max_iterations;
-  st.translation_eps = settings.translation_eps;
-  st.rotation_eps = settings.rotation_eps;
-  st.relative_error_eps = settings.relative_error_eps;
-  st.min_correspondences = settings.min_correspondences;
-  st.robust_kernel = int(settings.robust_kernel);
-  st.robust_kernel_width = settings.robust_kernel_width;
-  st.covariance_epsilon = settings.covariance_epsilon;
+  const fdm_align_settings st = detail::to_settings(settings);
   fdm_registration_result r;
   const int rc = fdm_cloud_register_vgicp(correspondence.voxelMap().handle(), source.size(), source.xData(), source.yData(),
                                           source.zData(), source.covarianceData(), 0, initial_guess.matrix().data(), &st, &r);
   if (rc < 0) throw std::runtime_error(std::string("alignVGICP: ") + fdm_last_error());
-  RegistrationResult out{Eigen::Isometry3d::Identity(), r.fitness, r.rmse, size_t(r.iterations), r.converged != 0, std::nullopt};
-  std::memcpy(out.transform.data(), r.transform, sizeof(r.transform));  // both column-major 4 x 4
-  if (r.has_covariance) {
-    Matrix6d cov;
-    for (int row = 0; row < 6; ++row)
-      for (int col = 0; col < 6; ++col) cov(row, col) = r.covariance[row * 6 + col];
-    out.covariance = cov;
-  }
-  return out;
+  return detail::to_result(r);
 }
 
 // ... building the map for this call alone (align.hpp:337-353)

@@ -1,17 +1,11 @@
 // fdm_engine_vgicp.inl — host side of voxelized GICP (kernels: fdm_vgicp.hpp): the voxel distribution map as a handle that
-// outlives a call — fdm_voxel_map_create, _destroy, _get_info, _records — and registration against it,
-// fdm_cloud_register_vgicp and fdm_cloud_register_vgicp_linearize.  Part of fdm_engine_post.hip, behind
-// fdm_engine_register.inl (RegCall: the source's staging and finite check, the partials, reg_solve) and
-// fdm_engine_segment.inl (SortBufs64).  Engine-free like the other cloud calls: a call picks the device, works on the null
-// stream and is synchronous; the build's scratch is freed when create returns, the map keeps its records and its table.
-
-struct fdm_voxel_map {
-  fdm_voxel_map_info info{};
-  void* rec_mem = nullptr;    // the records, one block
-  void* table_mem = nullptr;  // slot keys, then slot ranks
-  VgRecords R{};
-  VgTable T{};
-};
+// outlives a call — fdm_voxel_map_create, _destroy, _get_info, _records (struct fdm_voxel_map itself is stated in
+// fdm_engine_register.inl, which reads it) — and the two entries that register against it, fdm_cloud_register_vgicp and
+// fdm_cloud_register_vgicp_linearize: they pack a RegProblem whose target is the map and call the one registration path
+// of fdm_engine_register.inl (reg_align, reg_linearize), as the cloud entries do.  Part of fdm_engine_post.hip, behind
+// fdm_engine_register.inl and fdm_engine_segment.inl (SortBufs64).  Engine-free like the other cloud calls: a call picks
+// the device, works on the null stream and is synchronous; the build's scratch is freed when create returns, the map
+// keeps its records and its table.
 
 namespace {
 void vg_free(fdm_voxel_map* m) {
@@ -153,45 +147,19 @@ int vg_build(fdm_voxel_map* m, uint64_t n, const float* x, const float* y, const
   return FDM_OK;
 }
 
-// what both register entries refuse before a device is touched; *empty: the reference's early return applies
-int vg_check(const fdm_voxel_map* map, uint64_t n, const float* sx, const float* sy, const float* sz, const float* s_cov9,
-             const double* T16, const fdm_align_settings& st, bool* empty) {
-  *empty = false;
-  if (!map) return fail(FDM_ERR_INVALID, "null argument");
-  if (st.robust_kernel < kRegNone || st.robust_kernel > kRegCauchy)
-    return fail(FDM_ERR_INVALID, "robust_kernel must be 0 (NONE), 1 (HUBER), 2 (TUKEY) or 3 (CAUCHY)");
-  if (T16)
-    for (int a = 0; a < 16; ++a)
-      if (!std::isfinite(T16[a])) return fail(FDM_ERR_INVALID, "the transform has an entry that is not finite");
-  if (int rc = check_cloud(n, sx, sy, sz)) return rc;
-  if (n == 0 || map->info.num_voxels == 0) {
-    *empty = true;
-    return FDM_OK;
-  }
-  if (!s_cov9) return fail(FDM_ERR_INVALID, "alignVGICP: source must have covariances");
-  return FDM_OK;
-}
-
-// the map's device is current: the source staged and checked, its covariances regularised, the map's table in place
-int vg_prepare(RegCall& call, const fdm_voxel_map* map, uint64_t n, const float* sx, const float* sy, const float* sz,
-               const float* s_cov9, bool dev, const fdm_align_settings& st) {
-  if (dev) {  // device arrays are the caller's: they must live where the map does
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, sx) != hipSuccess)
-      (void)hipGetLastError();  // (not a pointer the runtime knows: left to the copy that reads it)
-    else if (at.type == hipMemoryTypeDevice && at.device != map->info.device)
-      return fail(FDM_ERR_INVALID, "the voxel map was built on another device than the source lives on");
-  }
-  if (int rc = call.stage_source(kRegVGICP, n, sx, sy, sz, dev, st)) return rc;
-  call.n_tgt = unsigned(std::min<uint64_t>(map->info.num_voxels, 0xFFFFFFFFull));
-  call.V = map->T;
-  g_register_stats.n_source = n;
-  g_register_stats.n_target = map->info.num_voxels;
-  g_register_stats.voxel = map->info.resolution;
-  if (int rc = call.mark(2)) return rc;
-  if (int rc = call.regularize_source(s_cov9, dev)) return rc;
-  if (int rc = call.mark(3)) return rc;
-  return call.alloc_sums();
+// a registration against `map`, on its device
+RegProblem vg_problem(const fdm_voxel_map* map, uint64_t n, const float* sx, const float* sy, const float* sz,
+                      const float* s_cov9, int on_device) {
+  RegProblem P;
+  P.method = kRegVGICP;
+  P.voxels = true;
+  P.map = map;
+  P.device = map ? map->info.device : 0;
+  P.n = n;
+  P.x = sx; P.y = sy; P.z = sz;
+  P.cov9 = s_cov9;
+  P.on_device = on_device != 0;
+  return P;
 }
 }  // namespace
 
@@ -251,64 +219,15 @@ int fdm_voxel_map_records(const fdm_voxel_map* map, int on_device, uint64_t* key
 int fdm_cloud_register_vgicp(const fdm_voxel_map* map, uint64_t n_source, const float* sx, const float* sy,
                              const float* sz, const float* s_cov9, int on_device, const double* initial_guess,
                              const fdm_align_settings* settings, fdm_registration_result* out) {
-  g_register_stats = fdm_register_stats{};
-  if (!out) return fail(FDM_ERR_INVALID, "null argument");
-  const fdm_align_settings st = reg_settings(settings);
-  bool empty = false;
-  if (int rc = vg_check(map, n_source, sx, sy, sz, s_cov9, initial_guess, st, &empty)) return rc;
-  const reg::Rigid guess = initial_guess ? reg::rigid_from_colmajor(initial_guess) : reg::rigid_identity();
-  reg::Result R = reg::failed_result(guess, 0);  // the early return of an empty source or map (align.hpp:281-283)
-  if (!empty) {
-    const ScopedDevice restore;
-    if (int rc = pick_device(map->info.device)) return rc;
-    RegCall call;
-    if (int rc = vg_prepare(call, map, n_source, sx, sy, sz, s_cov9, on_device != 0, st)) return rc;
-    if (int rc = reg_solve(call, n_source, guess, st, &R)) return rc;
-  }
-  reg_write_result(R, out);
-  return FDM_OK;
+  return reg_align(vg_problem(map, n_source, sx, sy, sz, s_cov9, on_device), initial_guess, settings, out);
 }
 
 int fdm_cloud_register_vgicp_linearize(const fdm_voxel_map* map, uint64_t n_source, const float* sx, const float* sy,
                                        const float* sz, const float* s_cov9, int on_device, const double* transform,
                                        const fdm_align_settings* settings, double H[21], double b[6], double* error,
                                        uint64_t* num_inliers, int32_t* corr) {
-  g_register_stats = fdm_register_stats{};
-  if (!H || !b || !error || !num_inliers) return fail(FDM_ERR_INVALID, "null argument");
-  const fdm_align_settings st = reg_settings(settings);
-  bool empty = false;
-  if (int rc = vg_check(map, n_source, sx, sy, sz, s_cov9, transform, st, &empty)) return rc;
-  reg::Model M;
-  if (!empty) {
-    const ScopedDevice restore;
-    if (int rc = pick_device(map->info.device)) return rc;
-    RegCall call;
-    if (int rc = vg_prepare(call, map, n_source, sx, sy, sz, s_cov9, on_device != 0, st)) return rc;
-    const bool host = on_device == 0;
-    if (corr) {
-      call.d_corr = corr;
-      if (host) {
-        if (int rc = call.b_corr.alloc(size_t(n_source) * sizeof(int32_t))) return rc;
-        call.d_corr = call.b_corr.as<int32_t>();
-      }
-    }
-    if (int rc = call.linearize(transform ? reg::rigid_from_colmajor(transform) : reg::rigid_identity(), M)) return rc;
-    if (corr && host) HIPCK(hipMemcpy(corr, call.d_corr, size_t(n_source) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    call.finish();
-  } else if (corr && n_source) {  // no voxel: nobody corresponds
-    if (on_device) {
-      const ScopedDevice restore;
-      if (int rc = pick_device(map->info.device)) return rc;
-      HIPCK(hipMemset(corr, 0xFF, size_t(n_source) * sizeof(int32_t)));
-    } else {
-      std::memset(corr, 0xFF, size_t(n_source) * sizeof(int32_t));
-    }
-  }
-  std::memcpy(H, M.H, sizeof(M.H));
-  std::memcpy(b, M.b, sizeof(M.b));
-  *error = M.error;
-  *num_inliers = M.num_inliers;
-  return FDM_OK;
+  return reg_linearize(vg_problem(map, n_source, sx, sy, sz, s_cov9, on_device), transform, settings, H, b, error,
+                       num_inliers, corr);
 }
 
 }  // extern "C"

@@ -34,7 +34,7 @@ constexpr int kRegThreads = 256;
 constexpr int kRegSums = 29;         // 21 H, 6 b, the error, the inlier count (as a double: exact below 2^53)
 constexpr int kRegStride = 32;       // doubles per partial
 constexpr int kRegSlices = 8;        // k_reg_reduce: runs of blocks summed side by side
-enum : int { kRegICP = 0, kRegPlane = 1, kRegGICP = 2 };
+enum : int { kRegICP = 0, kRegPlane = 1, kRegGICP = 2, kRegVGICP = 3 };  // (the fourth: fdm_vgicp.hpp, no public number)
 enum : int { kRegNone = 0, kRegHuber = 1, kRegTukey = 2, kRegCauchy = 3 };
 
 struct RegTransform {  // rotation row-major, translation

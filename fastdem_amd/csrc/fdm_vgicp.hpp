@@ -36,7 +36,6 @@
 
 namespace fdm {
 
-constexpr int kRegVGICP = 3;                    // the fourth method, behind kRegICP / kRegPlane / kRegGICP
 constexpr unsigned long long kVgEmpty = ~0ull;  // no valid key has bit 63 set
 constexpr unsigned kVgBatch = 4u;               // entries a lane loads ahead of its chains
 

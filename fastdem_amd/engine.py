@@ -1005,6 +1005,47 @@ def align_settings(**settings):
     return st
 
 
+def _cov_colmajor(cov, n):
+    """n covariances indexed [row][column] (a NumPy array or a torch tensor, or None) as (n, 3, 3) column-major, contiguous."""
+    if cov is None:
+        return None
+    if _is_torch(cov):
+        return cov.reshape(n, 3, 3).transpose(1, 2).contiguous()
+    return np.ascontiguousarray(cov.reshape(n, 3, 3).transpose(0, 2, 1))
+
+
+def _registration_result(res):
+    """RegistrationResult of an FdmRegistrationResult."""
+    T = np.array(res.transform, dtype=np.float64).reshape(4, 4).T.copy()
+    cov = np.array(res.covariance, dtype=np.float64).reshape(6, 6) if res.has_covariance else None
+    return RegistrationResult(T, float(res.fitness), float(res.rmse), int(res.iterations), bool(res.converged), cov)
+
+
+def _linearized(entry, n, like, return_correspondences):
+    """The outputs of one linearize entry: makes H, b, error, num_inliers and (asked for) corr — n int32 where the clouds
+    live: on the device of the tensor `like`, or in a NumPy array for `like` None —, calls entry(H, b, error, num_inliers,
+    corr) and returns the result dict."""
+    H, b = (C.c_double * 21)(), (C.c_double * 6)()
+    err, cnt = C.c_double(0.0), C.c_uint64(0)
+    corr = None
+    if return_correspondences:
+        if like is not None:
+            import torch
+            corr = torch.empty(n, dtype=torch.int32, device=like.device)
+        else:
+            corr = np.empty(n, dtype=np.int32)
+    _ck(entry(H, b, C.byref(err), C.byref(cnt), (_ptr if like is None else _dptr)(corr)))
+    Hu = np.array(H, dtype=np.float64)
+    full = np.zeros((6, 6))
+    full[np.triu_indices(6)] = Hu
+    full = full + np.triu(full, 1).T
+    out = {"H": full, "H_upper": Hu, "b": np.array(b, dtype=np.float64), "error": float(err.value),
+           "num_inliers": int(cnt.value)}
+    if return_correspondences:
+        out["corr"] = corr
+    return out
+
+
 def _register_clouds(source, target, target_normals, source_cov, target_cov):
     """(FdmRegisterClouds, device or None, the arrays it points into) for numpy arrays or torch device tensors."""
     sx, sy, sz = source
@@ -1023,7 +1064,6 @@ def _register_clouds(source, target, target_normals, source_cov, target_cov):
                                 "(or NumPy arrays throughout)")
             return v.contiguous()
         ptr, size = _dptr, lambda v: v.numel()                                     # noqa: E731
-        cov = lambda v, n: None if v is None else prep(v).reshape(n, 3, 3).transpose(1, 2).contiguous()   # noqa: E731
     else:
         device = None
 
@@ -1032,12 +1072,11 @@ def _register_clouds(source, target, target_normals, source_cov, target_cov):
                 raise TypeError("registration takes NumPy arrays throughout or torch device tensors throughout")
             return None if v is None else _f32(v).reshape(-1)
         ptr, size = _ptr, lambda v: v.size                                         # noqa: E731
-        cov = lambda v, n: None if v is None else np.ascontiguousarray(prep(v).reshape(n, 3, 3).transpose(0, 2, 1))   # noqa: E731
     if target_normals is not None and not isinstance(target_normals, (tuple, list)):
         target_normals = tuple(target_normals[:, k] for k in range(3))              # an (n, 3) array
     keep = [prep(v) for v in (sx, sy, sz, tx, ty, tz)] + [prep(v) for v in (target_normals or (None,) * 3)]
     ns, nt = size(keep[0]), size(keep[3])
-    keep += [cov(source_cov, ns), cov(target_cov, nt)]                              # [row][column] -> column-major
+    keep += [_cov_colmajor(prep(source_cov), ns), _cov_colmajor(prep(target_cov), nt)]
     p = [ptr(v) for v in keep]
     clouds = capi.FdmRegisterClouds(ns, p[0], p[1], p[2], p[9], nt, p[3], p[4], p[5], p[6], p[7], p[8], p[10],
                                     int(torch_in))
@@ -1055,9 +1094,7 @@ def _register(method, source, target, initial_guess, target_normals, source_cov,
     _ck(capi.load().fdm_cloud_register(capi.REGISTER_METHOD[method], C.byref(clouds), _guess16(initial_guess),
                                        C.byref(st), int(device if dev is None else dev), C.byref(res)))
     del keep
-    T = np.array(res.transform, dtype=np.float64).reshape(4, 4).T.copy()
-    cov = np.array(res.covariance, dtype=np.float64).reshape(6, 6) if res.has_covariance else None
-    return RegistrationResult(T, float(res.fitness), float(res.rmse), int(res.iterations), bool(res.converged), cov)
+    return _registration_result(res)
 
 
 def align_icp(sx, sy, sz, tx, ty, tz, initial_guess=None, device=0, **settings):
@@ -1086,29 +1123,10 @@ def linearize(method, sx, sy, sz, tx, ty, tz, transform=None, target_normals=Non
     of every source point (-1 for none)."""
     clouds, dev, keep = _register_clouds((sx, sy, sz), (tx, ty, tz), target_normals, source_cov, target_cov)
     st = settings.pop("settings", None) or align_settings(**settings)
-    H, b = (C.c_double * 21)(), (C.c_double * 6)()
-    err, cnt = C.c_double(0.0), C.c_uint64(0)
-    ns = int(clouds.n_source)
-    corr = None
-    if return_correspondences:
-        if clouds.on_device:
-            import torch
-            corr = torch.empty(ns, dtype=torch.int32, device=keep[0].device)
-        else:
-            corr = np.empty(ns, dtype=np.int32)
-    _ck(capi.load().fdm_cloud_register_linearize(capi.REGISTER_METHOD[method], C.byref(clouds), _guess16(transform),
-                                                 C.byref(st), int(device if dev is None else dev), H, b, C.byref(err),
-                                                 C.byref(cnt), (_dptr if clouds.on_device else _ptr)(corr)))
-    del keep
-    Hu = np.array(H, dtype=np.float64)
-    full = np.zeros((6, 6))
-    full[np.triu_indices(6)] = Hu
-    full = full + np.triu(full, 1).T
-    out = {"H": full, "H_upper": Hu, "b": np.array(b, dtype=np.float64), "error": float(err.value),
-           "num_inliers": int(cnt.value)}
-    if return_correspondences:
-        out["corr"] = corr
-    return out
+    lib, number = capi.load(), capi.REGISTER_METHOD[method]
+    return _linearized(lambda *out: lib.fdm_cloud_register_linearize(number, C.byref(clouds), _guess16(transform),
+                                                                     C.byref(st), int(device if dev is None else dev), *out),
+                       int(clouds.n_source), keep[0] if clouds.on_device else None, return_correspondences)
 
 
 def register_last_stats():
@@ -1192,13 +1210,10 @@ def _vgicp_source(sx, sy, sz, source_cov, device):
     n, p, on_device, _, keep, torch = _seg_cloud(sx, sy, sz, device)
     cov = None
     if source_cov is not None:
-        if torch is not None:
-            if not _is_torch(source_cov) or source_cov.device != keep[0].device:
-                raise TypeError("registration takes float32 tensors that all live on the source's device "
-                                "(or NumPy arrays throughout)")
-            cov = source_cov.float().reshape(n, 3, 3).transpose(1, 2).contiguous()
-        else:
-            cov = np.ascontiguousarray(_f32(source_cov).reshape(n, 3, 3).transpose(0, 2, 1))    # -> column-major
+        if torch is not None and (not _is_torch(source_cov) or source_cov.device != keep[0].device):
+            raise TypeError("registration takes float32 tensors that all live on the source's device "
+                            "(or NumPy arrays throughout)")
+        cov = _cov_colmajor(source_cov.float() if torch is not None else _f32(source_cov), n)
     return n, p + [(_dptr if on_device else _ptr)(cov)], on_device, keep + (cov,)
 
 
@@ -1229,9 +1244,7 @@ def align_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_resol
     finally:
         if mine:
             vmap.close()
-    T = np.array(res.transform, dtype=np.float64).reshape(4, 4).T.copy()
-    cov = np.array(res.covariance, dtype=np.float64).reshape(6, 6) if res.has_covariance else None
-    return RegistrationResult(T, float(res.fitness), float(res.rmse), int(res.iterations), bool(res.converged), cov)
+    return _registration_result(res)
 
 
 def linearize_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_resolution=1.0, transform=None, device=0,
@@ -1242,31 +1255,14 @@ def linearize_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_r
     vmap, mine = _vgicp_map(voxel_map, target, voxel_resolution, st, device)
     try:
         n, p, on_device, keep = _vgicp_source(sx, sy, sz, source_cov, device)
-        H, b = (C.c_double * 21)(), (C.c_double * 6)()
-        err, cnt = C.c_double(0.0), C.c_uint64(0)
-        corr = None
-        if return_correspondences:
-            if on_device:
-                import torch
-                corr = torch.empty(n, dtype=torch.int32, device=keep[0].device)
-            else:
-                corr = np.empty(n, dtype=np.int32)
-        _ck(capi.load().fdm_cloud_register_vgicp_linearize(vmap._handle(), n, p[0], p[1], p[2], p[3], on_device,
-                                                           _guess16(transform), C.byref(st), H, b, C.byref(err),
-                                                           C.byref(cnt), (_dptr if on_device else _ptr)(corr)))
-        del keep
+        lib = capi.load()
+        return _linearized(lambda *out: lib.fdm_cloud_register_vgicp_linearize(vmap._handle(), n, p[0], p[1], p[2], p[3],
+                                                                               on_device, _guess16(transform),
+                                                                               C.byref(st), *out),
+                           n, keep[0] if on_device else None, return_correspondences)
     finally:
         if mine:
             vmap.close()
-    Hu = np.array(H, dtype=np.float64)
-    full = np.zeros((6, 6))
-    full[np.triu_indices(6)] = Hu
-    full = full + np.triu(full, 1).T
-    out = {"H": full, "H_upper": Hu, "b": np.array(b, dtype=np.float64), "error": float(err.value),
-           "num_inliers": int(cnt.value)}
-    if return_correspondences:
-        out["corr"] = corr
-    return out
 
 
 # ---- cloud segmentation (fdm_cloud_segment_ground / _plane / _planes: include/fdm_engine.h) ----

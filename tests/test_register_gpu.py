@@ -356,6 +356,128 @@ def test_refusals_return_invalid_and_restore_the_device(gpu):
         gpu.align_icp(*[to_device(v).double() for v in s], *[to_device(v) for v in t])
 
 
+# The refusal texts, as fdm_last_error() gives them (the literals of fastdem_amd/csrc: fdm_engine_register.inl,
+# fdm_engine_cloud.inl's check_cloud, fdm_engine_dem.inl's knn_grid_build).
+MSG = {
+    "null": "null argument",
+    "method": "method must be 0 (ICP), 1 (PLANE) or 2 (GICP)",
+    "kernel": "robust_kernel must be 0 (NONE), 1 (HUBER), 2 (TUKEY) or 3 (CAUCHY)",
+    "max_dist": "max_correspondence_dist must not be negative or NaN",
+    "transform": "the transform has an entry that is not finite",
+    "count": "point count exceeds 2^31-1",
+    "array": "null coordinate array",
+    "normals": "alignPlaneICP: target must have normals (all of nx, ny, nz)",
+    "source_cov": "alignGICP: source must have covariances",
+    "target_cov": "alignGICP: target must have covariances",
+    "source_finite": "the source cloud has a coordinate that is not finite",
+    "target_finite": "the cloud has a coordinate that is not finite (undefined in the reference's k-d tree)",
+}
+
+
+CLEAN = object()                                                     # an argument left as lin_base() has it
+
+
+class RawEntries:
+    """fdm_cloud_register and fdm_cloud_register_linearize through ctypes on lin_base()'s clouds as host arrays; a call
+    returns (return code, fdm_last_error()) after asserting that both entries agree on both."""
+
+    def __init__(self, gpu):
+        s, t, sc, tn, tc = RC.lin_base()
+        self.gpu, self.lib = gpu, gpu.capi.load()
+        self.keep = [np.ascontiguousarray(v) for v in (*s, *t)] + [np.ascontiguousarray(tn[:, a]) for a in range(3)] + \
+            [np.ascontiguousarray(sc.transpose(0, 2, 1)), np.ascontiguousarray(tc.transpose(0, 2, 1))]
+        self.P = [v.ctypes.data_as(C.c_void_p) for v in self.keep]
+
+    def dirty(self, which, value=np.nan):
+        """The pointer of a copy of array `which` with one entry replaced."""
+        bad = self.keep[which].copy()
+        bad[500] = value
+        self.keep.append(bad)
+        return bad.ctypes.data_as(C.c_void_p)
+
+    def outputs(self):
+        return [C.byref(self.gpu.capi.FdmRegistrationResult())], \
+            [(C.c_double * 21)(), (C.c_double * 6)(), C.byref(C.c_double()), C.byref(C.c_uint64())]
+
+    def __call__(self, method=0, ns=1000, nt=1000, sx=CLEAN, tx=CLEAN, normals=CLEAN, scov=CLEAN, tcov=CLEAN, guess=None,
+                 clouds=CLEAN, null_output=None, **settings):
+        P = self.P
+        pick = lambda given, default: default if given is CLEAN else given   # noqa: E731
+        if clouds is CLEAN:
+            clouds = C.byref(self.gpu.capi.FdmRegisterClouds(ns, pick(sx, P[0]), P[1], P[2], pick(scov, P[9]), nt,
+                                                             pick(tx, P[3]), P[4], P[5], *pick(normals, P[6:9]),
+                                                             pick(tcov, P[10]), 0))
+        st = self.gpu.align_settings(**settings)
+        g = None if guess is None else (C.c_double * 16)(*guess)
+        out, lin = self.outputs()
+        if null_output is not None:                                  # 0: the align entry's `out`; 0-3: H, b, error, count
+            out[0] = None
+            lin[null_output] = None
+        rc = self.lib.fdm_cloud_register(method, clouds, g, C.byref(st), 0, *out)
+        said = self.lib.fdm_last_error().decode()
+        rc2 = self.lib.fdm_cloud_register_linearize(method, clouds, g, C.byref(st), 0, *lin, None)
+        assert (rc2, self.lib.fdm_last_error().decode()) == (rc, said)
+        return rc, said
+
+
+def test_every_refusal_says_why_and_the_first_fault_in_the_documented_order_wins(gpu):
+    """fdm_last_error() after every refusal of both cloud entries, and where two faults meet the earlier of: null clouds,
+    method, robust_kernel, max_correspondence_dist, transform, source cloud, target cloud, (the empty return), plane
+    normals, GICP source covariances, GICP target covariances — then the device's own: source, target not finite."""
+    call, INVALID = RawEntries(gpu), gpu.capi.FDM_ERR_INVALID
+    refused = lambda key, **kw: call(**kw) == (INVALID, MSG[key])       # noqa: E731
+    bad_T = np.eye(4).reshape(16).copy()
+    bad_T[7] = np.inf
+    assert call(0)[0] == 0 and call(1)[0] == 0 and call(2)[0] == 0
+    assert refused("null", clouds=None)
+    assert refused("method", method=3) and refused("method", method=-1)
+    assert refused("kernel", robust_kernel=4) and refused("kernel", robust_kernel=-1)
+    assert refused("max_dist", max_correspondence_dist=-1.0) and refused("max_dist", max_correspondence_dist=math.nan)
+    assert refused("transform", guess=bad_T)
+    assert refused("count", ns=1 << 31) and refused("count", nt=1 << 31)
+    assert refused("array", sx=None) and refused("array", tx=None)
+    assert refused("normals", method=1, normals=(None, None, None)) and refused("normals", method=1, normals=(call.P[6], None, call.P[8]))
+    assert refused("source_cov", method=2, scov=None) and refused("target_cov", method=2, tcov=None)
+    assert refused("source_finite", sx=call.dirty(0)) and refused("source_finite", sx=call.dirty(0, -np.inf))
+    assert refused("target_finite", tx=call.dirty(3)) and refused("target_finite", tx=call.dirty(3, np.inf))
+    # two faults at once
+    assert refused("null", clouds=None, method=7, robust_kernel=4)
+    assert refused("method", method=3, robust_kernel=4)
+    assert refused("kernel", robust_kernel=4, max_correspondence_dist=-1.0)
+    assert refused("max_dist", max_correspondence_dist=-1.0, guess=bad_T)
+    assert refused("transform", guess=bad_T, sx=None)
+    assert refused("count", ns=1 << 31, tx=None)                     # the source cloud, then the target
+    assert refused("array", tx=None, method=1, normals=(None, None, None))
+    assert refused("source_cov", method=2, scov=None, tcov=None)
+    assert refused("source_finite", sx=call.dirty(0), tx=call.dirty(3))
+    # an empty cloud returns before the channels are asked for
+    assert call(1, nt=0, normals=(None, None, None))[0] == 0 and call(2, ns=0, scov=None, tcov=None)[0] == 0
+
+
+def test_a_null_output_is_refused_before_anything_else_is_looked_at(gpu):
+    """out of fdm_cloud_register, and each of H, b, error and num_inliers of fdm_cloud_register_linearize: `null argument`,
+    whatever else is wrong with the call (here an unknown method, which is otherwise the first thing said)."""
+    call, INVALID = RawEntries(gpu), gpu.capi.FDM_ERR_INVALID
+    assert call(method=7) == (INVALID, MSG["method"])
+    for k in range(4):
+        assert call(null_output=k) == (INVALID, MSG["null"])
+        assert call(method=7, robust_kernel=4, null_output=k) == (INVALID, MSG["null"])
+
+
+def test_nobody_corresponds_on_the_device(gpu):
+    """linearize against an empty target with torch tensors: the correspondences come back as a device tensor of -1 (the
+    fill runs on the device), the sums are zero."""
+    import torch
+    s = [to_device(v) for v in RC.sphere(63)]
+    e = [torch.zeros(0, dtype=torch.float32, device=s[0].device) for _ in range(3)]
+    lin = gpu.linearize("icp", *s, *e, return_correspondences=True)
+    corr = lin["corr"]
+    assert torch.is_tensor(corr) and corr.device == s[0].device and corr.dtype == torch.int32 and corr.shape == (63,)
+    assert bool((corr == -1).all())
+    assert lin["num_inliers"] == 0 and lin["error"] == 0.0 and not lin["H"].any() and not lin["H_upper"].any() and not lin["b"].any()
+    assert gpu.register_last_stats()["linearizations"] == 0
+
+
 def test_python_entries_numpy_and_torch(gpu):
     case = RC.align_case("plane_icp")
     want = case.restated("forward")

@@ -12,6 +12,7 @@ case's recorded spread between summation orders (floor 1e-13).
 
 Run on the GPU box:  python -m pytest tests -m gpu
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -344,3 +345,101 @@ def test_early_returns_and_refusals(gpu):
     with pytest.raises(gpu.EngineError, match="closed"):
         vm.info()
     vm.close()                                                        # twice is fine
+
+
+# ---- 5. the C entries' refusals ----
+MSG = {                                                              # the literals of fastdem_amd/csrc, as fdm_last_error() gives them
+    "null": "null argument",
+    "kernel": "robust_kernel must be 0 (NONE), 1 (HUBER), 2 (TUKEY) or 3 (CAUCHY)",
+    "transform": "the transform has an entry that is not finite",
+    "count": "point count exceeds 2^31-1",
+    "array": "null coordinate array",
+    "source_cov": "alignVGICP: source must have covariances",
+    "source_finite": "the source cloud has a coordinate that is not finite",
+    "device": "the voxel map was built on another device than the source lives on",
+}
+
+
+def test_refusals_say_why_by_both_entries_and_restore_the_device(gpu):
+    """Every refusal of fdm_cloud_register_vgicp and fdm_cloud_register_vgicp_linearize: the same code and the same
+    fdm_last_error() from both, the earlier fault winning in the order null map, robust_kernel, transform, source cloud,
+    (the empty return), source covariances; a null output before all of them; max_correspondence_dist not looked at.  The
+    device: where a second one exists the thread is put on it and the map lives on device 0, so a call that did not put
+    the thread's device back would leave it on 0; on a machine with one device the assertion cannot fail and proves
+    nothing."""
+    import torch
+    other = torch.cuda.device_count() - 1                            # 0 where there is one device
+    torch.cuda.set_device(other)
+    lib, INVALID = gpu.capi.load(), gpu.capi.FDM_ERR_INVALID
+    c = VC.designed(300, (1, 2, 3, 4, 5, 8))
+    n = c[0].size
+    keep = [np.ascontiguousarray(v) for v in c] + [np.tile(np.eye(3, dtype=F32), (n, 1, 1))]
+    dirty = keep[0].copy()
+    dirty[17] = np.nan
+    P = [v.ctypes.data_as(C.c_void_p) for v in keep + [dirty]]
+    bad_T = np.eye(4).reshape(16).copy()
+    bad_T[13] = np.nan
+    e = tuple(np.zeros(0, dtype=F32) for _ in range(3))
+
+    def call(vm, ns=n, sx=P[0], cov=P[3], on_device=0, guess=None, null_output=None, **settings):
+        st = gpu.align_settings(**settings)
+        g = None if guess is None else (C.c_double * 16)(*guess)
+        out = [C.byref(gpu.capi.FdmRegistrationResult())]
+        lin = [(C.c_double * 21)(), (C.c_double * 6)(), C.byref(C.c_double()), C.byref(C.c_uint64())]
+        if null_output is not None:                                  # the align entry's `out`; H, b, error or count
+            out[0] = None
+            lin[null_output] = None
+        h = None if vm is None else vm._handle()
+        before = torch.cuda.current_device()
+        rc = lib.fdm_cloud_register_vgicp(h, ns, sx, P[1], P[2], cov, on_device, g, C.byref(st), *out)
+        said = lib.fdm_last_error().decode()
+        rc2 = lib.fdm_cloud_register_vgicp_linearize(h, ns, sx, P[1], P[2], cov, on_device, g, C.byref(st), *lin, None)
+        assert (rc2, lib.fdm_last_error().decode()) == (rc, said)
+        assert torch.cuda.current_device() == before == other
+        return rc, said
+
+    with gpu.VoxelMap(*c, resolution=VC.EDGE, device=0) as vm, gpu.VoxelMap(*e, resolution=VC.EDGE, device=0) as empty:
+        refused = lambda key, m=vm, **kw: call(m, **kw) == (INVALID, MSG[key])   # noqa: E731
+        assert call(vm)[0] == 0
+        assert call(vm, max_correspondence_dist=-1.0)[0] == 0 and call(vm, max_correspondence_dist=math.nan)[0] == 0
+        assert refused("null", m=None)
+        assert refused("kernel", robust_kernel=4) and refused("kernel", robust_kernel=-1)
+        assert refused("transform", guess=bad_T)
+        assert refused("count", ns=1 << 31) and refused("array", sx=None)
+        assert refused("source_cov", cov=None)
+        assert refused("source_finite", sx=P[4])
+        # two faults at once
+        assert refused("null", m=None, robust_kernel=4, guess=bad_T, sx=None, cov=None)
+        assert refused("kernel", robust_kernel=4, guess=bad_T)
+        assert refused("transform", guess=bad_T, sx=None)
+        assert refused("array", sx=None, cov=None)
+        assert refused("source_cov", sx=P[4], cov=None)
+        for k in range(4):
+            assert refused("null", null_output=k) and refused("null", null_output=k, robust_kernel=4, guess=bad_T)
+            assert refused("null", m=None, null_output=k)
+        # an empty source or map returns before the covariances are asked for
+        assert call(empty, cov=None)[0] == 0 and call(vm, ns=0, cov=None)[0] == 0
+        assert refused("kernel", m=empty, robust_kernel=4) and refused("array", m=empty, sx=None)
+        if other != 0:                                               # device arrays that live where the map does not
+            far = [torch.from_numpy(v).to(f"cuda:{other}") for v in keep]
+            torch.cuda.synchronize(other)
+            assert refused("device", sx=C.c_void_p(far[0].data_ptr()), cov=C.c_void_p(far[3].data_ptr()), on_device=1)
+    torch.cuda.set_device(0)
+
+
+def test_nobody_corresponds_on_the_device(gpu):
+    """linearize_vgicp against an empty map with torch tensors: the correspondences come back as a device tensor of -1 (the
+    fill runs on the device), the sums are zero."""
+    import torch
+    c = VC.designed(300, (1, 2, 3, 4, 5, 8))
+    s = [torch.from_numpy(np.array(v, dtype=F32)).cuda() for v in c]
+    cov = torch.eye(3, dtype=torch.float32, device=s[0].device).repeat(s[0].numel(), 1, 1)
+    e = tuple(np.zeros(0, dtype=F32) for _ in range(3))
+    with gpu.VoxelMap(*e, resolution=VC.EDGE) as empty:
+        out = gpu.linearize_vgicp(*s, cov, voxel_map=empty, return_correspondences=True)
+        st = gpu.register_last_stats()
+    corr = out["corr"]
+    assert torch.is_tensor(corr) and corr.device == s[0].device and corr.dtype == torch.int32 and corr.shape == (s[0].numel(),)
+    assert bool((corr == -1).all())
+    assert out["num_inliers"] == 0 and out["error"] == 0.0 and not out["H"].any() and not out["H_upper"].any() and not out["b"].any()
+    assert st["linearizations"] == 0
