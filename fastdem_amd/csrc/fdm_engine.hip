@@ -1626,7 +1626,7 @@ int fdm_engine_debug_batch_dirty(fdm_engine* e, uint64_t out[3]) {
     HIPCK(hipMemcpy(hz.data(), e->mzs[k], slots * sizeof(uint2), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < slots; ++i) {
       out[0] += hk[i] != kEmptyKey;
-      out[1] += (ha[i].x != 0u) + (ha[i].y != 0u) + (ha[i].z != kNoIdx) + (ha[i].w != 0u);
+      out[1] += (ha[i].x != 0u) + (ha[i].y != 0u) + (ha[i].z != 0u) + (ha[i].w != 0u);
       out[2] += (hz[i].x != 0xFFFFFFFFu) + (hz[i].y != 0xFFFFFFFFu);
     }
   }

@@ -97,8 +97,8 @@ int ensure_multi(fdm_engine* e, size_t max_n, size_t blocks) {
     for (int k = 0; k < 2; ++k) {
       const int blocks_f = int(std::min<size_t>((slots + 255) / 256, 4096));
       hipLaunchKernelGGL(k_fill_u64, dim3(blocks_f), dim3(256), 0, e->stream, e->mkey[k], kEmptyKey, slots);
-      hipLaunchKernelGGL(k_fill_aux, dim3(blocks_f), dim3(256), 0, e->stream, e->maux[k], slots);
       HIPCK(hipGetLastError());
+      HIPCK(hipMemsetAsync(e->maux[k], 0, slots * sizeof(uint4), e->stream));  // (every aux word a maximum: clean = 0)
       HIPCK(hipMemsetAsync(e->mzs[k], 0xFF, slots * sizeof(uint2), e->stream));
     }
   }
@@ -328,9 +328,9 @@ int enqueue_multi(fdm_engine* e, uint32_t count, const fdm_device_scan* scans, u
   K.has_var = hv ? 1 : 0;
   K.dbg = e->opt.dbg_batch;
   // the chain of moves walked one launch ahead (mwalk_body): automatic = every scan of a quantile-estimator batch; for
-  // Kalman without the ray stage only the scans from kKalmanWalkFrom on (the longest chains) — the earlier rows walk their
-  // own, which staggers their flushes behind the update half (profiles/r07: all rows at once, 17.6 us per launch against
-  // 15.6; rows 12-15 only, 24.2 -> 25.2 G pts/s); 1 = every scan of every batch
+  // Kalman without the ray stage the scans from kKalmanWalkFrom on — 0, every scan, since the flush's aux words leave as
+  // one request per record (profiles/r19/flush); it was 12 while the early rows' own walks had to stagger four
+  // requests per record behind the update half (profiles/r07); 1 = every scan of every batch
   K.walk = e->opt.batch_walk < 0 ? ((e->cfg.estimation_type == 1 || !ray) ? 1 : 0) : e->opt.batch_walk;
   K.walk_from = (e->opt.batch_walk < 0 && e->cfg.estimation_type != 1) ? kKalmanWalkFrom : 0;
 

@@ -101,9 +101,9 @@ __device__ __forceinline__ const T& kernarg_from_here(const T& v) {
 #define FDM_MB_WAVES 6  // waves per SIMD k_mbatch is compiled for (<= 80 VGPRs; the LDS allows 6 blocks per CU): every block of a 16-scan VLP-16 batch resident at once
 #endif
 #ifndef FDM_KALMAN_WALK_FROM
-#define FDM_KALMAN_WALK_FROM 12
+#define FDM_KALMAN_WALK_FROM 0
 #endif
-constexpr int kKalmanWalkFrom = FDM_KALMAN_WALK_FROM;  // Kalman batches: the first scan whose bin blocks take the walker's chain (fdm_engine_multi.inl)
+constexpr int kKalmanWalkFrom = FDM_KALMAN_WALK_FROM;  // Kalman batches: the first scan whose bin blocks take the walker's chain (fdm_engine_multi.inl; 12 until profiles/r19/flush)
 constexpr int kMStates = 4;              // ring of batch states: update b-1 | bin b | crop b+1 | being re-armed
 
 // Device-resident bookkeeping of one batch.  Every word other blocks poll or add to sits on its own 128-byte
@@ -367,8 +367,11 @@ __device__ __forceinline__ void mcrop_body(const MCrop& Cn, const MCommon& K, co
 // finish (phase stamps: 13.6 -> 17.1 us; measured again with the compact winner slots of mbin_body's merge: rocprof
 // 15.6 -> 17.6 us per launch, profiles/r07).  Taking the walker's chain only in the rows of the longest chains keeps the
 // stagger of the early rows and takes the tail off the late ones: scans >= 12 of a 16-scan Kalman batch
-// (MCommon::walk_from, kKalmanWalkFrom; profiles/r07: 24.2 -> 25.2 G pts/s against 10, 13 or 14 within 0.4 %).  So by
-// default the walker serves every scan with the quantile estimator, scans 12+ with Kalman without the ray stage, none
+// (MCommon::walk_from, kKalmanWalkFrom; profiles/r07: 24.2 -> 25.2 G pts/s against 10, 13 or 14 within 0.4 %).  That
+// stagger was worth something only while a record cost four memory-side requests: since the flush sends a record's aux
+// words as one (profiles/r19/flush: 123 K -> 71 K atomic requests per launch) every row takes the walker's chain —
+// kKalmanWalkFrom 0: 31.5 -> 34.8 G pts/s against 12, 33.8 with 8.  So by
+// default the walker serves every scan with the quantile estimator and with Kalman without the ray stage, none
 // with Kalman and raycasting (option "batch_walk": -1 automatic, 0 off, 1 on for every scan).  The walk itself is the reference's sequence, scan by scan: geometry before scan
 // k + 1 = scan k's candidate if scan k moved the map, else unchanged — the same numbers the per-block walk produces
 // (it defers the index wrap of short moves, which yields the candidate's wrapped index).
@@ -711,22 +714,12 @@ __device__ __forceinline__ void mbin_body(const MBin& B_, const MCommon& K_, con
   // wavefronts reached the counter — it depends on timing, and no output may depend on it: a cell never compares two
   // slots of one block.  j < the block's claims <= its inside points, so slot < n: inside the scan's slot of obs / cobs
   // and never kNoIdx.  fst and zs stay point indices (never gathered).
-  auto merge = [&](uint32_t c, unsigned long long key, uint32_t zmx, uint32_t imx, uint32_t fst, uint32_t lst,
-                   uint32_t slot) {
-    if (K.dbg == 1) return;
+  // The key half of a record (one lane per record): the key's atomic, the colour and the observation of the slot.
+  auto merge_key = [&](uint32_t c, unsigned long long key, uint32_t lst, uint32_t slot) {
     const uint32_t idx = uint32_t(key);  // the block-local winner's point index (kNoIdx: no finite z below FLT_MAX)
     if (idx != kNoIdx) key = (key & 0xFFFFFFFF00000000ull) | slot;
     atomicMin(&S_key[c], key);
-    uint32_t* a = S_aux + size_t(c) * 4;
-    if (zmx) atomicMax(a + 0, zmx);
-    if (has_int) {
-      if (imx) atomicMax(a + 1, imx);
-      atomicMin(a + 2, fst);
-    }
-    if (has_col) {
-      atomicMax(a + 3, slot);
-      S_cobs[slot] = prgb[lst];
-    }
+    if (has_col) S_cobs[slot] = prgb[lst];
     if (idx != kNoIdx) {
       const float4 p = S.s_pt[idx - lb * kMBlock];
       float var = 0.0f;  // CellObservation default (elevation_mapping.hpp:26-34)
@@ -883,10 +876,31 @@ __device__ __forceinline__ void mbin_body(const MBin& B_, const MCommon& K_, con
   FDM_PHASE(2);  // index + LDS fold done
 #endif
   __syncthreads();  // the table, the record list and its count are complete
-  const unsigned n_occ = uni(S.s_nrec);
-  for (unsigned j = threadIdx.x; j < n_occ; j += 256u) {
-    const unsigned t = S.s_list[j];
-    merge(S.t_cell[t], S.t_key[t], S.t_zmx[t], S.t_imx[t], S.t_fst[t], S.t_lst[t], lb * kMBlock + j);
+  // A pass takes 64 records.  Their aux words leave in ONE atomic instruction, four adjacent lanes per record (lane
+  // 4 r + w: word w of record r, 16 contiguous bytes — the memory side takes a record as one request where three
+  // instructions were three, scripts/ubench/atomic_rec.hip).  Every word of the scratch is a maximum and its clean value
+  // is 0: fst travels inverted (max of ~fst = ~ min of fst; kNoIdx -> 0), and a lane whose word is 0 has nothing to
+  // send — a channel the instantiation lacks, no finite intensity, make_zmax's 0.  The key halves of the pass go
+  // through ONE wavefront, another one in every pass and the last in the first (the records of a typical block fill
+  // the lower wavefronts with aux words): neither part waits for the other.
+  const unsigned n_occ = K.dbg == 1 ? 0u : uni(S.s_nrec);  // (dbg_batch 1: no merge at all)
+  for (unsigned j0 = 0u, p = 0u; j0 < n_occ; j0 += 64u, ++p) {
+    const unsigned r = j0 + (threadIdx.x >> 2), w = threadIdx.x & 3u;
+    if (r < n_occ) {
+      const unsigned t = S.s_list[r];
+      const uint32_t* const src = w == 0u ? S.t_zmx : w == 1u ? S.t_imx : S.t_fst;
+      uint32_t v = src[t];
+      if (w == 2u) v = ~v;
+      if (w == 3u) v = has_col ? lb * kMBlock + r : 0u;  // (the slot: a later block's is higher)
+      if (v) atomicMax(S_aux + size_t(S.t_cell[t]) * 4 + w, v);
+    }
+    if (wave == ((3u - p) & 3u)) {  // (wave-uniform)
+      const unsigned j = j0 + lane;
+      if (j < n_occ) {
+        const unsigned t = S.s_list[j];
+        merge_key(S.t_cell[t], S.t_key[t], S.t_lst[t], lb * kMBlock + j);
+      }
+    }
   }
   if (threadIdx.x == 0) {
     const unsigned ni = S.s_in[0] + S.s_in[1] + S.s_in[2] + S.s_in[3];
@@ -1028,7 +1042,7 @@ __device__ __forceinline__ void mupd_exchange(const MUpd& U, const typename POLI
   for (int q = 0; q < kPer; ++q) {
     const unsigned j = lt + unsigned(q) * 256u;
     ob_[q] = make_float2(kFltMax, 0.0f);  // (no finite z: FLT_MAX, variance 0 — elevation_mapping.hpp:26-34)
-    ax_[q] = make_uint4(0u, 0u, kNoIdx, 0u);
+    ax_[q] = make_uint4(0u, 0u, 0u, 0u);
     zs_[q] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
     ev_[q].idx = kNoIdx; ev_[q].cell = 0; ev_[q].k = 0;
     if (r0 + j < r1) {
@@ -1045,7 +1059,7 @@ __device__ __forceinline__ void mupd_exchange(const MUpd& U, const typename POLI
     const unsigned j = lt + unsigned(q) * 256u;
     if (r0 + j >= r1) continue;
     if (has_col) S.rgb[j] = U.cobs[size_t(ev_[q].k) * U.obs_stride + ax_[q].w];  // (one more dependent gather)
-    const uint32_t zm = ax_[q].x, imx = ax_[q].y, fst = ax_[q].z;
+    const uint32_t zm = ax_[q].x, imx = ax_[q].y, fst = ~ax_[q].z;  // (the scratch holds ~fst: mbin_body's flush)
     MObs ob;
     ob.min_z = ob_[q].x;
     ob.var = POLICY::obs_var(L, ob_[q].y);  // (Kalman: R, substituted here by 256 threads and not in the owners' walk)
@@ -1057,7 +1071,7 @@ __device__ __forceinline__ void mupd_exchange(const MUpd& U, const typename POLI
     FDM_PHASE(1);  // round trip 2 (observations, record) back
     const size_t oc = size_t(ev_[q].k) * ncell + (bid * cpb + ev_[q].cell);
     U.key[oc] = kEmptyKey;  // the scratch is clean again for the batch after next
-    U.aux[oc] = make_uint4(0u, 0u, kNoIdx, 0u);
+    U.aux[oc] = make_uint4(0u, 0u, 0u, 0u);
     if ((zs_[q].x & zs_[q].y) != 0xFFFFFFFFu) U.zs[oc] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
   }
 }
