@@ -4,18 +4,20 @@ Layout (only what the path needs):
   csrc/        hand-written HIP kernels + the C ABI (include/fdm_engine.h) -> lib/libfdm_engine.so
   capi.py      ctypes declarations of that ABI (plumbing)
   engine.py    Python handle used by tests / bench.py
+  cloud.py     the cloud library: rasterization, buildDEM, filters, normals, registration, segmentation, clustering
+  _arrays.py   what "NumPy arrays or torch device tensors" means for every cloud call
   pcd.py       PCD files: load_pcd, save_pcd, pcd2dem, Engine.to_pcd
   synth.py     synthetic scans of the BASELINE.json configurations
   tiling.py    multi-GPU spatial tiling + RCCL halo exchange of one global map
   cpp/         C++17 host mirror of fastdem::FastDEM / ElevationMap over the C ABI
 """
 from . import capi, synth  # noqa: F401
-from .engine import (ClusterResult, DEMConfig, Engine, EngineError, HostArray, RansacResult, RegistrationResult, VoxelMap, align_gicp,  # noqa: F401
-                     align_icp, align_plane_icp, align_settings, align_vgicp, linearize_vgicp, apply_cluster_labels, build_dem, cluster_last_stats, estimate_normals, euclidean_cluster,
-                     from_point_cloud,
-                     grid_max_z, host_array, linearize, normals_last_stats, register_last_stats, segment_ground,
-                     segment_last_stats, segment_multiple_planes, segment_plane, sor_last_stats,
-                     statistical_outlier_removal, voxel_grid)
+from .engine import Engine, EngineError, HostArray, host_array  # noqa: F401
+from .cloud import (ClusterResult, DEMConfig, RansacResult, RegistrationResult, VoxelMap, align_gicp, align_icp,  # noqa: F401
+                    align_plane_icp, align_settings, align_vgicp, apply_cluster_labels, build_dem, cluster_last_stats,
+                    estimate_normals, euclidean_cluster, from_point_cloud, grid_max_z, linearize, linearize_vgicp,
+                    normals_last_stats, register_last_stats, segment_ground, segment_last_stats, segment_multiple_planes,
+                    segment_plane, sor_last_stats, statistical_outlier_removal, voxel_grid)
 from . import pcd  # noqa: F401,E402
 
 __all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud", "DEMConfig", "build_dem",

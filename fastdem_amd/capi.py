@@ -469,3 +469,14 @@ def default_image_config():
     cfg = FdmImageConfig()
     load().fdm_default_image_config(C.byref(cfg))
     return cfg
+
+
+def stats_dict(st):
+    """A statistics struct as a dict: integer fields as int, floating-point fields as float, arrays as tuples of float;
+    `reserved*` fields are left out."""
+    out = {}
+    for name, _ in st._fields_:
+        if not name.startswith("reserved"):
+            v = getattr(st, name)
+            out[name] = v if isinstance(v, (int, float)) else tuple(float(e) for e in v)
+    return out

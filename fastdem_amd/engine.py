@@ -12,8 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (FdmCloud2Layout, FdmCloudOut, FdmCloudView, FdmConfig, FdmDemConfig, FdmDemStats, FdmGeometry, FdmRasterStats, FdmScanStats,
-                   FdmNormalStats, FdmSorStats, FdmTile)
+from ._arrays import arrays
+from .capi import FdmCloud2Layout, FdmGeometry, FdmRasterStats, FdmScanStats, FdmTile
 
 
 class EngineError(RuntimeError):
@@ -46,6 +46,21 @@ def _colmajor16(T):
 def _dptr(t):
     """Device pointer of a torch tensor (or None)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _pd(a):
+    """double * of a float64 array (which the caller keeps alive)."""
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _geometry(width, height, resolution, position):
+    g = FdmGeometry()
+    # ElevationMap::setGeometry(float,float,float) promotes float -> double
+    # (elevation_map.hpp:112-116): 0.1f becomes 0.100000001490116...
+    g.length_x, g.length_y = float(np.float32(width)), float(np.float32(height))
+    g.resolution = float(np.float32(resolution))
+    g.position_x, g.position_y = float(position[0]), float(position[1])
+    return g
 
 
 class HostArray:
@@ -95,10 +110,6 @@ def write_png(path, rgba):
                 chunk(b"IDAT", zlib.compress(lines.tobytes(), 6)) + chunk(b"IEND", b""))
 
 
-def _is_torch(a):
-    return hasattr(a, "data_ptr")
-
-
 def _raster_method(method):
     return capi.RASTER_METHOD[method] if isinstance(method, str) else int(method)
 
@@ -112,13 +123,7 @@ class Engine:
                  device=0):
         self._lib = capi.load()
         self.cfg = cfg if cfg is not None else capi.default_config()
-        g = FdmGeometry()
-        # ElevationMap::setGeometry(float,float,float) promotes float -> double
-        # (elevation_map.hpp:112-116): 0.1f becomes 0.100000001490116...
-        g.length_x = float(np.float32(width))
-        g.length_y = float(np.float32(height))
-        g.resolution = float(np.float32(resolution))
-        g.position_x, g.position_y = float(position[0]), float(position[1])
+        g = _geometry(width, height, resolution, position)
         self._tile = None
         tp = None
         if tile is not None:
@@ -127,6 +132,10 @@ class Engine:
         h = C.c_void_p()
         _ck(self._lib.fdm_engine_create(C.byref(g), C.byref(self.cfg), tp, int(device), C.byref(h)))
         self._h = h
+        self._opened()
+
+    def _opened(self):
+        """The sizes of the map and of this engine's share of it, and the class's default options, once the handle is there."""
         geo = self.geometry()
         self.rows, self.cols = geo.rows, geo.cols
         self.s_rows = self._tile.rows if self._tile else self.rows
@@ -143,11 +152,7 @@ class Engine:
         self._tile = None
         self._h = handle
         try:
-            geo = self.geometry()
-            self.rows, self.cols = geo.rows, geo.cols
-            self.s_rows, self.s_cols = self.rows, self.cols
-            for key, value in cls.default_options.items():
-                self.set_option(key, value)
+            self._opened()
         except Exception:
             self.close()  # (the handle is this object's alone: nobody else would destroy it)
             raise
@@ -156,10 +161,7 @@ class Engine:
     @classmethod
     def create_map(cls, width, height, resolution, position=(0.0, 0.0), device=0):
         """ElevationMap(width, height, resolution) alone (fdm_engine_create_map): the three basic layers, no estimator."""
-        g = FdmGeometry()
-        g.length_x, g.length_y = float(np.float32(width)), float(np.float32(height))
-        g.resolution = float(np.float32(resolution))
-        g.position_x, g.position_y = float(position[0]), float(position[1])
+        g = _geometry(width, height, resolution, position)
         h = C.c_void_p()
         _ck(capi.load().fdm_engine_create_map(C.byref(g), None, int(device), C.byref(h)))
         return cls._adopt(h)
@@ -202,9 +204,7 @@ class Engine:
         tbs, twb = _colmajor16(T_base_sensor), _colmajor16(T_world_base)
         st = FdmScanStats()
         rc = _ck(self._lib.fdm_engine_integrate(
-            self._h, x.size, _ptr(x), _ptr(y), _ptr(z), _ptr(a), _ptr(c), _ptr(v),
-            tbs.ctypes.data_as(C.POINTER(C.c_double)), twb.ctypes.data_as(C.POINTER(C.c_double)),
-            C.byref(st)))
+            self._h, x.size, _ptr(x), _ptr(y), _ptr(z), _ptr(a), _ptr(c), _ptr(v), _pd(tbs), _pd(twb), C.byref(st)))
         return rc, st.as_dict()
 
     def integrate_points4(self, xyz1, T_base_sensor, T_world_base, intensity=None, rgb=None, sigma_z2=None):
@@ -218,8 +218,8 @@ class Engine:
         tbs, twb = _colmajor16(T_base_sensor), _colmajor16(T_world_base)
         st = FdmScanStats()
         rc = _ck(self._lib.fdm_engine_integrate_points4(
-            self._h, p.shape[0], p.ctypes.data if p.shape[0] else None, _ptr(a), _ptr(c), _ptr(v),
-            tbs.ctypes.data_as(C.POINTER(C.c_double)), twb.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st)))
+            self._h, p.shape[0], p.ctypes.data if p.shape[0] else None, _ptr(a), _ptr(c), _ptr(v), _pd(tbs), _pd(twb),
+            C.byref(st)))
         return rc, st.as_dict()
 
     def wait_torch(self):
@@ -532,9 +532,7 @@ class Engine:
             b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8))
             data, dev = _ptr(b), 0
         rc = _ck(self._lib.fdm_engine_integrate_cloud2(
-            self._h, data, dev, int(n_points), C.byref(layout),
-            tbs.ctypes.data_as(C.POINTER(C.c_double)), twb.ctypes.data_as(C.POINTER(C.c_double)),
-            C.byref(st)))
+            self._h, data, dev, int(n_points), C.byref(layout), _pd(tbs), _pd(twb), C.byref(st)))
         return rc, st.as_dict()
 
     # -- static point clouds (fastdem/io/pcd_convert.hpp) --
@@ -542,39 +540,23 @@ class Engine:
         """fastdem::fromPointCloud(cloud, map, method): numpy arrays (staged) or torch device tensors (read in place).
         Synchronous.  Returns (status, {"n_points_used", "n_cells_written"}); status 0 = written, 1 = empty cloud,
         3 = no point landed in a cell (the map, its layer list included, is untouched)."""
+        A = arrays(x)
         st = FdmRasterStats()
-        m = _raster_method(method)
-        if _is_torch(x):
-            import torch
-            torch.cuda.current_stream().synchronize()  # the call reads the tensors at once, on the engine's stream
-            rc = _ck(self._lib.fdm_engine_from_point_cloud_device(
-                self._h, x.numel(), _dptr(x), _dptr(y), _dptr(z), _dptr(intensity), _dptr(rgb), m, C.byref(st)))
-        else:
-            x, y, z = _f32(x), _f32(y), _f32(z)
-            a, c = _f32(intensity), _u32(rgb)
-            rc = _ck(self._lib.fdm_engine_from_point_cloud(self._h, x.size, _ptr(x), _ptr(y), _ptr(z), _ptr(a), _ptr(c),
-                                                           m, C.byref(st)))
-        return rc, {"n_points_used": int(st.n_points_used), "n_cells_written": int(st.n_cells_written)}
+        fn = self._lib.fdm_engine_from_point_cloud_device if A.on_device else self._lib.fdm_engine_from_point_cloud
+        rc = _ck(fn(self._h, A.n, *A.cloud5(x, y, z, intensity, rgb), _raster_method(method), C.byref(st)))
+        return rc, capi.stats_dict(st)
 
     def remove_floating_points(self, x, y, z, height_threshold=2.0, bin_size=0.0):
         """removeFloatingPoints(cloud, map, height_threshold, bin) on this map's geometry: the keep mask (bool[n], or a
         torch uint8 device tensor for device tensors).  bin_size 0 = the resolution.  The map is not touched."""
+        A = arrays(x)
+        p = A.xyz(x, y, z)
         n_kept = C.c_uint64(0)
-        if _is_torch(x):
-            import torch
-            torch.cuda.current_stream().synchronize()
-            keep = torch.zeros(x.numel(), dtype=torch.uint8, device=x.device)
-            _ck(self._lib.fdm_engine_remove_floating_points(self._h, x.numel(), _dptr(x), _dptr(y), _dptr(z), 1,
-                                                            float(height_threshold), float(bin_size), _dptr(keep),
-                                                            C.byref(n_kept)))
-            return keep
-        x, y, z = _f32(x), _f32(y), _f32(z)
-        keep = np.zeros(x.size, dtype=np.uint8)
-        _ck(self._lib.fdm_engine_remove_floating_points(self._h, x.size, _ptr(x), _ptr(y), _ptr(z), 0,
-                                                        float(height_threshold), float(bin_size), _ptr(keep),
-                                                        C.byref(n_kept)))
+        keep = A.zeros(A.n, "u8")
+        _ck(self._lib.fdm_engine_remove_floating_points(self._h, A.n, *p, A.on_device, float(height_threshold),
+                                                        float(bin_size), A.ptr(keep), C.byref(n_kept)))
         assert int(keep.sum()) == n_kept.value
-        return keep.astype(bool)
+        return A.mask(keep)
 
     def last_raster_ms(self):
         """(ids, grouping, walk) device ms of the last from_point_cloud (enable_profile() first)."""
@@ -743,748 +725,3 @@ class Engine:
         ms = (C.c_float * 2)()
         _ck(self._lib.fdm_engine_last_kernel_ms(self._h, ms))
         return float(ms[0]), float(ms[1])
-
-
-def from_point_cloud(x, y, z, resolution, intensity=None, rgb=None, method="max", device=0):
-    """fastdem::fromPointCloud(cloud, resolution, method): a map-only Engine sized to the cloud's x / y bounding box
-    (found on the device) with the cloud rasterized into it; None for an empty cloud.  numpy arrays or torch device
-    tensors.  A cloud without a finite, positive extent (every x or y NaN, an infinite coordinate) raises EngineError."""
-    lib = capi.load()
-    h, st = C.c_void_p(), FdmRasterStats()
-    m = _raster_method(method)
-    if _is_torch(x):
-        import torch
-        torch.cuda.current_stream().synchronize()
-        n, on_device = x.numel(), 1
-        args = [_dptr(v) for v in (x, y, z, intensity, rgb)]
-    else:
-        x, y, z = _f32(x), _f32(y), _f32(z)
-        keep = (x, y, z, _f32(intensity), _u32(rgb))
-        n, on_device = x.size, 0
-        args = [_ptr(v) for v in keep]
-    rc = _ck(lib.fdm_engine_create_from_point_cloud(n, *args, on_device, float(np.float32(resolution)), m, int(device),
-                                                    C.byref(h), C.byref(st)))
-    if rc != 0 or not h.value:
-        return None
-    return Engine._adopt(h)
-
-
-class DEMConfig:
-    """fastdem::DEMConfig (io/pcd_convert.hpp:28-42), with the reference's defaults."""
-
-    def __init__(self, resolution=0.1, method="max", sor_k=10, sor_std_mul=1.0, height_threshold=2.0, bin_size=0.0,
-                 inpaint_iterations=3):
-        self.resolution, self.method = resolution, method
-        self.sor_k, self.sor_std_mul = sor_k, sor_std_mul
-        self.height_threshold, self.bin_size = height_threshold, bin_size
-        self.inpaint_iterations = inpaint_iterations
-
-    def as_struct(self):
-        return FdmDemConfig(float(np.float32(self.resolution)), _raster_method(self.method), int(self.sor_k),
-                            float(np.float32(self.sor_std_mul)), float(np.float32(self.height_threshold)),
-                            float(np.float32(self.bin_size)), int(self.inpaint_iterations))
-
-
-def sor_last_stats():
-    """What this thread's last outlier removal did: n_queries, n_fallback (queries the brute-force queue took), grid_x,
-    grid_y, voxel, ms (grid build, search, fallback queue, statistics)."""
-    st = FdmSorStats()
-    _ck(capi.load().fdm_sor_last_stats(C.byref(st)))
-    return {"n_queries": int(st.n_queries), "n_fallback": int(st.n_fallback), "grid_x": int(st.grid_x),
-            "grid_y": int(st.grid_y), "voxel": float(st.voxel), "ms": tuple(float(v) for v in st.ms)}
-
-
-def statistical_outlier_removal(x, y, z, k=10, std_mul=1.0, device=0, return_details=False):
-    """nanopcl::filters::statisticalOutlierRemoval(cloud, k, std_mul) as a keep mask over the input points: bool[n] for
-    numpy arrays, a torch uint8 device tensor for torch device tensors.  return_details: (keep, mean_dist, threshold)
-    with mean_dist the per-point mean distance to its k nearest neighbours (float32) and threshold a np.float32."""
-    lib = capi.load()
-    thr, n_kept = C.c_float(0.0), C.c_uint64(0)
-    if _is_torch(x):
-        import torch
-        torch.cuda.current_stream().synchronize()
-        n = x.numel()
-        keep = torch.zeros(n, dtype=torch.uint8, device=x.device)
-        mean = torch.zeros(n, dtype=torch.float32, device=x.device)
-        _ck(lib.fdm_statistical_outlier_removal(n, _dptr(x), _dptr(y), _dptr(z), 1, int(k), float(np.float32(std_mul)),
-                                                int(device), _dptr(keep), _dptr(mean), C.byref(thr), C.byref(n_kept)))
-    else:
-        x, y, z = _f32(x), _f32(y), _f32(z)
-        n = x.size
-        keep8 = np.zeros(n, dtype=np.uint8)
-        mean = np.zeros(n, dtype=np.float32)
-        _ck(lib.fdm_statistical_outlier_removal(n, _ptr(x), _ptr(y), _ptr(z), 0, int(k), float(np.float32(std_mul)),
-                                                int(device), _ptr(keep8), _ptr(mean), C.byref(thr), C.byref(n_kept)))
-        assert int(keep8.sum()) == n_kept.value
-        keep = keep8.astype(bool)
-    return (keep, mean, np.float32(thr.value)) if return_details else keep
-
-
-def build_dem(x, y, z, intensity=None, rgb=None, config=None, device=0, return_stats=False):
-    """fastdem::buildDEM(cloud, config): outlier removal, floating-point removal, rasterization and inpainting on the
-    device.  Returns a map-only Engine, or None where the reference returns an uninitialised map (an empty cloud, a
-    cloud the outlier removal empties).  numpy arrays or torch device tensors.  return_stats: (engine, dict of
-    fdm_dem_stats)."""
-    lib = capi.load()
-    cfg = (config if config is not None else DEMConfig()).as_struct()
-    h, st = C.c_void_p(), FdmDemStats()
-    if _is_torch(x):
-        import torch
-        torch.cuda.current_stream().synchronize()
-        n, on_device = x.numel(), 1
-        args = [_dptr(v) for v in (x, y, z, intensity, rgb)]
-    else:
-        x, y, z = _f32(x), _f32(y), _f32(z)
-        keep = (x, y, z, _f32(intensity), _u32(rgb))
-        n, on_device = x.size, 0
-        args = [_ptr(v) for v in keep]
-    rc = _ck(lib.fdm_engine_build_dem(n, *args, on_device, C.byref(cfg), int(device), C.byref(h), C.byref(st)))
-    eng = Engine._adopt(h) if rc == 0 and h.value else None
-    if not return_stats:
-        return eng
-    stats = {"status": rc, "n_input": int(st.n_input), "n_after_sor": int(st.n_after_sor),
-             "n_after_height": int(st.n_after_height), "n_sor_fallback": int(st.n_sor_fallback),
-             "sor_threshold": np.float32(st.sor_threshold), "stage_ms": tuple(float(v) for v in st.stage_ms),
-             "n_points_used": int(st.raster.n_points_used), "n_cells_written": int(st.raster.n_cells_written)}
-    return eng, stats
-
-
-def _downsample(x, y, z, size, mode, intensity, rgb, normals, cov, order, device, return_index):
-    """fdm_cloud_voxel_grid (mode 0 .. 3) / fdm_cloud_grid_max_z (mode None) on numpy arrays or torch device tensors."""
-    lib = capi.load()
-    torch_in = _is_torch(x)
-    if normals is not None and not isinstance(normals, (tuple, list)):
-        normals = tuple(normals[:, k] for k in range(3))       # an (n, 3) array
-    if torch_in:
-        import torch
-        torch.cuda.current_stream(x.device).synchronize()
-        device = x.device.index if x.device.index is not None else torch.cuda.current_device()  # where the tensors live
-        n = x.numel()
-        given = {"x": x, "y": y, "z": z, "intensity": intensity, "rgb": rgb, "cov9": cov}
-        for k, v in zip(("nx", "ny", "nz"), normals or (None,) * 3):
-            given[k] = v
-        given = {k: (None if v is None else v.contiguous()) for k, v in given.items()}
-        outs = {k: torch.empty((n, 9) if k == "cov9" else n, dtype=v.dtype, device=x.device)
-                for k, v in given.items() if v is not None}
-        outs["idx"] = torch.empty(n, dtype=torch.int32, device=x.device)
-        ptr = _dptr
-    else:
-        x, y, z = _f32(x).reshape(-1), _f32(y).reshape(-1), _f32(z).reshape(-1)
-        n = x.size
-        given = {"x": x, "y": y, "z": z, "intensity": _f32(intensity), "rgb": _u32(rgb),
-                 "cov9": None if cov is None else _f32(cov).reshape(n, 9)}
-        for k, v in zip(("nx", "ny", "nz"), normals or (None,) * 3):
-            given[k] = _f32(v)
-        outs = {k: np.empty((n, 9) if k == "cov9" else n, dtype=v.dtype) for k, v in given.items() if v is not None}
-        outs["idx"] = np.empty(n, dtype=np.uint32)
-        ptr = _ptr
-    view = FdmCloudView(**{k: ptr(v) for k, v in given.items()})
-    out = FdmCloudOut(**{k: ptr(v) for k, v in outs.items()})
-    n_out = C.c_uint64(0)
-    size = float(np.float32(size))
-    if mode is None:
-        _ck(lib.fdm_cloud_grid_max_z(n, C.byref(view), int(torch_in), size, int(order), int(device), C.byref(out),
-                                     C.byref(n_out)))
-    else:
-        m = capi.VOXEL_MODE[mode.lower()] if isinstance(mode, str) else int(mode)
-        _ck(lib.fdm_cloud_voxel_grid(n, C.byref(view), int(torch_in), size, m, int(order), int(device), C.byref(out),
-                                     C.byref(n_out)))
-    k = int(n_out.value)
-    res = {name: v[:k] for name, v in outs.items()}
-    if "nx" in res:
-        res["normals"] = (res.pop("nx"), res.pop("ny"), res.pop("nz"))
-    if "cov9" in res:
-        res["cov"] = res.pop("cov9")
-    idx = res.pop("idx")
-    if return_index:
-        res["idx"] = (idx.long() & 0xFFFFFFFF) if torch_in else idx
-    return res
-
-
-def voxel_grid(x, y, z, voxel_size, mode="centroid", intensity=None, rgb=None, normals=None, cov=None, order=0,
-               device=0, return_index=False):
-    """nanopcl::filters::voxelGrid(cloud, voxel_size, mode) on the device: mode "centroid", "nearest", "any" or "center".
-    numpy arrays in, numpy arrays out; torch device tensors in, device tensors out (they can feed integrate_device or
-    from_point_cloud as they are).  normals: three arrays (nx, ny, nz) or one of shape (n, 3); cov: (n, 9).  Returns a
-    dict with "x", "y", "z" and the channels given ("intensity", "rgb", "normals" as a tuple of three, "cov");
-    return_index adds "idx", the input index each output point was copied from (centroid, center: the voxel's
-    representative).  order: 0 = ties in input order, 1 = the order std::sort leaves (engine option "voxel_any_order").
-    device: the ordinal numpy input runs on; torch tensors run on the device they live on."""
-    return _downsample(x, y, z, voxel_size, mode, intensity, rgb, normals, cov, order, device, return_index)
-
-
-def grid_max_z(x, y, z, grid_size, intensity=None, rgb=None, normals=None, cov=None, order=0, device=0,
-               return_index=False):
-    """nanopcl::filters::gridMaxZ(cloud, grid_size) on the device: per (x, y) cell the point with the largest z, every
-    channel that point's.  Arguments and result as voxel_grid."""
-    return _downsample(x, y, z, grid_size, None, intensity, rgb, normals, cov, order, device, return_index)
-
-
-def normals_last_stats():
-    """What this thread's last estimate_normals did: n_queries, n_fallback (queries the brute-force queue took),
-    n_invalid, grid_x, grid_y, voxel, ms (grid build, search, fallback queue, write; zeros unless
-    fdm_cloud_debug_profile is on)."""
-    st = FdmNormalStats()
-    _ck(capi.load().fdm_normals_last_stats(C.byref(st)))
-    return {"n_queries": int(st.n_queries), "n_fallback": int(st.n_fallback), "n_invalid": int(st.n_invalid),
-            "grid_x": int(st.grid_x), "grid_y": int(st.grid_y), "voxel": float(st.voxel),
-            "ms": tuple(float(v) for v in st.ms)}
-
-
-def estimate_normals(x, y, z, k=20, viewpoint=(0.0, 0.0, 0.0), covariances=False, device=0, return_stats=False):
-    """nanopcl::geometry::estimateNormals(cloud, k, viewpoint) on the device, or estimateNormalsCovariances with
-    covariances=True: per point the PCA of its k nearest points (itself included), the normal turned towards the
-    viewpoint, the covariance regularised for GICP to eigenvalues (1e-3, 1, 1).  numpy arrays in, numpy arrays out; torch
-    device tensors in, device tensors out.  Returns normals[n, 3], or (normals, cov[n, 3, 3]) with covariances; points
-    with fewer than 3 neighbours or a degenerate neighbourhood get a zero normal and the identity.  return_stats appends
-    normals_last_stats().  device: the ordinal numpy input runs on; torch tensors run on the device they live on."""
-    lib = capi.load()
-    vp = (C.c_float * 3)(*[float(np.float32(v)) for v in viewpoint])
-    n_invalid = C.c_uint64(0)
-    if _is_torch(x):
-        import torch
-        torch.cuda.current_stream(x.device).synchronize()
-        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        x, y, z = (v.contiguous() for v in (x, y, z))
-        n = x.numel()
-        soa = torch.empty((3, n), dtype=torch.float32, device=x.device)
-        cov9 = torch.empty((n, 9), dtype=torch.float32, device=x.device) if covariances else None
-        _ck(lib.fdm_cloud_estimate_normals(n, _dptr(x), _dptr(y), _dptr(z), 1, int(k), vp, int(device), _dptr(soa[0]),
-                                           _dptr(soa[1]), _dptr(soa[2]), _dptr(cov9), C.byref(n_invalid)))
-        normals = soa.t().contiguous()
-        cov = cov9.view(n, 3, 3).transpose(1, 2).contiguous() if covariances else None   # column-major -> [row][column]
-    else:
-        x, y, z = _f32(x).reshape(-1), _f32(y).reshape(-1), _f32(z).reshape(-1)
-        n = x.size
-        soa = np.empty((3, n), dtype=np.float32)
-        cov9 = np.empty((n, 9), dtype=np.float32) if covariances else None
-        _ck(lib.fdm_cloud_estimate_normals(n, _ptr(x), _ptr(y), _ptr(z), 0, int(k), vp, int(device), _ptr(soa[0]),
-                                           _ptr(soa[1]), _ptr(soa[2]), _ptr(cov9), C.byref(n_invalid)))
-        normals = np.ascontiguousarray(soa.T)
-        cov = np.ascontiguousarray(cov9.reshape(n, 3, 3).transpose(0, 2, 1)) if covariances else None
-    out = (normals, cov) if covariances else (normals,)
-    if return_stats:
-        out = out + (normals_last_stats(),)
-    return out[0] if len(out) == 1 else out
-
-
-class RegistrationResult:
-    """nanopcl::registration::RegistrationResult: transform (4 x 4, source -> target), fitness, rmse, iterations,
-    converged and covariance (6 x 6 in [v; omega] order, or None)."""
-
-    __slots__ = ("transform", "fitness", "rmse", "iterations", "converged", "covariance")
-
-    def __init__(self, transform, fitness, rmse, iterations, converged, covariance):
-        self.transform, self.fitness, self.rmse = transform, fitness, rmse
-        self.iterations, self.converged, self.covariance = iterations, converged, covariance
-
-    def success(self, min_fitness=0.5):
-        return self.converged and self.fitness >= min_fitness
-
-    def information_matrix(self):
-        return None if self.covariance is None else np.linalg.inv(self.covariance)
-
-    def __repr__(self):
-        return (f"RegistrationResult(fitness={self.fitness:.4g}, rmse={self.rmse:.4g}, iterations={self.iterations}, "
-                f"converged={self.converged}, covariance={'yes' if self.covariance is not None else 'None'})")
-
-
-def align_settings(**settings):
-    """fdm_align_settings with AlignSettings' defaults and the given fields: max_correspondence_dist, max_iterations,
-    translation_eps, rotation_eps, relative_error_eps, min_correspondences, robust_kernel ("none", "huber", "tukey",
-    "cauchy" or its number), robust_kernel_width, covariance_epsilon."""
-    st = capi.FdmAlignSettings()
-    capi.load().fdm_default_align_settings(C.byref(st))
-    names = {f[0] for f in capi.FdmAlignSettings._fields_} - {"reserved"}
-    for key, value in settings.items():
-        if key not in names:
-            raise TypeError(f"unknown registration setting {key!r}")
-        if key == "robust_kernel" and isinstance(value, str):
-            value = capi.ROBUST_KERNEL[value.lower()]
-        setattr(st, key, value)
-    return st
-
-
-def _cov_colmajor(cov, n):
-    """n covariances indexed [row][column] (a NumPy array or a torch tensor, or None) as (n, 3, 3) column-major, contiguous."""
-    if cov is None:
-        return None
-    if _is_torch(cov):
-        return cov.reshape(n, 3, 3).transpose(1, 2).contiguous()
-    return np.ascontiguousarray(cov.reshape(n, 3, 3).transpose(0, 2, 1))
-
-
-def _registration_result(res):
-    """RegistrationResult of an FdmRegistrationResult."""
-    T = np.array(res.transform, dtype=np.float64).reshape(4, 4).T.copy()
-    cov = np.array(res.covariance, dtype=np.float64).reshape(6, 6) if res.has_covariance else None
-    return RegistrationResult(T, float(res.fitness), float(res.rmse), int(res.iterations), bool(res.converged), cov)
-
-
-def _linearized(entry, n, like, return_correspondences):
-    """The outputs of one linearize entry: makes H, b, error, num_inliers and (asked for) corr — n int32 where the clouds
-    live: on the device of the tensor `like`, or in a NumPy array for `like` None —, calls entry(H, b, error, num_inliers,
-    corr) and returns the result dict."""
-    H, b = (C.c_double * 21)(), (C.c_double * 6)()
-    err, cnt = C.c_double(0.0), C.c_uint64(0)
-    corr = None
-    if return_correspondences:
-        if like is not None:
-            import torch
-            corr = torch.empty(n, dtype=torch.int32, device=like.device)
-        else:
-            corr = np.empty(n, dtype=np.int32)
-    _ck(entry(H, b, C.byref(err), C.byref(cnt), (_ptr if like is None else _dptr)(corr)))
-    Hu = np.array(H, dtype=np.float64)
-    full = np.zeros((6, 6))
-    full[np.triu_indices(6)] = Hu
-    full = full + np.triu(full, 1).T
-    out = {"H": full, "H_upper": Hu, "b": np.array(b, dtype=np.float64), "error": float(err.value),
-           "num_inliers": int(cnt.value)}
-    if return_correspondences:
-        out["corr"] = corr
-    return out
-
-
-def _register_clouds(source, target, target_normals, source_cov, target_cov):
-    """(FdmRegisterClouds, device or None, the arrays it points into) for numpy arrays or torch device tensors."""
-    sx, sy, sz = source
-    tx, ty, tz = target
-    torch_in = _is_torch(sx)
-    if torch_in:
-        import torch
-        torch.cuda.current_stream(sx.device).synchronize()
-        device = sx.device.index if sx.device.index is not None else torch.cuda.current_device()
-
-        def prep(v):
-            if v is None:
-                return None
-            if not _is_torch(v) or v.dtype != torch.float32 or v.device != sx.device:
-                raise TypeError("registration takes float32 tensors that all live on the source's device "
-                                "(or NumPy arrays throughout)")
-            return v.contiguous()
-        ptr, size = _dptr, lambda v: v.numel()                                     # noqa: E731
-    else:
-        device = None
-
-        def prep(v):
-            if _is_torch(v):
-                raise TypeError("registration takes NumPy arrays throughout or torch device tensors throughout")
-            return None if v is None else _f32(v).reshape(-1)
-        ptr, size = _ptr, lambda v: v.size                                         # noqa: E731
-    if target_normals is not None and not isinstance(target_normals, (tuple, list)):
-        target_normals = tuple(target_normals[:, k] for k in range(3))              # an (n, 3) array
-    keep = [prep(v) for v in (sx, sy, sz, tx, ty, tz)] + [prep(v) for v in (target_normals or (None,) * 3)]
-    ns, nt = size(keep[0]), size(keep[3])
-    keep += [_cov_colmajor(prep(source_cov), ns), _cov_colmajor(prep(target_cov), nt)]
-    p = [ptr(v) for v in keep]
-    clouds = capi.FdmRegisterClouds(ns, p[0], p[1], p[2], p[9], nt, p[3], p[4], p[5], p[6], p[7], p[8], p[10],
-                                    int(torch_in))
-    return clouds, device, keep
-
-
-def _guess16(T):
-    return None if T is None else (C.c_double * 16)(*_colmajor16(T))
-
-
-def _register(method, source, target, initial_guess, target_normals, source_cov, target_cov, device, settings):
-    clouds, dev, keep = _register_clouds(source, target, target_normals, source_cov, target_cov)
-    st = settings.pop("settings", None) or align_settings(**settings)
-    res = capi.FdmRegistrationResult()
-    _ck(capi.load().fdm_cloud_register(capi.REGISTER_METHOD[method], C.byref(clouds), _guess16(initial_guess),
-                                       C.byref(st), int(device if dev is None else dev), C.byref(res)))
-    del keep
-    return _registration_result(res)
-
-
-def align_icp(sx, sy, sz, tx, ty, tz, initial_guess=None, device=0, **settings):
-    """nanopcl::registration::alignICP(source, target, initial_guess, settings) on the device: point-to-point ICP.
-    numpy arrays or torch device tensors (they run on the device they live on); initial_guess a 4 x 4 matrix (None = the
-    identity); settings: the fields of AlignSettings by name (align_settings).  Returns a RegistrationResult."""
-    return _register("icp", (sx, sy, sz), (tx, ty, tz), initial_guess, None, None, None, device, settings)
-
-
-def align_plane_icp(sx, sy, sz, tx, ty, tz, target_normals, initial_guess=None, device=0, **settings):
-    """alignPlaneICP: point-to-plane ICP against the target's normals (three arrays or one of shape (n, 3), e.g. from
-    estimate_normals).  Otherwise as align_icp."""
-    return _register("plane", (sx, sy, sz), (tx, ty, tz), initial_guess, target_normals, None, None, device, settings)
-
-
-def align_gicp(sx, sy, sz, tx, ty, tz, source_cov, target_cov, initial_guess=None, device=0, **settings):
-    """alignGICP: generalized ICP with both clouds' covariances, (n, 3, 3) indexed [row][column] as
-    estimate_normals(..., covariances=True) returns them.  Otherwise as align_icp."""
-    return _register("gicp", (sx, sy, sz), (tx, ty, tz), initial_guess, None, source_cov, target_cov, device, settings)
-
-
-def linearize(method, sx, sy, sz, tx, ty, tz, transform=None, target_normals=None, source_cov=None, target_cov=None,
-              device=0, return_correspondences=False, **settings):
-    """One linearization of `method` ("icp", "plane", "gicp") at `transform` — the reference's linearizer: a dict with H
-    (6 x 6, symmetric), H_upper (21), b (6), error and num_inliers; return_correspondences adds "corr", the target index
-    of every source point (-1 for none)."""
-    clouds, dev, keep = _register_clouds((sx, sy, sz), (tx, ty, tz), target_normals, source_cov, target_cov)
-    st = settings.pop("settings", None) or align_settings(**settings)
-    lib, number = capi.load(), capi.REGISTER_METHOD[method]
-    return _linearized(lambda *out: lib.fdm_cloud_register_linearize(number, C.byref(clouds), _guess16(transform),
-                                                                     C.byref(st), int(device if dev is None else dev), *out),
-                       int(clouds.n_source), keep[0] if clouds.on_device else None, return_correspondences)
-
-
-def register_last_stats():
-    """What this thread's last registration call did: n_source, n_target, grid_x, grid_y, voxel (the target's search
-    grid), ring_limit, linearizations, ms (grid build, regularisation, the linearizations summed; zeros unless
-    fdm_cloud_debug_profile is on)."""
-    st = capi.FdmRegisterStats()
-    _ck(capi.load().fdm_register_last_stats(C.byref(st)))
-    return {"n_source": int(st.n_source), "n_target": int(st.n_target), "grid_x": int(st.grid_x), "grid_y": int(st.grid_y),
-            "voxel": float(st.voxel), "ring_limit": int(st.ring_limit), "linearizations": int(st.linearizations),
-            "ms": tuple(float(v) for v in st.ms)}
-
-
-# ---- voxelized GICP (fdm_voxel_map_* / fdm_cloud_register_vgicp: include/fdm_engine.h) ----
-class VoxelMap:
-    """nanopcl::registration::VoxelDistributionMap on the device: per-voxel means and covariances of a target cloud, built
-    once and registered against any number of times (align_vgicp, linearize_vgicp).  x, y, z: NumPy arrays, or torch
-    device tensors (the map then lives on their device).  Owns device memory until close() (or the end of a `with`)."""
-
-    def __init__(self, x, y, z, resolution=1.0, covariance_epsilon=1e-3, device=0):
-        self._h = None
-        n, p, on_device, dev, keep, _ = _seg_cloud(x, y, z, device)
-        h = C.c_void_p()
-        _ck(capi.load().fdm_voxel_map_create(n, p[0], p[1], p[2], on_device, float(resolution),
-                                             float(covariance_epsilon), int(dev), C.byref(h)))
-        del keep
-        self._h = h
-
-    def close(self):
-        h, self._h = self._h, None
-        if h:
-            capi.load().fdm_voxel_map_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _handle(self):
-        if not self._h:
-            raise EngineError("the voxel map is closed")
-        return self._h
-
-    def info(self):
-        """dict: resolution, inv_resolution, covariance_epsilon, device, n_points, n_skipped (not finite), num_voxels,
-        n_sparse (fewer than 3 points), max_count, table_slots, max_probe, ms (keys + sort, reduce + regularise, hash:
-        zeros unless fdm_cloud_debug_profile was on)."""
-        st = capi.FdmVoxelMapInfo()
-        _ck(capi.load().fdm_voxel_map_get_info(self._handle(), C.byref(st)))
-        out = {k: getattr(st, k) for k in ("resolution", "inv_resolution", "covariance_epsilon", "device", "n_points",
-                                           "n_skipped", "num_voxels", "n_sparse", "max_count", "table_slots",
-                                           "max_probe")}
-        out["ms"] = tuple(float(v) for v in st.ms)
-        return out
-
-    def __len__(self):
-        return int(self.info()["num_voxels"])
-
-    def records(self):
-        """dict of NumPy arrays in ascending key order: key uint64[m], count uint32[m], mean float32[m, 3], cov
-        float32[m, 3, 3] and creg float64[m, 3, 3] (the regularised covariance), both indexed [row][column]."""
-        m = len(self)
-        key, count = np.empty(m, dtype=np.uint64), np.empty(m, dtype=np.uint32)
-        mean, cov9 = np.empty((m, 3), dtype=np.float32), np.empty((m, 9), dtype=np.float32)
-        c6 = np.empty((m, 6), dtype=np.float64)
-        _ck(capi.load().fdm_voxel_map_records(self._handle(), 0, _ptr(key), _ptr(mean), _ptr(cov9), _ptr(c6), _ptr(count)))
-        creg = c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(m, 3, 3)
-        return {"key": key, "count": count, "mean": mean,
-                "cov": np.ascontiguousarray(cov9.reshape(m, 3, 3).transpose(0, 2, 1)), "creg": np.ascontiguousarray(creg)}
-
-
-def _vgicp_source(sx, sy, sz, source_cov, device):
-    """(n, pointers of x y z cov9, on_device, the arrays kept alive) of a NumPy or torch device source cloud."""
-    n, p, on_device, _, keep, torch = _seg_cloud(sx, sy, sz, device)
-    cov = None
-    if source_cov is not None:
-        if torch is not None and (not _is_torch(source_cov) or source_cov.device != keep[0].device):
-            raise TypeError("registration takes float32 tensors that all live on the source's device "
-                            "(or NumPy arrays throughout)")
-        cov = _cov_colmajor(source_cov.float() if torch is not None else _f32(source_cov), n)
-    return n, p + [(_dptr if on_device else _ptr)(cov)], on_device, keep + (cov,)
-
-
-def _vgicp_map(voxel_map, target, voxel_resolution, st, device):
-    """(the map to use, whether it is this call's to close)."""
-    if (voxel_map is None) == (target is None):
-        raise TypeError("give exactly one of voxel_map and target")
-    if voxel_map is not None:
-        return voxel_map, False
-    tx, ty, tz = target
-    return VoxelMap(tx, ty, tz, voxel_resolution, st.covariance_epsilon, device), True
-
-
-def align_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_resolution=1.0, initial_guess=None, device=0,
-                **settings):
-    """nanopcl::registration::alignVGICP on the device.  Give a prebuilt VoxelMap (the fast path: one lookup per point
-    and iteration), or target=(tx, ty, tz), which builds a map of voxel_resolution with settings' covariance_epsilon for
-    this call alone.  source_cov: (n, 3, 3) indexed [row][column].  max_correspondence_dist is not used.  Otherwise as
-    align_icp."""
-    st = settings.pop("settings", None) or align_settings(**settings)
-    vmap, mine = _vgicp_map(voxel_map, target, voxel_resolution, st, device)
-    try:
-        n, p, on_device, keep = _vgicp_source(sx, sy, sz, source_cov, device)
-        res = capi.FdmRegistrationResult()
-        _ck(capi.load().fdm_cloud_register_vgicp(vmap._handle(), n, p[0], p[1], p[2], p[3], on_device,
-                                                 _guess16(initial_guess), C.byref(st), C.byref(res)))
-        del keep
-    finally:
-        if mine:
-            vmap.close()
-    return _registration_result(res)
-
-
-def linearize_vgicp(sx, sy, sz, source_cov, voxel_map=None, target=None, voxel_resolution=1.0, transform=None, device=0,
-                    return_correspondences=False, **settings):
-    """One VGICP linearization at `transform`, shaped like linearize: H, H_upper, b, error, num_inliers, and with
-    return_correspondences "corr": every source point's voxel as its rank in ascending key order (-1 for none)."""
-    st = settings.pop("settings", None) or align_settings(**settings)
-    vmap, mine = _vgicp_map(voxel_map, target, voxel_resolution, st, device)
-    try:
-        n, p, on_device, keep = _vgicp_source(sx, sy, sz, source_cov, device)
-        lib = capi.load()
-        return _linearized(lambda *out: lib.fdm_cloud_register_vgicp_linearize(vmap._handle(), n, p[0], p[1], p[2], p[3],
-                                                                               on_device, _guess16(transform),
-                                                                               C.byref(st), *out),
-                           n, keep[0] if on_device else None, return_correspondences)
-    finally:
-        if mine:
-            vmap.close()
-
-
-# ---- cloud segmentation (fdm_cloud_segment_ground / _plane / _planes: include/fdm_engine.h) ----
-def _seg_cloud(x, y, z, device):
-    """(n, pointers of x y z, on_device, device, the arrays kept alive, torch module or None)."""
-    if _is_torch(x):
-        import torch
-        torch.cuda.current_stream(x.device).synchronize()
-        dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        keep = tuple(v.contiguous().float() for v in (x, y, z))
-        return keep[0].numel(), [_dptr(v) for v in keep], 1, dev, keep, torch
-    keep = tuple(_f32(v).reshape(-1) for v in (x, y, z))
-    return keep[0].size, [_ptr(v) for v in keep], 0, int(device), keep, None
-
-
-def _seg_u32(torch, n, like):
-    """An index array of capacity n where the cloud lives; (array, pointer)."""
-    if torch is not None:
-        a = torch.zeros(max(n, 1), dtype=torch.int32, device=like.device)
-        return a, _dptr(a)
-    a = np.zeros(max(n, 1), dtype=np.uint32)
-    return a, _ptr(a)
-
-
-def _seg_take(torch, a, k):
-    return (a[:k].long() & 0xFFFFFFFF) if torch is not None else a[:k].copy()
-
-
-def segment_ground(x, y, z, grid_resolution=0.5, cell_percentile=0.2, ground_thickness=0.3, max_ground_height=0.5,
-                   min_points_per_cell=2, device=0):
-    """nanopcl::segmentation::segmentGround(cloud, config) on the device: (ground, obstacles), the point indices of each
-    in ascending order — uint32 numpy arrays for numpy input, int64 device tensors for torch device tensors."""
-    lib = capi.load()
-    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
-    cfg = capi.FdmGroundSegConfig(float(np.float32(grid_resolution)), float(np.float32(cell_percentile)),
-                                  float(np.float32(ground_thickness)), float(np.float32(max_ground_height)),
-                                  int(min_points_per_cell))
-    ground, pg = _seg_u32(torch, n, keep[0])
-    obstacles, po = _seg_u32(torch, n, keep[0])
-    ng, no = C.c_uint64(0), C.c_uint64(0)
-    _ck(lib.fdm_cloud_segment_ground(n, *ptrs, on_device, C.byref(cfg), dev, pg, po, C.byref(ng), C.byref(no)))
-    return _seg_take(torch, ground, int(ng.value)), _seg_take(torch, obstacles, int(no.value))
-
-
-class RansacResult:
-    """nanopcl::segmentation::RansacResult: coefficients (float32[4]: nx, ny, nz, d), inliers (indices into the cloud, in
-    index-list order), fitness, iterations, success."""
-
-    def __init__(self, coefficients, inliers, fitness, iterations, success):
-        self.coefficients, self.inliers = coefficients, inliers
-        self.fitness, self.iterations, self.success = float(fitness), int(iterations), bool(success)
-
-    def outliers(self, total):
-        """RansacResult::outliers(total_points): the indices 0 .. total - 1 that are no inlier, ascending."""
-        if _is_torch(self.inliers):
-            import torch
-            mask = torch.ones(int(total), dtype=torch.bool, device=self.inliers.device)
-            mask[self.inliers] = False
-            return torch.nonzero(mask).reshape(-1)
-        mask = np.ones(int(total), dtype=bool)
-        mask[self.inliers] = False
-        return np.nonzero(mask)[0].astype(np.uint32)
-
-    def __repr__(self):
-        return (f"RansacResult(success={self.success}, coefficients={self.coefficients.tolist()}, "
-                f"inliers={len(self.inliers)}, fitness={self.fitness:.6f}, iterations={self.iterations})")
-
-
-def _ransac_config(distance_threshold, max_iterations, probability, min_inliers, refine_model):
-    return capi.FdmRansacConfig(float(np.float32(distance_threshold)), int(max_iterations), float(probability),
-                                int(min_inliers), 1 if refine_model else 0)
-
-
-def _ransac_result(torch, r, inliers):
-    return RansacResult(np.array(r.coefficients, dtype=np.float32), _seg_take(torch, inliers, int(r.n_inliers)),
-                        r.fitness, r.iterations, r.success)
-
-
-def segment_plane(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, min_inliers=3,
-                  refine_model=True, indices=None, device=0):
-    """nanopcl::segmentation::segmentPlane (RANSAC, fixed seed) over the whole cloud or over `indices` (positions are
-    sampled in that list, which may repeat a point).  Returns a RansacResult; its inliers are a uint32 numpy array for
-    numpy input, an int64 device tensor for torch device tensors."""
-    lib = capi.load()
-    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
-    cfg = _ransac_config(distance_threshold, max_iterations, probability, min_inliers, refine_model)
-    p_idx, m, idx = None, n, None
-    if indices is not None:
-        if torch is not None:
-            idx = indices.to(device=keep[0].device, dtype=torch.int64).to(torch.int32).contiguous()
-            p_idx, m = _dptr(idx), idx.numel()
-        else:
-            idx = np.ascontiguousarray(np.asarray(indices).astype(np.uint32)).reshape(-1)
-            p_idx, m = _ptr(idx), idx.size
-    inliers, pi = _seg_u32(torch, m, keep[0])
-    r = capi.FdmRansacResult()
-    _ck(lib.fdm_cloud_segment_plane(n, *ptrs, on_device, p_idx, m, C.byref(cfg), dev, pi, C.byref(r)))
-    del idx
-    return _ransac_result(torch, r, inliers)
-
-
-def segment_multiple_planes(x, y, z, distance_threshold=0.1, max_iterations=1000, probability=0.99, min_inliers=3,
-                            refine_model=True, max_planes=5, min_fitness=0.1, device=0):
-    """nanopcl::segmentation::segmentMultiplePlanes: planes are taken one after the other, each from the points the
-    earlier ones left, until max_planes, fewer than 3 points, or a result without success or below min_fitness.
-    Returns a list of RansacResult."""
-    lib = capi.load()
-    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
-    cfg = _ransac_config(distance_threshold, max_iterations, probability, min_inliers, refine_model)
-    inliers, pi = _seg_u32(torch, n, keep[0])
-    res = (capi.FdmRansacResult * max(int(max_planes), 1))()
-    count = C.c_uint64(0)
-    _ck(lib.fdm_cloud_segment_planes(n, *ptrs, on_device, C.byref(cfg), int(max_planes), float(min_fitness), dev, pi, res,
-                                     C.byref(count)))
-    out, at = [], 0
-    for k in range(int(count.value)):
-        out.append(_ransac_result(torch, res[k], inliers[at:]))
-        at += int(res[k].n_inliers)
-    return out
-
-
-def segment_last_stats():
-    """What this thread's last segmentation call did: n_batches (launches of the scoring kernel), n_hypotheses,
-    n_invalid_samples, batch (iterations per launch), ms (zeros unless fdm_cloud_debug_profile is on)."""
-    st = capi.FdmSegmentStats()
-    _ck(capi.load().fdm_segment_last_stats(C.byref(st)))
-    return {"n_batches": int(st.n_batches), "n_hypotheses": int(st.n_hypotheses),
-            "n_invalid_samples": int(st.n_invalid_samples), "batch": int(st.batch), "ms": tuple(float(v) for v in st.ms)}
-
-
-# ---- Euclidean clustering (fdm_cloud_cluster: include/fdm_engine.h) ----
-class ClusterResult:
-    """nanopcl::segmentation::ClusterResult in CSR form: indices (every clustered point's index into the cloud, cluster
-    after cluster), offsets (num_clusters + 1 boundaries), and labels (per list position 0 = noise, else cluster number
-    + 1).  Kept clusters come in descending size, equal sizes by their smallest list position; inside a cluster the list
-    positions ascend.  uint32 numpy arrays for numpy input, int64 device tensors for torch device tensors."""
-
-    def __init__(self, indices, offsets, labels):
-        self.indices, self.offsets, self.labels = indices, offsets, labels
-
-    @property
-    def num_clusters(self):
-        return max(len(self.offsets) - 1, 0)
-
-    def __len__(self):
-        return self.num_clusters
-
-    @property
-    def total_clustered_points(self):
-        return len(self.indices)
-
-    def cluster_size(self, i):
-        return int(self.offsets[i + 1]) - int(self.offsets[i])
-
-    def cluster_indices(self, i):
-        """ClusterResult::clusterIndices(i): a view, no copy."""
-        return self.indices[int(self.offsets[i]):int(self.offsets[i + 1])]
-
-    def cluster_sizes(self):
-        return self.offsets[1:] - self.offsets[:-1]
-
-    def noise_indices(self, total):
-        """ClusterResult::noiseIndices(total_points): the indices 0 .. total - 1 in no cluster, ascending."""
-        if _is_torch(self.indices):
-            import torch
-            mask = torch.ones(int(total), dtype=torch.bool, device=self.indices.device)
-            mask[self.indices] = False
-            return torch.nonzero(mask).reshape(-1)
-        mask = np.ones(int(total), dtype=bool)
-        mask[self.indices] = False
-        return np.nonzero(mask)[0].astype(np.uint32)
-
-    def __repr__(self):
-        return f"ClusterResult(num_clusters={self.num_clusters}, total_clustered_points={self.total_clustered_points})"
-
-
-def euclidean_cluster(x, y, z, indices=None, tolerance=0.5, min_size=10, max_size=100000, device=0):
-    """nanopcl::segmentation::euclideanCluster on the device over the whole cloud or over `indices` (the values written
-    are then the list's entries, i.e. indices into the cloud; a duplicate entry counts as two points).  Returns a
-    ClusterResult; the relation and the order are stated in include/fdm_engine.h."""
-    lib = capi.load()
-    n, ptrs, on_device, dev, keep, torch = _seg_cloud(x, y, z, device)
-    cfg = capi.FdmClusterConfig(float(np.float32(tolerance)), int(min_size), int(max_size))
-    p_idx, m, idx = None, n, None
-    if indices is not None:
-        if torch is not None:
-            idx = indices.to(device=keep[0].device, dtype=torch.int64).to(torch.int32).contiguous()
-            p_idx, m = _dptr(idx), idx.numel()
-        else:
-            idx = np.ascontiguousarray(np.asarray(indices).astype(np.uint32)).reshape(-1)
-            p_idx, m = _ptr(idx), idx.size
-    out, po = _seg_u32(torch, m, keep[0])
-    offsets, pf = _seg_u32(torch, m + 1, keep[0])
-    labels, pl = _seg_u32(torch, m, keep[0])
-    count = C.c_uint64(0)
-    _ck(lib.fdm_cloud_cluster(n, *ptrs, on_device, p_idx, m, C.byref(cfg), dev, po, pf, pl, C.byref(count)))
-    del idx
-    k = int(count.value)
-    off = _seg_take(torch, offsets, k + 1)
-    return ClusterResult(_seg_take(torch, out, int(off[k])), off, _seg_take(torch, labels, m))
-
-
-def apply_cluster_labels(result, total, semantic_class=0):
-    """nanopcl::segmentation::applyClusterLabels: the uint32 Label channel of a cloud of `total` points,
-    (semantic_class << 16) | uint16(cluster number + 1) for a clustered point — the instance id truncated to 16 bits as
-    in the reference — and (semantic_class << 16) for noise.  A numpy array."""
-    sem = np.uint32((int(semantic_class) & 0xFFFF) << 16)
-    out = np.full(int(total), sem, dtype=np.uint32)
-    ind = result.indices.cpu().numpy() if _is_torch(result.indices) else np.asarray(result.indices)
-    off = result.offsets.cpu().numpy() if _is_torch(result.offsets) else np.asarray(result.offsets)
-    if ind.size:
-        sizes = np.diff(off.astype(np.int64))
-        ids = (np.arange(sizes.size, dtype=np.int64) + 1) & 0xFFFF
-        out[ind.astype(np.int64)] = sem | np.repeat(ids, sizes).astype(np.uint32)
-    return out
-
-
-def cluster_last_stats():
-    """What this thread's last euclidean_cluster did: the counts of fdm_cluster_stats and ms (zeros unless
-    fdm_cloud_debug_profile is on)."""
-    st = capi.FdmClusterStats()
-    _ck(capi.load().fdm_cluster_last_stats(C.byref(st)))
-    out = {k: int(getattr(st, k)) for k, _ in capi.FdmClusterStats._fields_ if k != "ms"}
-    out["ms"] = tuple(float(v) for v in st.ms)
-    return out

@@ -8,7 +8,9 @@ import numpy as np
 
 from . import capi
 from .capi import FdmDemStats, FdmPcdHeader
-from .engine import DEMConfig, Engine, _ck, _dptr, _is_torch, _ptr
+from ._arrays import arrays, outputs
+from .cloud import DEMConfig
+from .engine import Engine, _ck, _ptr
 
 ASCII, BINARY = capi.PCD_ASCII, capi.PCD_BINARY
 CHANNELS = ("x", "y", "z", "intensity", "rgb", "nx", "ny", "nz")
@@ -50,25 +52,14 @@ def decode(h, body, device=None, body_ptr=None, body_bytes=None):
     has = present(h) if n else dict.fromkeys(CHANNELS, False)
     for k in "xyz":
         has[k] = True
-    out, args = {}, []
-    if device is None:
-        for k in CHANNELS:
-            out[k] = np.zeros(n, dtype=np.uint32 if k == "rgb" else np.float32) if has[k] else None
-            args.append(_ptr(out[k]))
-    else:
-        import torch
-        for k in CHANNELS:
-            out[k] = torch.zeros(n, dtype=torch.int32 if k == "rgb" else torch.float32, device=f"cuda:{device}") \
-                if has[k] else None
-            args.append(_dptr(out[k]))
-        torch.cuda.synchronize(device)
+    A = outputs(device)
+    out = {k: A.zeros(n, "u32" if k == "rgb" else "f32") if has[k] else None for k in CHANNELS}
     if body_ptr is not None:
         src, size, on_device = C.c_void_p(body_ptr), int(body_bytes), 1
     else:
         keep = np.frombuffer(body, dtype=np.uint8)
         src, size, on_device = _ptr(keep) if keep.size else None, keep.size, 0
-    _ck(lib.fdm_pcd_decode(C.byref(h), src, size, on_device, *args, 0 if device is None else 1,
-                           0 if device is None else int(device)))
+    _ck(lib.fdm_pcd_decode(C.byref(h), src, size, on_device, *[A.ptr(out[k]) for k in CHANNELS], A.on_device, A.device))
     return out
 
 
@@ -85,30 +76,19 @@ def load_pcd(path, device=None, return_header=False):
 def encode(cloud, fmt=BINARY, precision=8, device=0):
     """savePCD's data section for a dict of NumPy arrays or torch device tensors (absent channels None or missing)."""
     lib = capi.load()
-    x = cloud["x"]
-    on_device = _is_torch(x)
-    vals = [cloud.get(k) for k in CHANNELS]
-    if on_device:
-        import torch
-        torch.cuda.current_stream().synchronize()
-        n = x.numel()
-        args = [_dptr(v) for v in vals]
-    else:
-        vals = [None if v is None else np.ascontiguousarray(v, dtype=np.uint32 if k == "rgb" else np.float32)
-                for k, v in zip(CHANNELS, vals)]
-        n = vals[0].size
-        args = [_ptr(v) for v in vals]
+    A = arrays(cloud["x"], device)
+    vals = [A.u32(cloud.get(k)) if k == "rgb" else A.f32(cloud.get(k)) for k in CHANNELS]
+    n = A.n
+    call = (n, *[A.ptr(v) for v in vals], A.on_device, int(fmt), int(precision), A.device)
     need = C.c_uint64(0)
     words = sum(v is not None for v in vals)
     cap = n * words * 4 if fmt == BINARY else 0
     buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = _ck(lib.fdm_pcd_encode(n, *args, int(on_device), int(fmt), int(precision), int(device), _ptr(buf), cap,
-                                C.byref(need)))
+    rc = _ck(lib.fdm_pcd_encode(*call, _ptr(buf), cap, C.byref(need)))
     if rc == capi.FDM_SKIP_BUFFER_TOO_SMALL:                  # ASCII: the size is known once the text exists
         cap = need.value
         buf = np.empty(max(cap, 1), dtype=np.uint8)
-        rc = _ck(lib.fdm_pcd_encode(n, *args, int(on_device), int(fmt), int(precision), int(device), _ptr(buf), cap,
-                                    C.byref(need)))
+        rc = _ck(lib.fdm_pcd_encode(*call, _ptr(buf), cap, C.byref(need)))
     assert rc == 0, rc
     return buf[:need.value].tobytes()
 
@@ -116,7 +96,7 @@ def encode(cloud, fmt=BINARY, precision=8, device=0):
 def save_pcd(path, cloud, fmt=BINARY, precision=8, viewpoint=None, device=0):
     """nanopcl::io::savePCD(path, cloud, options)."""
     has = {k: cloud.get(k) is not None for k in CHANNELS}
-    n = cloud["x"].numel() if _is_torch(cloud["x"]) else np.asarray(cloud["x"]).size
+    n = arrays(cloud["x"], device).n
     head = write_header(n, has["intensity"], has["rgb"], has["nx"] and has["ny"] and has["nz"], viewpoint, fmt)
     body = encode(cloud, fmt, precision, device)
     with open(path, "wb") as f:
